@@ -34,6 +34,9 @@ secondary figure only (`event_us`; an EMPTY kernel reads ~4 us through them: `ev
                     torch CPU ops; thread count swept, best reported, plus the matmul-only variant), rank 0, N=1 only.
 
 Other workloads (development / profiles): --workload a16w4_4096_m256 | a16w4_8192_m256 | a16w2_16384_m1 ... [--single]
+--dump-outputs DIR: after the timed steps, every layer's output of the last timed step as float32 DIR/out.npy [layers, M, N], or, past
+64 MB, a fixed seeded sample of the same positions in every layer (DIR/out_sample.npy + DIR/out_sample_index.npy).  Inputs are seeded:
+the same arguments give the same inputs, so two builds can be compared output for output.
 Multi-GPU: the path does not shard (SURVEY.md §8 e) -> N independent replicas, no collective in the data path.
 """
 import argparse
@@ -220,10 +223,11 @@ class Runner:
         torch.cuda.synchronize()
         self.graph = self.chain_graph = None
         self.chain_reps = 1
+        self.outs = []  # what the last run_step() returned to the caller, one tensor per layer (the graph's static outputs when replayed)
         if use_graph:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=self.stream):
-                self.step_eager()
+                self.outs = self.step_eager()
             # chained timing: one graph replay costs the host / command processor ~10 us whatever it holds (guide row
             # graph-replay-floor), so short steps (2 .. 8 launches) are repeated inside ONE graph until it holds >= 32 launches
             self.chain_reps = max(1, -(-32 // self.layers))
@@ -244,15 +248,14 @@ class Runner:
         return lin.forward_manual(self.x, self.matmul_type) if self.matmul_type else lin(self.x)
 
     def step_eager(self):
-        for lin in self.mods:
-            self.call(lin)
+        return [self.call(lin) for lin in self.mods]
 
     def run_step(self):
         if self.graph is not None:
             self.graph.replay()
         else:
             with torch.cuda.stream(self.stream):
-                self.step_eager()
+                self.outs = self.step_eager()
 
     def run_chain(self):
         if self.chain_graph is not None:
@@ -437,6 +440,34 @@ def empty_launch_period_us(lib, stream, n=64, min_seconds=0.05):
     return (time.perf_counter() - t0) / (reps * n) * 1e6
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 0
+
+
+def dump_outputs(outs, directory):
+    """Write the per-layer outputs of the last timed step as float32 .npy files under `directory`.
+    Stacked [layers, M, N] as `out.npy` when that fits DUMP_LIMIT_BYTES; otherwise the same seeded sample of flat positions of
+    every layer as `out_sample.npy` [layers, S], with the positions (row * N + col) in `out_sample_index.npy` (float64, exact)."""
+    os.makedirs(directory, exist_ok=True)
+    for f in ("out.npy", "out_sample.npy", "out_sample_index.npy"):  # never leave a file of an earlier dump of another shape behind
+        if os.path.exists(os.path.join(directory, f)):
+            os.remove(os.path.join(directory, f))
+    ys = [y.reshape(-1, y.shape[-1]) for y in outs]
+    L, (M, N) = len(ys), ys[0].shape
+    slack = 4096  # two .npy headers
+    if L * M * N * 4 + slack <= DUMP_LIMIT_BYTES:
+        arr = torch.stack([y.float() for y in ys]).cpu().numpy()
+        np.save(os.path.join(directory, "out.npy"), arr)
+        return {"out": list(arr.shape)}
+    S = (DUMP_LIMIT_BYTES - slack) // (4 * L + 8)
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, M * N, size=S))  # sorted, distinct, at most S
+    idx_dev = torch.from_numpy(idx).to(ys[0].device)
+    arr = torch.stack([y.reshape(-1)[idx_dev].float() for y in ys]).cpu().numpy()
+    np.save(os.path.join(directory, "out_sample.npy"), arr)
+    np.save(os.path.join(directory, "out_sample_index.npy"), idx.astype(np.float64))
+    return {"out_sample": list(arr.shape), "of": [L, M, N]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -451,7 +482,11 @@ def main():
     ap.add_argument("--full-out", default="", help="also write the verbose per-block records (clock strings, event timings, byte counts) to this file")
     ap.add_argument("--tuning", default="", help="development: comma-separated tuning[] override, e.g. 4,8")
     ap.add_argument("--matmul-type", default="", help="development: force a kernel family (forward_manual)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (every layer's output, float32) under DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from gemlite_amd.bench_utils import ReplicaGroup, timed_steps, whole_job_rate
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -473,6 +508,9 @@ def main():
     layers = main_run.layers
 
     elapsed = timed_steps(rgroup, main_run.run_step, args.steps, args.warmup, device_sync=torch.cuda.synchronize, device=device)
+    dumped = None
+    if args.dump_outputs:  # before anything else runs on the GPU: the buffers hold the last timed step
+        dumped = dump_outputs(main_run.outs, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"))
     launches = args.steps * layers
     ms_per_step = elapsed / args.steps * 1e3
     gap_us = elapsed / launches * 1e6
@@ -518,7 +556,8 @@ def main():
                                f"(cache-cold rotation), {'hipGraph replay' if main_run.graph is not None else 'eager'}",
                    "layers_per_step": layers, "launches_per_step": layers, "replicas": world,
                    **({"tuning": args.tuning} if args.tuning else {}),
-                   **({"matmul_type": args.matmul_type} if args.matmul_type else {})},
+                   **({"matmul_type": args.matmul_type} if args.matmul_type else {}),
+                   **({"dump_outputs": dumped} if dumped else {})},
         "roofline": roof,
     }
 

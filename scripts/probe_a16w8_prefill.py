@@ -1,5 +1,5 @@
 import sys, os, time, json, torch
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import gemlite_amd
 H = gemlite_amd.helper
 dev = torch.device("cuda:0")
