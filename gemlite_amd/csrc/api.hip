@@ -277,7 +277,7 @@ static void resolve_mx_plan(const gemlite_hip_forward_args& a, Resolved& r, cons
         p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
         p.group_size = 32;
         p.stride_xm = a.stride_xm; p.stride_xk = a.stride_xk; p.stride_wk = 1;
-        p.flags = a.tuning[3];
+        p.flags = caller_flags(a);
         if (plan_gemm_wn_mma_mx(a, p, r.lp)) { r.kind = K_TILED_WN; r.wn = p; return; }
     }
     // fp8 / fp4 activations that no tile kernel took (K % 512 != 0 with fp4 activations ...): the few-row kernel over 64-row tiles
@@ -303,7 +303,7 @@ static void resolve_mx_plan(const gemlite_hip_forward_args& a, Resolved& r, cons
         p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
         p.group_size = 16;
         p.stride_xm = a.K; p.stride_xk = 1; p.stride_wk = 1;
-        p.flags = a.tuning[3];
+        p.flags = caller_flags(a);
         if (plan_gemm_wn_mma_mx(b, p, r.lp, 1)) {
             r.kind = K_NV_MMA;
             r.wn = p;
@@ -473,7 +473,7 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
         p.meta_dt = a.meta_dtype; p.zeros_dt = a.zeros_dtype; p.zero_is_scalar = a.zero_is_scalar;
         p.stride_xm = a.K; p.stride_xk = 1; p.stride_wk = a.stride_wk;
         p.stride_meta_g = (pgm && eg < a.K) ? a.stride_meta_g : 0;
-        p.flags = a.tuning[3];
+        p.flags = caller_flags(a);
         p.gs_shift = eg >= a.K ? 31 : ((eg & (eg - 1)) == 0 ? __builtin_ctz((unsigned)eg) : -1);
         LaunchPlan lp{};
         if (p.gs_shift < 0 || !plan_gemv_a8wn(b, p, lp, true)) return;
@@ -496,7 +496,7 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
         // one metadata row spanning all of K ([1, N] scales of a K-long group): the row stride is never used, and views of a
         // [N, 1] tensor carry arbitrary values there (1 for `.t()`), which the planners' alignment checks would reject
         p.stride_meta_g = (per_group_meta && eff_group < a.K) ? a.stride_meta_g : 0;
-        p.flags = a.tuning[3];
+        p.flags = caller_flags(a);
         p.gs_shift = eff_group >= a.K ? 31
                      : ((eff_group > 0 && (eff_group & (eff_group - 1)) == 0) ? __builtin_ctz((unsigned)eff_group) : -1);
         const int mt = a.matmul_type;
@@ -535,9 +535,9 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
         // blocks, K unsplit, weights requested first, x through LDS in whole cache lines.  Every block re-reads all of x (M K 2 bytes through
         // the CU's L2 -> LDS path), so the default stops at a budget on that traffic; groups of 32 and N % 64 != 0 — which no other
         // specialised kernel takes at M >= 2 — always come here (any M: row blocks along grid.y).  tuning[0] = 9 forces the kernel
-        // (tuning[1] = 1 / 2 column tiles per block), tuning[3] & 65536 keeps the round-4 choice (A/B runs).
+        // (tuning[1] = 1 / 2 column tiles per block), GEMLITE_TF_NO_ROWS_KERNEL keeps the round-4 choice (A/B runs).
         if (x16 && (a.W_nbits == 4 || a.W_nbits == 2) && (mt == GEMLITE_MATMUL_AUTO || mt == GEMLITE_MATMUL_GEMM_SPLITK || (mt == GEMLITE_MATMUL_GEMM && a.tuning[0] == 9)) &&
-            !(a.tuning[3] & 65536) && (a.tuning[0] == 9 || (a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && a.M >= 2))) {
+            !(caller_flags(a) & GEMLITE_TF_NO_ROWS_KERNEL) && (a.tuning[0] == 9 || (a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && a.M >= 2))) {
             // nothing FASTER behind this one.  2-bit groups of 32 and N % 64 != 0: only the coverage kernel.  4-bit groups of 32 over N % 64 == 0 do have
             // gemm_wn_stream_kernel behind them (round 4's choice) and ADVICE r5 asked to hand M > 64 back to it, because the rows kernel re-streams
             // the weights once per 32-row block there — measured (round 6, profiles/r06/probe_g32_rows_vs_stream.log, layer(x) in us, rows / stream):
@@ -568,9 +568,9 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
         //     1536 x 8960 10.7 vs 14.9) except a long K over a narrow N, which takes the registers-only kernel with 64-column tiles and
         //     K slices (4096 x 14336 11.7 vs 16.5, 8192 x 28672 22.2 vs 28.5); N >= 12288: the registers-only kernel's 64-column tiles
         //     unsplit (13824 x 5120 10.9 vs 11.6 .. 17.6, 28672 x 8192 21.9 vs 30.5) — profiles/r03/probe_m4_llm_shapes_*.log.
-        // tuning[3] & 512 = never, & 1024 = wherever it applies (A/B runs).
+        // GEMLITE_TF_NO_MFMA_GEMV = never, GEMLITE_TF_FORCE_MFMA_GEMV = wherever it applies (A/B runs).
         if (x16 && a.W_nbits == 4 && a.M >= 2 && a.M <= 4 && mt == GEMLITE_MATMUL_AUTO && a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 &&
-            !(a.tuning[3] & 1024) && a.K >= 12288 && a.N <= 8192 && a.N % 64 == 0 && a.N / 64 >= 40) {
+            !(caller_flags(a) & GEMLITE_TF_FORCE_MFMA_GEMV) && a.K >= 12288 && a.N <= 8192 && a.N % 64 == 0 && a.N / 64 >= 40) {
             gemlite_hip_forward_args a2 = a;
             a2.tuning[0] = 4;
             a2.tuning[1] = a.N / 64 >= 128 ? 2 : 4;
@@ -578,7 +578,7 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
             LaunchPlan ld{};
             if (plan_gemm_wn_direct(a2, pd, ld)) { r.kind = K_STREAM_WN; r.wn = pd; r.lp = ld; return; }
         }
-        if (x16 && !(a.tuning[3] & 512) && a.tuning[1] == 0 &&
+        if (x16 && !(caller_flags(a) & GEMLITE_TF_NO_MFMA_GEMV) && a.tuning[1] == 0 &&
             ((want_gemv && a.M == 1 && mt != GEMLITE_MATMUL_GEMV_SPLITK) || (a.M >= 2 && a.M <= 4 && mt == GEMLITE_MATMUL_AUTO))) {
             WnParams pm = p;
             LaunchPlan lm{};
@@ -594,7 +594,7 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
                 // is not a multiple of 1024 (K = 8960 / 9728 / 11008: 7.26 vs 8.04, 7.84 vs 8.22, 8.29 vs 9.16), and 2 .. 4 rows as before.
                 (void)cols;
                 const bool wins = a.M >= 2 ? (a.W_nbits != 4 || a.N < 12288) : (a.W_nbits == 2 && a.K % 1024 != 0);
-                if ((a.tuning[3] & 1024) || a.tuning[0] != 0 || wins) { r.kind = K_GEMV_WN; r.wn = pm; r.lp = lm; return; }
+                if ((caller_flags(a) & GEMLITE_TF_FORCE_MFMA_GEMV) || a.tuning[0] != 0 || wins) { r.kind = K_GEMV_WN; r.wn = pm; r.lp = lm; return; }
             }
         }
         if (want_gemv && plan_gemv_wn(a, p, lp)) { r.kind = K_GEMV_WN; r.wn = p; r.lp = lp; return; }
@@ -617,7 +617,7 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
             // LDS-staged streaming kernel, 1.3 - 2.2x behind the 32-row MFMA tiles (profiles/r05/probe_g64_m17_32_w{4,2}.log, 4-bit / 2-bit:
             // 4096^2 16.3 / 15.7 -> 12.9 / 11.9 us, 6144 x 4096 2-bit 23.1 -> 12.2, 11008 x 4096 31.4 / 31.0 -> 16.5 / 22.6, 8192^2 2-bit 25.3 -> 17.2);
             // a short K keeps the streaming kernel (8960 x 1536: 10.6 vs 11.1)
-            if (mt == GEMLITE_MATMUL_AUTO && a.M > 16 && a.K >= 2048 && a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(a.tuning[3] & 65536) &&
+            if (mt == GEMLITE_MATMUL_AUTO && a.M > 16 && a.K >= 2048 && a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(caller_flags(a) & GEMLITE_TF_NO_ROWS_KERNEL) &&
                 plan_gemm_wn_mma(a, p, lp)) { r.kind = K_TILED_WN; r.wn = p; r.lp = lp; return; }
             if (a.tuning[0] != 3 && plan_gemm_wn_stream(a, p, lp)) { r.kind = K_STREAM_WN; r.wn = p; r.lp = lp; return; }
             // shapes the few-row kernels do not take (K = 11008, 8960, ...): small tiles of the MFMA kernel, never the
@@ -668,7 +668,7 @@ coverage:
         gq.int_acc = a.w_dtype == GEMLITE_DT_INT8 ? 1 : 0;
         gq.epi.scales_x = nullptr; gq.epi.stride_sx_m = 1;
         gq.cq_x = a.x; gq.cq_stride_xm = a.stride_xm; gq.cq_xdt = a.input_dtype;
-        gq.flags = a.tuning[3];
+        gq.flags = caller_flags(a);
         r.status = GEMLITE_OK;
         r.kind = K_A8_FQ;
         r.gp = gq;
@@ -713,7 +713,7 @@ coverage:
     // tuning[0] = 10 forces them, tuning[0] = 6 keeps the round-3 choice
     if (!packed && a.matmul_type != GEMLITE_MATMUL_GEMV && a.matmul_type != GEMLITE_MATMUL_GEMV_SPLITK &&
         a.matmul_type != GEMLITE_MATMUL_GEMV_REVSPLITK &&
-        (a.tuning[0] == 10 || (a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(a.tuning[3] & 64) && a8w8_sq128_pays(a))) && plan_gemm_a8w8_sq128(a, r.gp, r.lp)) {
+        (a.tuning[0] == 10 || (a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(caller_flags(a) & GEMLITE_TF_A8W8_WEIGHTS_FROM_MEMORY) && a8w8_sq128_pays(a))) && plan_gemm_a8w8_sq128(a, r.gp, r.lp)) {
         r.kind = K_A8_MMA;
         return;
     }
@@ -721,7 +721,7 @@ coverage:
     // tuning[0] = 5 forces them, tuning[0] = 6 keeps the round-3 choice
     if (!packed && a.matmul_type != GEMLITE_MATMUL_GEMV && a.matmul_type != GEMLITE_MATMUL_GEMV_SPLITK &&
         a.matmul_type != GEMLITE_MATMUL_GEMV_REVSPLITK &&
-        (a.tuning[0] == 5 || (a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(a.tuning[3] & 64) && a8w8_sq_pays(a))) && plan_gemm_a8w8_sq(a, r.gp, r.lp)) {
+        (a.tuning[0] == 5 || (a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(caller_flags(a) & GEMLITE_TF_A8W8_WEIGHTS_FROM_MEMORY) && a8w8_sq_pays(a))) && plan_gemm_a8w8_sq(a, r.gp, r.lp)) {
         r.kind = K_A8_MMA;
         return;
     }
@@ -767,7 +767,7 @@ coverage:
             p.M = (int)a.M; p.N = (int)a.N; p.K = (int)a.K;
             p.group_size = 32;
             p.stride_xm = a.stride_xm; p.stride_xk = a.stride_xk; p.stride_wk = 1;
-            p.flags = a.tuning[3];
+            p.flags = caller_flags(a);
             if (plan_gemm_wn_mma_mx(a, p, r.lp, 2)) { r.kind = K_TILED_WN; r.wn = p; return; }
         }
         // round 4: 16-column blocks, weights converted in registers, MFMA (tuning[0] = 7 keeps the streaming kernel of rounds 1-3)
@@ -951,7 +951,7 @@ int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) {
             r.wn.counters = (unsigned*)args->workspace;
             r.wn.slabs = (float*)((char*)args->workspace + COUNTER_BYTES);
         } else if (args->workspace && args->workspace_bytes >= COUNTER_BYTES) {
-            r.wn.counters = (unsigned*)args->workspace;  // lets the opt-in timeline probes (tuning[3] & 4) find a buffer
+            r.wn.counters = (unsigned*)args->workspace;  // lets the opt-in timeline probes (GEMLITE_TF_TIMELINE) find a buffer
         }
         const int e = ensure_lds(r.lp.fn, r.lp.lds_bytes, dev);
         if (e != GEMLITE_OK) return e;

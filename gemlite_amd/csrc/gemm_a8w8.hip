@@ -328,7 +328,7 @@ __global__ __launch_bounds__(512, 2) void gemm_a8w8_mma_kernel(const GenericPara
     int bid = blockIdx.x, slice = blockIdx.y;
     {  // blocks of one XCD (block b runs on XCD b % 8) share a K slice: its x rows stay in that XCD's L2 (speed only)
         const int T = gridDim.x, S = gridDim.y;
-        if ((p.flags & 8) && S > 1 && (8 % S) == 0 && ((T * S) & 7) == 0) {
+        if ((p.flags & GEMLITE_TF_XCD_SLICE_MAP) && S > 1 && (8 % S) == 0 && ((T * S) & 7) == 0) {
             const int lin = blockIdx.x + T * blockIdx.y, xcd = lin & 7, idx = lin >> 3;
             slice = xcd % S;
             bid = idx * (8 / S) + xcd / S;
@@ -690,8 +690,8 @@ __global__ __launch_bounds__(512, (NST <= 2 ? 2 : 1)) void gemm_a8w8_sq_kernel(c
     // lines in lockstep.  The order of the K steps changes per row tile: exact for int8; for fp8 the fp32 sums differ in the last bits between tiles.
     // (measured, one box: 13.14 -> 12.05 us at int8 4096^2 M = 256, M = 128 13.1 -> 11.1, M = 512 21.5 -> 18.0, 2048 x 8192 M = 256 19.7 -> 15.0;
     //  staggering the column tiles that share a row tile of x as well: nothing.  It pays only while the weight tiles an XCD works on at a time stay in
-    //  its L2 — the planner sets bit 30 of flags by that rule (k_rotation_pays() below: 4096 x 14336 M = 256, 7 MB per XCD, 34.4 -> 40.2 us).
-    //  profiles/r06/probe_a8w8_sq_k_rotation.log, probe_k_rotation_*.log; tuning[3] & 4194304 = never, for A/B runs)
+    //  its L2 — the planner sets K_ORDER_ON in flags by that rule (k_rotation_pays() below: 4096 x 14336 M = 256, 7 MB per XCD, 34.4 -> 40.2 us).
+    //  profiles/r06/probe_a8w8_sq_k_rotation.log, probe_k_rotation_*.log; GEMLITE_TF_NO_K_ROTATION = never, for A/B runs)
     KOrder kord;
     kord.init(mt, mtiles, nsteps, p.flags);
     auto kof = [&](int step) __attribute__((always_inline)) { return kord.at(step); };
@@ -1027,10 +1027,10 @@ bool plan_gemm_a8w8_sq128(const gemlite_hip_forward_args& a, GenericParams& g, L
     g.splitk = 1;
     // K order between the row tiles of a column tile (k_order(), gl_async.h): groups of ONE step for fp8 — FP8 16384^2 M = 256 94.7 -> 89.6 us, 8192^2 M = 512 45.1 -> 43.2 —
     // and the plain order for int8 (8192^2 M = 512 46.3 -> 47.5, 4096^2 M = 1024 27.5 -> 28.1 with it); larger groups and the whole-K rotation lose on these
-    // 2-MB tiles (profiles/r06/probe_k_order_groups*.log, probe_k_rotation_sq128_slower.log).  tuning[3] bits 24 .. 27 force a group size, & 4194304 = plain.
-    g.flags = a.tuning[3] & ~((1 << 30) | 0x0F000000);
-    if (a.tuning[3] & 0x0F000000) g.flags |= (1 << 30) | (a.tuning[3] & 0x0F000000);
-    else if (!(a.tuning[3] & 4194304) && a.input_dtype != GEMLITE_DT_INT8 && (a.M + 127) / 128 >= 2 && ((a.N / 128) & 7) == 0) g.flags |= (1 << 30) | (1 << 24);
+    // 2-MB tiles (profiles/r06/probe_k_order_groups*.log, probe_k_rotation_sq128_slower.log).  GEMLITE_TF_K_ORDER_GROUP_MASK forces a group size, GEMLITE_TF_NO_K_ROTATION = plain.
+    g.flags = caller_flags(a);
+    if (g.flags & GEMLITE_TF_K_ORDER_GROUP_MASK) g.flags |= K_ORDER_ON;
+    else if (!(g.flags & GEMLITE_TF_NO_K_ROTATION) && a.input_dtype != GEMLITE_DT_INT8 && (a.M + 127) / 128 >= 2 && ((a.N / 128) & 7) == 0) g.flags |= K_ORDER_ON | K_ORDER_GROUPS_OF_1;
     lp.fn = (const void*)fn;
     lp.name = "gemm_a8w8_sq_kernel<128x128>";
     lp.grid = dim3((unsigned)tiles, 1, 1);
@@ -1046,7 +1046,7 @@ bool plan_gemm_a8w8_sq128(const gemlite_hip_forward_args& a, GenericParams& g, L
 // part of the tile from HBM and the others find it in that XCD's L2 — IF it is still there: an XCD works on min(column tiles per XCD, CUs per XCD /
 // row tiles) weight tiles at a time, and the rotation pays while those fit its 4-MB L2 (2 MB: -8 .. -24 %; 4 MB: even; 7 MB: +17 %).
 bool k_rotation_pays(const gemlite_hip_forward_args& a, int64_t tile_bytes) {
-    if (a.tuning[3] & 4194304) return false;
+    if (caller_flags(a) & GEMLITE_TF_NO_K_ROTATION) return false;
     const int64_t mtiles = (a.M + 63) / 64, ntiles = a.N / 64;
     if (mtiles < 2 || (ntiles & 7) != 0) return false;
     const int64_t cus_per_xcd = resident_block_limit() / 8 > 0 ? resident_block_limit() / 8 : 1;
@@ -1058,16 +1058,16 @@ bool k_rotation_pays(const gemlite_hip_forward_args& a, int64_t tile_bytes) {
 // inside its L2, else the GROUPED order with groups of one step — every tile leads on one step of each run of mtiles steps, so a line only has to survive
 // mtiles - 1 steps (late round 6, profiles/r06/probe_k_order_groups*.log: int8 4096 x 14336 M = 256, 7 MB per XCD: 34.5 -> 31.0 us where the whole rotation
 // cost +17 %; 4096 x 8192, 4 MB: whole 21.4 = none 21.6, grouped 20.1; MXFP8 4096 x 8192 28 .. 31 -> 25.4 whole -> 23.4 grouped; where the whole rotation
-// pays it stays ahead: 4096^2 M = 256 12.0 vs 12.8, 2048 x 8192 15.5 vs 17.9).  tuning[3] bits 24 .. 27 force a group size (1 + log2), & 4194304 = plain order.
+// pays it stays ahead: 4096^2 M = 256 12.0 vs 12.8, 2048 x 8192 15.5 vs 17.9).  GEMLITE_TF_K_ORDER_GROUP_MASK forces a group size (1 + log2), GEMLITE_TF_NO_K_ROTATION = plain order.
 int k_order_flags(const gemlite_hip_forward_args& a, int64_t tile_bytes) {
-    if (a.tuning[3] & 4194304) return 0;
-    if (a.tuning[3] & 0x0F000000) return (1 << 30) | (a.tuning[3] & 0x0F000000);
+    if (caller_flags(a) & GEMLITE_TF_NO_K_ROTATION) return 0;
+    if (const int group = caller_flags(a) & GEMLITE_TF_K_ORDER_GROUP_MASK) return K_ORDER_ON | group;
     const int64_t mtiles = (a.M + 63) / 64, ntiles = a.N / 64;
     if (mtiles < 2 || (ntiles & 7) != 0) return 0;
     const int64_t cus_per_xcd = resident_block_limit() / 8 > 0 ? resident_block_limit() / 8 : 1;
     const int64_t at_a_time = cus_per_xcd / mtiles > 0 ? cus_per_xcd / mtiles : 1;
     const int64_t tiles_x = ntiles / 8 < at_a_time ? ntiles / 8 : at_a_time;
-    return tiles_x * tile_bytes < (4ll << 20) ? (1 << 30) : ((1 << 30) | (1 << 24));
+    return tiles_x * tile_bytes < (4ll << 20) ? K_ORDER_ON : (K_ORDER_ON | K_ORDER_GROUPS_OF_1);
 }
 
 bool plan_gemm_a8w8_sq(const gemlite_hip_forward_args& a, GenericParams& g, LaunchPlan& lp) {
@@ -1093,14 +1093,14 @@ bool plan_gemm_a8w8_sq(const gemlite_hip_forward_args& a, GenericParams& g, Laun
     fn_t fn = nullptr;
     auto pick = [&](auto dt) -> fn_t {
         constexpr int DT = decltype(dt)::value;
-        // (tuning[3] & 2097152: the round-4 order of a step — requests first — for A/B runs)
-        if (!(a.tuning[3] & 2097152)) return nst == 2 ? gemm_a8w8_sq_kernel<DT, 2, true> : (nst == 3 ? gemm_a8w8_sq_kernel<DT, 3, true> : gemm_a8w8_sq_kernel<DT, 4, true>);
+        // (GEMLITE_TF_A8W8_TILE_REQUESTS_FIRST: the round-4 order of a step — requests first — for A/B runs)
+        if (!(caller_flags(a) & GEMLITE_TF_A8W8_TILE_REQUESTS_FIRST)) return nst == 2 ? gemm_a8w8_sq_kernel<DT, 2, true> : (nst == 3 ? gemm_a8w8_sq_kernel<DT, 3, true> : gemm_a8w8_sq_kernel<DT, 4, true>);
         return nst == 2 ? gemm_a8w8_sq_kernel<DT, 2> : (nst == 3 ? gemm_a8w8_sq_kernel<DT, 3> : gemm_a8w8_sq_kernel<DT, 4>);
     };
     fn = a.input_dtype == GEMLITE_DT_INT8 ? pick(std::integral_constant<int, GEMLITE_DT_INT8>{})
          : (a.input_dtype == GEMLITE_DT_FP8E4 ? pick(std::integral_constant<int, GEMLITE_DT_FP8E4>{}) : pick(std::integral_constant<int, GEMLITE_DT_FP8E5>{}));
     g.splitk = 1;
-    g.flags = (a.tuning[3] & ~((1 << 30) | 0x0F000000)) | k_order_flags(a, (int64_t)64 * a.K);
+    g.flags = caller_flags(a) | k_order_flags(a, (int64_t)64 * a.K);
     lp.fn = (const void*)fn;
     lp.name = "gemm_a8w8_sq_kernel<64x64>";
     lp.grid = dim3((unsigned)tiles, 1, 1);
@@ -1135,7 +1135,7 @@ static const void* a8_pick_lds(int mi) {
 }
 
 // 8-wave kernels: M >= 2 (tuning[0]: 2 = the 4-wave kernel of round 1; tuning[1] = K slices; tuning[2] = tile rows / 32;
-// tuning[3] & 64: weights straight from memory also for the 128- / 256-row tiles, the A/B switch of the LDS-B variant)
+// GEMLITE_TF_A8W8_WEIGHTS_FROM_MEMORY: weights straight from memory also for the 128- / 256-row tiles, the A/B switch of the LDS-B variant)
 bool plan_gemm_a8w8_mma(const gemlite_hip_forward_args& a, GenericParams& g, LaunchPlan& lp) {
     if (a.elements_per_sample != 1 || a.W_group_mode != 0 || a.M < 2) return false;
     if (a.w_dtype != a.input_dtype) return false;
@@ -1165,7 +1165,7 @@ bool plan_gemm_a8w8_mma(const gemlite_hip_forward_args& a, GenericParams& g, Lau
     }
     if (a.tuning[2] == 1 || a.tuning[2] == 2 || a.tuning[2] == 4 || a.tuning[2] == 8) mi = a.tuning[2];
     const int bm = 32 * mi;
-    const bool lds_b = mi >= 4 && !(a.tuning[3] & 64);  // both operands through LDS (128-byte K steps)
+    const bool lds_b = mi >= 4 && !(caller_flags(a) & GEMLITE_TF_A8W8_WEIGHTS_FROM_MEMORY);  // both operands through LDS (128-byte K steps)
     if (lds_b) units = (int)(a.K / 128);
     const int64_t tiles = (int64_t)(a.N / 128) * ((a.M + bm - 1) / bm);
     int splitk = 0;
@@ -1192,7 +1192,7 @@ bool plan_gemm_a8w8_mma(const gemlite_hip_forward_args& a, GenericParams& g, Lau
                               : (a.input_dtype == GEMLITE_DT_FP8E4 ? a8_pick<GEMLITE_DT_FP8E4>(mi) : a8_pick<GEMLITE_DT_FP8E5>(mi)));
     if (!fn) return false;
     g.splitk = splitk;
-    g.flags = a.tuning[3];
+    g.flags = caller_flags(a);
     lp.fn = fn;
     lp.name = mi == 8 ? "gemm_a8w8_mma_kernel<256x128>" : (mi == 4 ? "gemm_a8w8_mma_kernel<128x128>"
               : (mi == 2 ? "gemm_a8w8_mma_kernel<64x128>" : "gemm_a8w8_mma_kernel<32x128>"));
@@ -1383,7 +1383,7 @@ bool plan_a8w8_rows(const gemlite_hip_forward_args& a, LaunchPlan& lp, bool fq) 
     if (((uintptr_t)a.x | (uintptr_t)a.w_q) % 16 != 0 || a.stride_xm % 16 != 0 || a.stride_wn % 16 != 0) return false;
     if ((int64_t)a.M * a.stride_xm + a.K >= (1ll << 31) || (int64_t)a.N * a.stride_wn + a.K >= (1ll << 31)) return false;
     const int mt = a.M <= 16 ? 1 : (a.M <= 32 ? 2 : 4);
-    // round 6: x through LDS in whole cache lines (gemm_w8_rows.hip; tuning[3] & 524288 keeps the register-fed kernel of round 3 below).  Measured
+    // round 6: x through LDS in whole cache lines (gemm_w8_rows.hip; GEMLITE_TF_W8_ROWS_X_FROM_REGISTERS keeps the register-fed kernel of round 3 below).  Measured
     // on 4096^2, 8192^2, 14336 x 4096, 4096 x 14336, int8 and fp8, `layer(x)` (profiles/r06/probe_w8_rows_lds_*.log):
     //   * layers whose 16-column blocks are ONE resident round (N <= 4096 on 256 CUs): ahead of the round-3 kernel from 2 rows (4096^2 M = 2 / 16 /
     //     32 / 64: 9.2 / 10.8 / 12.6 / 17.2 -> 8.6 / 9.7 / 11.7 / 13.7 us) and ahead of every tile kernel while the blocks' re-reads of x stay below
@@ -1391,7 +1391,7 @@ bool plan_a8w8_rows(const gemlite_hip_forward_args& a, LaunchPlan& lp, bool fq) 
     //   * more blocks than CUs: the 64-KB form, two blocks per CU, from 4 rows (8192^2 M = 4 / 8 / 16: 20.5 / 22.1 / 23.8 (tiles) -> 19.9 / 20.6 /
     //     22.0); not on layers with 192 or more 64-column tiles, where the unsplit tiles take over from 5 rows (14336 x 4096 M = 8: 18.2 vs 19.8)
     //     and the round-3 kernel is ahead below (M = 2 / 4: 17.8 / 18.6 vs 18.7 / 19.4).
-    if (!fq && !(a.tuning[3] & 524288) && a.K % 256 == 0) {
+    if (!fq && !(caller_flags(a) & GEMLITE_TF_W8_ROWS_X_FROM_REGISTERS) && a.K % 256 == 0) {
         const int64_t blocks = a.N / 16;
         const bool forced = a.tuning[0] == 4;
         bool lds;
@@ -1585,7 +1585,7 @@ __global__ __launch_bounds__(512) void a16w8_rows_kernel(const GenericParams p) 
 //   * more blocks than CUs (the 64-KB form, two blocks per CU): up to 16 rows — 8192^2 M = 16: 24.4 -> 21.7, 14336 x 4096 M = 16: 23.0 -> 21.7;
 //     M = 24: 25.3 (tile) vs 25.6.
 bool a16w8_rows_lds_pays(const gemlite_hip_forward_args& a) {
-    if ((a.tuning[3] & 524288) || a.K % 256 != 0 || a.N % 16 != 0 || a.M < 4 || a.M > 64) return false;
+    if ((caller_flags(a) & GEMLITE_TF_W8_ROWS_X_FROM_REGISTERS) || a.K % 256 != 0 || a.N % 16 != 0 || a.M < 4 || a.M > 64) return false;
     const int64_t blocks = a.N / 16;
     if (blocks <= resident_block_limit()) return (int64_t)a.M * a.K * 2 * blocks <= (256ll << 20);
     return a.M <= 16;
@@ -1606,9 +1606,9 @@ bool plan_a16w8_rows(const gemlite_hip_forward_args& a, LaunchPlan& lp) {
     if (a.stride_wk != 1 || a.stride_xk != 1 || a.N % 16 != 0 || a.K % 64 != 0) return false;
     if (((uintptr_t)a.x | (uintptr_t)a.w_q) % 16 != 0 || (a.stride_xm * 2) % 16 != 0 || a.stride_wn % 16 != 0) return false;
     if (((int64_t)a.M * a.stride_xm + a.K) * 2 >= (1ll << 31) || (int64_t)a.N * a.stride_wn + a.K >= (1ll << 31)) return false;
-    // round 6: x through LDS in whole cache lines (gemm_w8_rows.hip; tuning[3] & 524288 keeps the register-fed kernel of round 4 below) from 4
+    // round 6: x through LDS in whole cache lines (gemm_w8_rows.hip; GEMLITE_TF_W8_ROWS_X_FROM_REGISTERS keeps the register-fed kernel of round 4 below) from 4
     // rows — at 2 / 3 rows the two tie on one-round layers and the round-4 kernel leads on the others (a16w8_rows_lds_pays() has the numbers)
-    if (!mx && !(a.tuning[3] & 524288) && a.K % 256 == 0 && (a.M >= 4 || (a.tuning[3] & 1048576)) && (a.N / 16 <= resident_block_limit() || a.M <= 32) &&
+    if (!mx && !(caller_flags(a) & GEMLITE_TF_W8_ROWS_X_FROM_REGISTERS) && a.K % 256 == 0 && (a.M >= 4 || (caller_flags(a) & GEMLITE_TF_W8_ROWS_LDS_BELOW_4_ROWS)) && (a.N / 16 <= resident_block_limit() || a.M <= 32) &&
         plan_w8_rows_lds(a, lp, w8_lds_mt(a.M), w8_lds_two(a))) return true;
     const int mt = a.M <= 16 ? 1 : (a.M <= 32 ? 2 : 4);
     typedef void (*fn_t)(const GenericParams);

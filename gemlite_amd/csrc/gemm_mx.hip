@@ -368,8 +368,9 @@ bool plan_mx_gemv(const gemlite_hip_forward_args& a, GenericParams& g, LaunchPla
     lp.fn = fn;
     lp.name = w8 ? "mx_gemv_w8_kernel" : "mx_gemv_w4_kernel";
     // waves (= adjacent columns) per block: measured at 4096^2, M = 1 (profiles/r02/mx): fp4 weights 16 waves 5.9 vs 6.9 us with 4
-    // (the columns share the lines of the [K/32][N] scale bytes), fp8 weights 4 waves 8.1 vs 8.9 us.  tuning[3]: 1 = 4, 2 = 16.
-    const int nw = a.tuning[3] == 1 ? 4 : (a.tuning[3] == 2 ? 16 : (w8 ? 4 : 16));
+    // (the columns share the lines of the [K/32][N] scale bytes), fp8 weights 4 waves 8.1 vs 8.9 us.
+    const int wf = caller_flags(a) & GEMLITE_TF_MX_GEMV_WAVES_MASK;
+    const int nw = wf == GEMLITE_TF_MX_GEMV_4_WAVES ? 4 : (wf == GEMLITE_TF_MX_GEMV_16_WAVES ? 16 : (w8 ? 4 : 16));
     lp.grid = dim3((unsigned)((a.N + nw - 1) / nw), (unsigned)((a.M + mb - 1) / mb), 1);
     lp.block = dim3(64 * nw, 1, 1);
     lp.lds_bytes = 0;
@@ -1146,9 +1147,9 @@ __global__ __launch_bounds__(512, 2) void gemm_mx_tile_kernel(const GenericParam
     const int col = lane & 31, h = lane >> 5;
     const int mtiles = (p.M + BM - 1) / BM, ntiles = p.N / BN;
     // Block b runs on XCD b % 8 and every XCD has its own 4 MiB L2: give each XCD a compact sub-grid (ntiles / 8 weight panels
-    // x all row panels) so that a panel stage is fetched into an L2 once and shared (tuning[3] & 16: plain M-fastest order)
+    // x all row panels) so that a panel stage is fetched into an L2 once and shared (GEMLITE_TF_MX_PLAIN_TILE_ORDER: plain M-fastest order)
     int mt = blockIdx.x % mtiles, nt = blockIdx.x / mtiles;
-    if ((ntiles & 7) == 0 && !(p.flags & 16)) {
+    if ((ntiles & 7) == 0 && !(p.flags & GEMLITE_TF_MX_PLAIN_TILE_ORDER)) {
         const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = ntiles >> 3;
         mt = idx % mtiles;
         nt = xcd * per + (idx / mtiles) % per;
@@ -1376,7 +1377,7 @@ bool plan_gemm_mx_tile(const gemlite_hip_forward_args& a, GenericParams& g, Laun
                       : (f4 ? (bx ? gemm_mx_tile_kernel<4, 4, nst, true> : gemm_mx_tile_kernel<4, 4, nst, false>)
                             : (bx ? gemm_mx_tile_kernel<0, 4, nst, true> : gemm_mx_tile_kernel<0, 4, nst, false>));  // (6 stages of 26 KiB for A8W4: 142 vs 139 us — depth is not the limit)
     g.splitk = 1;
-    g.flags = a.tuning[3];  // & 16: plain M-fastest tile order (A/B runs)
+    g.flags = caller_flags(a);
     lp.fn = (const void*)f;
     lp.name = f8 ? "gemm_mx_a8w8_tile_kernel<256x256>" : (f4 ? "gemm_mx_a4w4_tile_kernel<256x256>" : "gemm_mx_a8w4_tile_kernel<256x256>");
     lp.grid = dim3((unsigned)tiles, 1, 1);
@@ -1467,8 +1468,8 @@ __global__ __launch_bounds__(512, (NST <= 2 ? 2 : 1)) void gemm_mx_sq_kernel(con
     const uint32_t ldss = lds_base + (uint32_t)(s_is_w ? SC_B + (sp - 2) * 256 : SC_A + sp * 256);
     // K rotation (round 6, see gemm_a8w8_sq_kernel): the row tiles that share a weight column tile (same XCD) start their K loops mtiles-ths apart, so
     // that each sibling CU pulls a different part of the HBM-cold weights and finds the rest in L2 (MXFP8 4096^2 M = 256 16.1 -> 12.3 us, MXFP4 9.5 ..
-    // 10.6 -> 9.0, 4096 x 8192 27.8 -> 25.1: profiles/r06/probe_k_rotation_mx_and_int8_64x64.log).  The planner sets bit 30 of flags where the weight
-    // tiles an XCD works on at a time fit its L2 (k_rotation_pays(), gemm_a8w8.hip); tuning[3] & 4194304 = never (A/B runs)
+    // 10.6 -> 9.0, 4096 x 8192 27.8 -> 25.1: profiles/r06/probe_k_rotation_mx_and_int8_64x64.log).  The planner sets K_ORDER_ON in flags where the weight
+    // tiles an XCD works on at a time fit its L2 (k_rotation_pays(), gemm_a8w8.hip); GEMLITE_TF_NO_K_ROTATION = never (A/B runs)
     KOrder kord;
     kord.init(mt, mtiles, nsteps, p.flags);
     auto request = [&](int stage, int step) __attribute__((always_inline)) {
@@ -1599,7 +1600,7 @@ bool plan_gemm_mx_sq(const gemlite_hip_forward_args& a, GenericParams& g, Launch
     mx_kernel_fn_t f = f8 ? pick(F8{}, F8{}) : (f4 ? pick(F4{}, F4{}) : pick(F8{}, F4{}));
     g.splitk = 1;
     const int64_t wtile_bytes = (int64_t)64 * a.K / (g.mx_w == MX_FP4 ? 2 : 1);  // the weight bytes of a 64-column tile (fp8: K per column, fp4: K / 2)
-    g.flags = (a.tuning[3] & ~((1 << 30) | 0x0F000000)) | k_order_flags(a, wtile_bytes);
+    g.flags = caller_flags(a) | k_order_flags(a, wtile_bytes);
     lp.fn = (const void*)f;
     lp.name = f8 ? "gemm_mx_a8w8_sq_kernel<64x64>" : (f4 ? "gemm_mx_a4w4_sq_kernel<64x64>" : "gemm_mx_a8w4_sq_kernel<64x64>");
     lp.grid = dim3((unsigned)tiles, 1, 1);
@@ -1680,7 +1681,7 @@ bool plan_gemm_mx_mma(const gemlite_hip_forward_args& a, GenericParams& g, Launc
     // 128-row tiles, late round 6 (profiles/r06/scan_mx_*.log): two blocks share a CU, and blocks past one per CU cost a second round — 5120 x 13824 M = 512,
     // 160 tiles: one slice 131 us, two (320 blocks) 142, three (480) 104.  The slice count that minimises rounds x slice length + 3.3 us per slice
     // (slab traffic and the combine; 9.5 us per block and 1024 k) — equal to the rule above wherever that one stays within one round.
-    if (mi == 4 && a.tuning[1] == 0 && !(a.tuning[3] & 16384)) {
+    if (mi == 4 && a.tuning[1] == 0 && !(caller_flags(a) & GEMLITE_TF_MX_NO_SLICE_RULE)) {
         const int64_t cus = resident_block_limit();
         double best = 0;
         for (int sk = 1; sk <= sk_max && sk <= units; ++sk) {
@@ -1693,7 +1694,7 @@ bool plan_gemm_mx_mma(const gemlite_hip_forward_args& a, GenericParams& g, Launc
     const void* fn = g.mx_x == MX_FP8 ? (g.mx_w == MX_FP8 ? mx_pick<0, 0>(mi) : mx_pick<0, 4>(mi)) : mx_pick<4, 4>(mi);
     if (!fn) return false;
     g.splitk = splitk;
-    g.flags = a.tuning[3];
+    g.flags = caller_flags(a);
     lp.fn = fn;
     static const char* names[3][3] = {
         {"gemm_mx_a8w8_kernel<32x128>", "gemm_mx_a8w8_kernel<64x128>", "gemm_mx_a8w8_kernel<128x128>"},

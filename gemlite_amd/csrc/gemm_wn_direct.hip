@@ -98,7 +98,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_wn_direct_kernel(const WnPara
 
 #ifdef GL_DIRECT_TIMELINE  // development build only (scripts/timeline_direct.py): wave 0 of every block stamps the 100 MHz clock
     const int lin_blk = tile + gridDim.x * (slice + gridDim.y * mtile);
-    const bool probe = (p.flags & 4) && p.counters && wave == 0 && lane == 0 && lin_blk < 512;
+    const bool probe = (p.flags & GEMLITE_TF_TIMELINE) && p.counters && wave == 0 && lane == 0 && lin_blk < 512;
     unsigned long long* stamps = (unsigned long long*)(p.counters + MAX_SPLITK_COUNTERS) + lin_blk * 8;
     auto stamp = [&](int i) { if (probe) stamps[i] = __builtin_amdgcn_s_memrealtime(); };
 #else

@@ -7,8 +7,8 @@ namespace gl {
 bool k_rotation_pays(const gemlite_hip_forward_args& a, int64_t tile_bytes);  // gemm_a8w8.hip
 
 
-const void* mma_lookup_f16(int kind, int nbits, int mi, int xdt, int xch);
-const void* mma_lookup_bf16(int kind, int nbits, int mi, int xdt, int xch);
+const void* mma_lookup_f16(int kind, int nbits, int mi, int xdt);
+const void* mma_lookup_bf16(int kind, int nbits, int mi, int xdt);
 
 // When the narrow 64 x 64 tiles (KH = 4, 256-k steps) are the default: 0 = never, 1 = K unsplit, 2 = two K slices.  From sweeps over 20 LLM
 // layer shapes x M = 40 .. 256 for 4-bit words under 16-bit activations (profiles/r04/probe_mma_narrow_llm_shapes.log, ..._m40_m64.log) and
@@ -72,9 +72,9 @@ bool plan_gemm_wn_mma_mx(const gemlite_hip_forward_args& a, WnParams& p, LaunchP
         if (((uintptr_t)a.out % oal) != 0 || (a.stride_om * (oal / 4)) % oal != 0) return false;
         if (k8 && p.epi.c_mode != 0 && p.epi.c_mode != 2 && ((uintptr_t)p.epi.scales_w % 16) != 0) return false;  // 4 channel scales per load
     }
-    int nauto = (a.tuning[1] == 0 && a.tuning[2] == 0 && !(a.tuning[3] & 16384)) ? narrow_auto(a.M, a.N, a.K, 2) : 0;
+    int nauto = (a.tuning[1] == 0 && a.tuning[2] == 0 && !(caller_flags(a) & GEMLITE_TF_NO_NARROW_TILES)) ? narrow_auto(a.M, a.N, a.K, 2) : 0;
     // (first fitted on the plain 8-bit weights, then found to hold for the block-scaled ones as well: scan_mxa16_w{4,8}_*.log — 22 / 16 of 60 cells within 3 % before)
-    const bool k8_auto = a.M > 64 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(a.tuning[3] & 16384);
+    const bool k8_auto = a.M > 64 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(caller_flags(a) & GEMLITE_TF_NO_NARROW_TILES);
     // plain 8-bit weights (late round 6, profiles/r06/scan_a16w8_*.log): very few narrow tiles take FOUR K slices while those stay one round
     // (1024 x 4096 M = 128: 14.8 -> 12.6 us; 1536 x 8960 / 2048 x 8192 M = 96 .. 128: 26 .. 28 -> 17.6 .. 18.1)
     if (k8_auto && a.N % 64 == 0 && a.K % 256 == 0 && (a.N / 64) * ((a.M + 63) / 64) * 4 <= 256 && a.K / 256 >= 16) nauto = 4;
@@ -86,7 +86,7 @@ bool plan_gemm_wn_mma_mx(const gemlite_hip_forward_args& a, WnParams& p, LaunchP
         if (splitk > units) return false;
         const int64_t tiles = (int64_t)(a.N / 64) * ((a.M + 63) / 64);
         if (splitk > 1 && tiles > MAX_SPLITK_COUNTERS) return false;
-        const void* fn = f16 ? mma_lookup_f16(6, nb, 0, 0, 0) : mma_lookup_bf16(6, nb, 0, 0, 0);
+        const void* fn = f16 ? mma_lookup_f16(6, nb, 0, 0) : mma_lookup_bf16(6, nb, 0, 0);
         if (!fn) return false;
         p.splitk = splitk;
         p.rows_per_slice = (int)a.K;
@@ -96,9 +96,8 @@ bool plan_gemm_wn_mma_mx(const gemlite_hip_forward_args& a, WnParams& p, LaunchP
         p.w_mode = 2;
         p.gs_shift = 5;
         p.combine = 0;
-        // K rotation between the row tiles of a column tile (bit 30 of flags, gemm_wn_mma_kernel.inc): 8-bit weights, K unsplit, the L2 rule of the A8W8 tiles
-        p.flags &= ~(1 << 30);
-        if ((k8 || nb == mma::MXW8) && splitk == 1 && k_rotation_pays(a, (int64_t)64 * a.K)) p.flags |= (1 << 30);
+        // K rotation between the row tiles of a column tile (K_ORDER_ON, gemm_wn_mma_kernel.inc): 8-bit weights, K unsplit, the L2 rule of the A8W8 tiles
+        if ((k8 || nb == mma::MXW8) && splitk == 1 && k_rotation_pays(a, (int64_t)64 * a.K)) p.flags |= K_ORDER_ON;
         lp.fn = fn;
         lp.name = k8 ? "gemm_a16w8_kernel<64x64>" : (nv ? "gemm_nvfp4_f16_kernel<64x64>" : (nb == mma::MXW8 ? "gemm_a16w8_mxfp_kernel<64x64>" : "gemm_a16w4_mxfp_kernel<64x64>"));
         lp.grid = dim3((unsigned)tiles, splitk, 1);
@@ -178,7 +177,7 @@ bool plan_gemm_wn_mma_mx(const gemlite_hip_forward_args& a, WnParams& p, LaunchP
     if (splitk > units) return false;
     if (splitk > 1 && tiles > MAX_SPLITK_COUNTERS) return false;
     if ((uint64_t)splitk * bm * mma::BN * 4 >= (1ull << 31)) return false;
-    const void* fn = f16 ? mma_lookup_f16(2, nb, mi, 0, 0) : mma_lookup_bf16(2, nb, mi, 0, 0);
+    const void* fn = f16 ? mma_lookup_f16(2, nb, mi, 0) : mma_lookup_bf16(2, nb, mi, 0);
     if (!fn) return false;
     p.splitk = splitk;
     p.rows_per_slice = (int)a.K;  // E = 1: "packed rows" are k
@@ -258,7 +257,7 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
         if (((int64_t)(a.K / 32) * p.stride_meta_g + a.N) * 2 >= (1ll << 31)) return false;
         if (splitk > 1 && tiles > MAX_SPLITK_COUNTERS) return false;
         const bool f16 = tag_dt == GEMLITE_DT_FP16;
-        const void* fn = f16 ? mma_lookup_f16(8, nbits, 1, xdt, 0) : mma_lookup_bf16(8, nbits, 1, xdt, 0);
+        const void* fn = f16 ? mma_lookup_f16(8, nbits, 1, xdt) : mma_lookup_bf16(8, nbits, 1, xdt);
         if (!fn) return false;
         p.splitk = splitk;
         p.rows_per_slice = rows;
@@ -306,13 +305,13 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
     };
     int mi = 0, splitk = 0;
     // narrow tiles (32 MI x 64, KH = 4; round 4): tuning[2] = 32 + variant forces them (variants: gemm_wn_mma_kernel.inc, mma_pick_narrow);
-    // tuning[3] & 16384 keeps the round-3 choice (A/B runs)
+    // GEMLITE_TF_NO_NARROW_TILES keeps the round-3 choice (A/B runs)
     // Automatic: narrow_auto() above (4- / 2-bit words under 16-bit or 8-bit activations)
     int narrow_v = -1, narrow_sk = 0;
     if (a.tuning[2] >= 32 && a.tuning[2] <= 35) {
         narrow_v = a.tuning[2] - 32;
         narrow_sk = a.tuning[1] > 0 ? a.tuning[1] : 1;
-    } else if (a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(a.tuning[3] & 16384) && (nbits == 4 || nbits == 2)) {
+    } else if (a.tuning[0] == 0 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(caller_flags(a) & GEMLITE_TF_NO_NARROW_TILES) && (nbits == 4 || nbits == 2)) {
         if (const int na = narrow_auto(a.M, a.N, a.K, es)) {
             narrow_v = 0;
             narrow_sk = na;
@@ -330,11 +329,10 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
         const int64_t tiles = (int64_t)(a.N / 64) * ((a.M + bm - 1) / bm);
         if (splitk > 1 && tiles > MAX_SPLITK_COUNTERS) return false;
         const bool f16 = tag_dt == GEMLITE_DT_FP16;
-        const int expv = (int)(((unsigned)a.tuning[3] >> 20) & 63u) << 8;  // (development builds: K-loop ablation, see mma_exp_lookup)
         // round 6: the 64 x 64 tiles fetch their packed words through LDS (one DMA request per wave and step instead of four register loads per
-        // lane: cfgA M = 256 16.5 -> see profiles/r06/probe_mma_wl.log); tuning[3] & 131072 keeps the round-5 register path (A/B runs)
-        const bool wl = v == 0 && x16 && nbits == 4 && expv == 0 && !(a.tuning[3] & 131072);
-        const void* fn = f16 ? mma_lookup_f16(6, nbits, wl ? 4 : v, xdt, expv) : mma_lookup_bf16(6, nbits, wl ? 4 : v, xdt, expv);
+        // lane: cfgA M = 256 16.5 -> see profiles/r06/probe_mma_wl.log); GEMLITE_TF_WORDS_AS_REGISTER_LOADS keeps the round-5 register path (A/B runs)
+        const bool wl = v == 0 && x16 && nbits == 4 && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
+        const void* fn = f16 ? mma_lookup_f16(6, nbits, wl ? 4 : v, xdt) : mma_lookup_bf16(6, nbits, wl ? 4 : v, xdt);
         if (!fn) return false;
         p.splitk = splitk;
         p.rows_per_slice = rows;
@@ -406,7 +404,7 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
         // round of one-block-per-CU tiles (8960 x 1536 M = 256: two slices 30.8 us, one 16.0) and its 64-row tiles lose wherever 128 rows fill the
         // chip (5120 x 13824 M = 256: 77.2 vs 50.4)).  A block-time model instead, rounds x (fixed + us per 1024 k) + 1 us per slice, per block:
         // 64 rows 5 + 5.0, 128 rows 7 + 6.1, 256 rows 9 + 12; a slice keeps >= 1024 k.  60 cells after: 50 within 3 %, 58 within 10 %.
-        if (nbits == 2 && x16 && a.M > 64 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(a.tuning[3] & 16384)) {
+        if (nbits == 2 && x16 && a.M > 64 && a.tuning[1] == 0 && a.tuning[2] == 0 && !(caller_flags(a) & GEMLITE_TF_NO_NARROW_TILES)) {
             static const double FIX[3] = {5.0, 7.0, 9.0}, PER_K[3] = {5.0, 6.1, 12.0};
             const int64_t cus = resident_block_limit();
             double best = 1e30;
@@ -461,21 +459,20 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
     if (splitk > 1 && tiles > MAX_SPLITK_COUNTERS) return false;
     if ((uint64_t)splitk * bm * bn * 4 >= (1ull << 31)) return false;  // slab buffer descriptor range
     const bool f16 = tag_dt == GEMLITE_DT_FP16;
-    const int expv = (int)(((unsigned)a.tuning[3] >> 20) & 63u) << 8;  // (development builds: K-loop ablation, see mma_exp_lookup)
-    const void* fn = f16 ? mma_lookup_f16(wide ? 1 : 0, nbits, mi, xdt, expv) : mma_lookup_bf16(wide ? 1 : 0, nbits, mi, xdt, expv);
+    const void* fn = f16 ? mma_lookup_f16(wide ? 1 : 0, nbits, mi, xdt) : mma_lookup_bf16(wide ? 1 : 0, nbits, mi, xdt);
     // K-slice combine: reduce-scatter between the slices of a tile when they are certain to be co-resident (every block of the
     // launch fits on the device at once: <= one block per CU), the slices divide the tile's row blocks, and the variant exists
     // (4- / 2-bit words, 16-bit activations); else slabs + ticket.  From 4 slices on: with 2 slices the ticket protocol is as fast
     // or faster (cfgA 64x128 x 2: 19.6 vs 21.2 us, cfgB 128x128 x 2: 43.9 vs 43.4; with 4 slices of 256-row tiles 27.5 -> 25.1 and
-    // 47.9 -> 44.9, profiles/r03/probe_mma3_v3*.log).  tuning[3]: & 128 forces the ticket protocol, & 2048 takes the reduce-scatter
-    // with 2 slices too, & 256 = & 2048 + every block hands its rows over after one poll (tests of that path).
-    const bool use_xch = !wide && splitk > 1 && (splitk & (splitk - 1)) == 0 && mi >= 2 && splitk <= mi && !(a.tuning[3] & 128) &&
-                     (splitk >= 4 || (a.tuning[3] & (2048 | 256))) &&
+    // 47.9 -> 44.9, profiles/r03/probe_mma3_v3*.log).  GEMLITE_TF_COMBINE_TICKET forces the ticket protocol, GEMLITE_TF_COMBINE_REDUCE_SCATTER_2 takes
+    // the reduce-scatter with 2 slices too, GEMLITE_TF_COMBINE_HANDOVER_TEST = that + every block hands its rows over after one poll (tests of that path).
+    const bool use_xch = !wide && splitk > 1 && (splitk & (splitk - 1)) == 0 && mi >= 2 && splitk <= mi && !(caller_flags(a) & GEMLITE_TF_COMBINE_TICKET) &&
+                     (splitk >= 4 || (caller_flags(a) & (GEMLITE_TF_COMBINE_REDUCE_SCATTER_2 | GEMLITE_TF_COMBINE_HANDOVER_TEST))) &&
                      xdt == 0 && (nbits == 4 || nbits == 2) && tiles * splitk <= resident_block_limit();
-    if (use_xch) fn = f16 ? mma_lookup_f16(4, nbits, mi, 0, 1) : mma_lookup_bf16(4, nbits, mi, 0, 1);
+    if (use_xch) fn = f16 ? mma_lookup_f16(4, nbits, mi, 0) : mma_lookup_bf16(4, nbits, mi, 0);
     // round 6: the 128 x 128 tiles of 4-bit words under 16-bit activations fetch their packed words through LDS as well (slab + ticket combine)
-    const bool wl128 = !wide && !use_xch && mi == 4 && x16 && nbits == 4 && expv == 0 && !(a.tuning[3] & 131072);
-    if (wl128) fn = f16 ? mma_lookup_f16(7, nbits, mi, 0, 0) : mma_lookup_bf16(7, nbits, mi, 0, 0);
+    const bool wl128 = !wide && !use_xch && mi == 4 && x16 && nbits == 4 && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
+    if (wl128) fn = f16 ? mma_lookup_f16(7, nbits, mi, 0) : mma_lookup_bf16(7, nbits, mi, 0);
     if (!fn) return false;
     p.splitk = splitk;
     p.rows_per_slice = rows;  // ALL packed rows: the kernel derives each slice's step range itself

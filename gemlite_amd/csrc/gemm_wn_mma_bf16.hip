@@ -3,5 +3,5 @@
 #include "gemm_wn_mma_kernel.inc"
 
 namespace gl {
-const void* mma_lookup_bf16(int kind, int nbits, int mi, int xdt, int xch) { return mma_lookup<bf16_tag>(kind, nbits, mi, xdt, xch); }
+const void* mma_lookup_bf16(int kind, int nbits, int mi, int xdt) { return mma_lookup<bf16_tag>(kind, nbits, mi, xdt); }
 }  // namespace gl

@@ -3,5 +3,5 @@
 #include "gemm_wn_mma_kernel.inc"
 
 namespace gl {
-const void* mma_lookup_f16(int kind, int nbits, int mi, int xdt, int xch) { return mma_lookup<half_tag>(kind, nbits, mi, xdt, xch); }
+const void* mma_lookup_f16(int kind, int nbits, int mi, int xdt) { return mma_lookup<half_tag>(kind, nbits, mi, xdt); }
 }  // namespace gl

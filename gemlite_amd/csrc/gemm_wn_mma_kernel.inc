@@ -344,7 +344,7 @@ __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, unsigned ch
 }  // namespace mma
 
 // MI 32-row blocks per wave (tile rows = 32 * MI), KSTEP k per step (each wave: KSTEP / 2).
-// EXP (development builds only, -DGL_MMA_EXPERIMENTS + tuning[3] >> 8): drop parts of the K loop to see what each costs —
+// EXP (development builds only, -DGL_MMA_EXPERIMENTS + GEMLITE_DEV_ABLATION): drop parts of the K loop to see what each costs —
 // 1 barrier + counted wait, 2 dequant VALU, 4 A-fragment reads, 8 x DMA requests, 16 weight requests, 32 the scalar address
 // arithmetic of the requests (constant offsets).  Results are wrong.
 // KH = 2 (default): tile 32 MI x 128, wave (cg = wave & 3, kh = wave >> 2) owns 32 columns x one HALF of every K step.
@@ -415,14 +415,14 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
     const int cg = KH == 1 ? wave : (wave & (NCG - 1)), kh = KH == 1 ? 0 : (KH == 2 ? (wave >> 2) : (wave >> 1));
     const int col = lane & 31, h = lane >> 5;
     const int mtiles = (p.M + BM - 1) / BM;
-    // (tile, K slice) of this block.  Opt-in (tuning[3] & 8): block b runs on XCD b % 8 and every XCD has its own L2, so
+    // (tile, K slice) of this block.  Opt-in (GEMLITE_TF_XCD_SLICE_MAP): block b runs on XCD b % 8 and every XCD has its own L2, so
     // giving all blocks of one XCD the SAME K slice keeps that slice's x rows (re-read by every column tile) in one L2.
     // Measured SLOWER (cfgB 53 vs 46 us, cfgA 21.2 vs 19.1 us: 32 CUs asking for the same lines at once), so the default
     // is the plain (x = tile, y = slice) grid.  Speed only; any map is correct.
     int bid = blockIdx.x, slice = blockIdx.y;
     {
         const int T = gridDim.x, S = gridDim.y;
-        if ((p.flags & 8) && S > 1 && (8 % S) == 0 && ((T * S) & 7) == 0) {
+        if ((p.flags & GEMLITE_TF_XCD_SLICE_MAP) && S > 1 && (8 % S) == 0 && ((T * S) & 7) == 0) {
             const int lin = blockIdx.x + T * blockIdx.y, xcd = lin & 7, idx = lin >> 3;
             slice = xcd % S;
             bid = idx * (8 / S) + xcd / S;
@@ -451,11 +451,11 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
     const int row_s0 = s_begin * STEP_ROWS;  // first packed row of the slice
     const int k_s0 = row_s0 * G::E;
 
-    // opt-in timeline (tuning[3] & 4): wave 0 of EVERY block (the first 256) stores the 100 MHz global clock (s_memrealtime)
+    // opt-in timeline (GEMLITE_TF_TIMELINE): wave 0 of EVERY block (the first 256) stores the 100 MHz global clock (s_memrealtime)
     // at 8 points behind the tickets, slot [block][i]: 0 start | 1 prologue barrier | 2 first step | 3 loop done | 4 K halves
     // added | 5 partial tile sent | 6 peers arrived / ticket taken | 7 output stored   (scripts/timeline_mma3.py)
     const int lin_block = blockIdx.x + gridDim.x * blockIdx.y;
-    const bool probe = (p.flags & 4) && p.counters && wave == 0 && lane == 0 && lin_block < 256;
+    const bool probe = (p.flags & GEMLITE_TF_TIMELINE) && p.counters && wave == 0 && lane == 0 && lin_block < 256;
     unsigned long long* stamps = (unsigned long long*)(p.counters + MAX_SPLITK_COUNTERS) + lin_block * 8;
     auto stamp = [&](int i) __attribute__((always_inline)) {
         if (probe) stamps[i] = __builtin_amdgcn_s_memrealtime();
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
     // (cfgA 16.75 vs 16.9 with it; the same row tiles on one XCD for the 128-row tiles + rotation: cfgB 43.7 -> 44.3) — their loops are not bound by
     // the weight stream: profiles/r06/probe_a16w8_tiles_rotation.log, probe_xcd_map_and_rotation_w4_tiles_no_gain.log.  The fp32 sums of a row
     // tile are added in rotated K order: last-bit differences between row tiles, none between runs.
-    const int rot = (p.flags & (1 << 30)) && mtiles > 1 ? (mt * nsteps) / mtiles : 0;
+    const int rot = (p.flags & K_ORDER_ON) && mtiles > 1 ? (mt * nsteps) / mtiles : 0;
     auto kof = [&](int step) __attribute__((always_inline)) { const int k = step + rot; return k >= nsteps ? k - nsteps : k; };
     auto req_b = [&](BStep& b, int step, int it) __attribute__((always_inline)) {
         if constexpr (MXW) step = kof(step);   // (only the K-contiguous geometries are ever rotated: the three scalar instructions per request cost cfgA 0.2 us)
@@ -826,7 +826,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
     //      more LDS round trip and barrier with a quarter of the block working — ~0.4 of the 1.5 us tail of the unsplit 64 x 64 tiles.
     constexpr bool DIRECT_EPI = KH >= 2 && (KH * BM * C_PITCH * 4 <= 144 * 1024);
     if constexpr (DIRECT_EPI) {
-        if (p.splitk == 1 && !(p.flags & 262144)) {  // (tuning[3] & 262144: the round-5 epilogue, A/B runs)
+        if (p.splitk == 1 && !(p.flags & GEMLITE_TF_ROUND5_TILE_EPILOGUE)) {  // (else the round-5 epilogue, A/B runs)
             __syncthreads();
             float* parts = (float*)smem;  // [KH][BM][C_PITCH]
 #pragma unroll
@@ -952,7 +952,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
             bool gave_up = false;
             {
                 // ~0.3 us per poll: the usual skew between the slices of a tile is a few us; after ~100 us the peers are not coming soon
-                const unsigned polls = (p.flags & 256) ? 1u : 384u;  // tuning[3] & 256: give up at once (tests of the hand-over)
+                const unsigned polls = (p.flags & GEMLITE_TF_COMBINE_HANDOVER_TEST) ? 1u : 384u;  // give up at once (tests of the hand-over)
                 if (tid == 0) {
                     unsigned n = 0;
                     while ((__hip_atomic_load(cnt + slice, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xffffu) != (unsigned)(S - 1)) {
@@ -1287,8 +1287,9 @@ static const void* mma_pick_wide(int nbits, int mi) {
 // kernel template for one 16-bit type each, in parallel).  kind: 0 register path (nbits, mi, xdt) | 1 wide tiles (nbits, mi) |
 // 2 block-scaled weights (nbits = MXW8 / MXW4 / NVW4, mi) | 4 reduce-scatter combine (nbits, mi) | 6 narrow tiles (nbits, variant) | 7 128 x 128 tiles, words through LDS (nbits) | 8 groups of 32, 32-row tiles (nbits, xdt)
 #ifdef GL_MMA_EXPERIMENTS
-// development builds (make MMA_EXTRA=-DGL_MMA_EXPERIMENTS): the K-loop ablations of the two M = 256 headline kernels, selected by
-// tuning[3] >> 20 (the planner passes it down as `xch`): 4-bit words, 64 x 64 narrow tiles (kind 6, variant 0) and 128 x 128 tiles (kind 0, mi 4)
+// development builds (make MMA_EXTRA=-DGL_MMA_EXPERIMENTS): the K-loop ablations of the two M = 256 headline kernels, selected by the
+// environment variable GEMLITE_DEV_ABLATION: 4-bit words, 64 x 64 narrow tiles (kind 6) and 128 x 128 tiles (kind 0, mi 4; kind 7).  The ablation
+// kernels fetch the packed words as register loads: they also stand in for the words-through-LDS variants (kind 6 variant 4, kind 7)
 template <typename Tag, int EXP>
 static const void* mma_exp_pick(int kind) {
     mma_kernel_fn f = kind == 6 ? gemm_wn_mma_kernel<Tag, 4, 2, 256, 6, 3, EXP, 0, 4> : gemm_wn_mma_kernel<Tag, 4, 4, 128, 6, 3, EXP, 0>;
@@ -1311,9 +1312,9 @@ static const void* mma_exp_lookup(int kind, int exp) {
 #endif
 
 template <typename Tag>
-static const void* mma_lookup(int kind, int nbits, int mi, int xdt, int xch) {
+static const void* mma_lookup(int kind, int nbits, int mi, int xdt) {
 #ifdef GL_MMA_EXPERIMENTS
-    if (xch >= 256 && nbits == 4 && xdt == 0 && ((kind == 6 && mi == 0) || (kind == 0 && mi == 4))) return mma_exp_lookup<Tag>(kind, xch >> 8);
+    if (const int e = dev_ablation(); e && nbits == 4 && xdt == 0 && ((kind == 6 && (mi == 0 || mi == 4)) || (kind == 0 && mi == 4) || kind == 7)) return mma_exp_lookup<Tag>(kind == 6 ? 6 : 0, e);
 #endif
     switch (kind) {
         case 0: return mma_pick<Tag>(nbits, mi, xdt);

@@ -337,7 +337,7 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void gemm_w4_rows_kernel(const c
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host-side planning.  tuning[0] = 9 forces this kernel (any M), tuning[3] & 65536 = never (the round-4 choice, A/B runs)
+// host-side planning.  tuning[0] = 9 forces this kernel (any M), GEMLITE_TF_NO_ROWS_KERNEL = never (the round-4 choice, A/B runs)
 // ---------------------------------------------------------------------------------------------------------------------
 typedef void (*rows5_fn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, int, uint32_t, uint32_t);
 

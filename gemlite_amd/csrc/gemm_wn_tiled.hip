@@ -262,10 +262,10 @@ __global__ __launch_bounds__(256, (MI <= 4 ? 2 : 1)) void gemm_w4_tiled_kernel(c
                 for (int mi = 0; mi < MI; ++mi)
                     af[(ks + 1) & 1][mi] = *(const u32x4*)(abase + mi * 32 * (TBK * 2) + a_off[ks + 1]);
             }
-            if (p.flags & 1) __builtin_amdgcn_s_setprio(1);  // experiment (tuning[3] & 1): favour the MFMA-issuing wave
+            if (p.flags & GEMLITE_TF_TILED_SETPRIO) __builtin_amdgcn_s_setprio(1);  // experiment: favour the MFMA-issuing wave
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) acc[mi] = mfma32<Tag>(af[ks & 1][mi], bfrag[ks], acc[mi]);
-            if (p.flags & 1) __builtin_amdgcn_s_setprio(0);
+            if (p.flags & GEMLITE_TF_TILED_SETPRIO) __builtin_amdgcn_s_setprio(0);
         }
     };
 
@@ -377,7 +377,7 @@ struct DeqPipe<bf16_tag> {
 // registers).  A dequantised weight fragment feeds MI MFMAs, and one wave per SIMD can hide only ~5 other
 // instructions behind a 32-cycle MFMA (MI355X_MICROARCH.md), so MI = 8 halves the VALU work per MFMA slot:
 // 19 dequant instructions per packed word / 8 MFMAs + 1 ds_read per slot fits that budget, MI = 4 does not.
-// EXP (development, tuning[3] >> 8): drop parts of the loop to see what each costs — 1 LDS writes, 2 barrier,
+// EXP (development builds, -DGL_TILED_EXPERIMENTS + GEMLITE_DEV_ABLATION): drop parts of the loop to see what each costs — 1 LDS writes, 2 barrier,
 // 4 dequant VALU, 8 fragment reads, 16 global loads.  Results are wrong for EXP != 0.
 template <typename Tag, int MI, int EXP = 0>
 __global__ __launch_bounds__(256, (MI <= 4 ? 2 : 1)) void gemm_w4_pipe_kernel(const WnParams p) {
@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256, (MI <= 4 ? 2 : 1)) void gemm_w4_pipe_kernel(co
     for (int ks = 0; ks < 4; ++ks) woff[ks] = (uint32_t)((kb + 2 * ks) * sw + n) * 4u;
     const uint32_t moff = (uint32_t)n * 2u;
     struct BStep { uint32_t w[4]; uint16_t s, z; };
-    // (round 1 had two timing probes here, tuning[3] & 8 / & 16, that pushed the weight / activation offsets out of range — wrong
+    // (round 1 had two timing probes here, tuning[3] values 8 / 16, that pushed the weight / activation offsets out of range — wrong
     //  results on request; removed in round 3: & 8 is the documented XCD-map switch of the 8-wave kernel, and this kernel is that
     //  kernel's fallback for K = 64 x odd)
     constexpr uint32_t bkill = 0u, akill = 0u;
@@ -667,7 +667,7 @@ bool plan_gemm_wn_tiled(const gemlite_hip_forward_args& a, WnParams& p, LaunchPl
 #endif
         lp.fn = f16 ? (const void*)gemm_w4_pipe_kernel<half_tag, 4> : (const void*)gemm_w4_pipe_kernel<bf16_tag, 4>;
 #ifdef GL_TILED_EXPERIMENTS
-        if (mi == 8 && !f16) switch (a.tuning[3] >> 8) {
+        if (mi == 8 && !f16) switch (dev_ablation()) {
             case 1: lp.fn = (const void*)gemm_w4_pipe_kernel<bf16_tag, 8, 1>; break;
             case 2: lp.fn = (const void*)gemm_w4_pipe_kernel<bf16_tag, 8, 2>; break;
             case 3: lp.fn = (const void*)gemm_w4_pipe_kernel<bf16_tag, 8, 3>; break;

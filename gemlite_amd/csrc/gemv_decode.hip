@@ -79,7 +79,7 @@ __global__ __launch_bounds__(1024, 1) void gemv_w4_decode3_kernel(const char* wb
         ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
     };
 
-    // opt-in timeline (tuning[3] & 4): the mode bit is a preloaded SGPR, so a normal launch never touches `counters` (the one
+    // opt-in timeline (GEMLITE_TF_TIMELINE): the mode bit is a preloaded SGPR, so a normal launch never touches `counters` (the one
     // argument behind the preloaded 14 dwords) and never waits for a kernarg load
     auto stamp = [&](int i) {
         if (__builtin_expect((modes & M_PROBE) != 0u, 0)) {

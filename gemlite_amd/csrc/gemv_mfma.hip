@@ -142,9 +142,9 @@ __global__ __launch_bounds__(NW * 64, 1) void gemv_mfma_kernel(const WnParams p)
     unsigned char* xw = smem + (size_t)wave * (2 * MB * 1024);            // this wave's x slots: [2 buffers][MB rows][64 chunks x 16 B]
     float* red = (float*)(smem + (size_t)NW * (2 * MB * 1024));           // [NW][64][4 V]
 
-    // opt-in timeline (tuning[3] & 4, needs a workspace): wave 0 of every block stores the 100 MHz global clock at
+    // opt-in timeline (GEMLITE_TF_TIMELINE, needs a workspace): wave 0 of every block stores the 100 MHz global clock at
     // [start, first batch requested, arithmetic done, output stored] (scripts/timeline_decode.py)
-    const bool probe = (p.flags & 4) && p.counters && wave == 0 && lane == 0 && blockIdx.x < 1024;
+    const bool probe = (p.flags & GEMLITE_TF_TIMELINE) && p.counters && wave == 0 && lane == 0 && blockIdx.x < 1024;
     unsigned long long* stamps = (unsigned long long*)(p.counters + MAX_SPLITK_COUNTERS) + blockIdx.x * 4;
     auto stamp = [&](int i) {
         if (probe) stamps[i] = __builtin_amdgcn_s_memrealtime();

@@ -302,13 +302,13 @@ __global__ __launch_bounds__(NW * 64, ((MB * (16 / NBITS) >= 32 || R * MB >= 32 
         xsum_s[task] = sum_s;
     };
 
-    // opt-in timeline (tuning[3] & 4, needs a workspace): lane 0 of every wave of block (0,0) stores s_memtime stamps
+    // opt-in timeline (GEMLITE_TF_TIMELINE, needs a workspace): lane 0 of every wave of block (0,0) stores s_memtime stamps
     // (round 3: scripts/isa_loops.py shows hipcc waiting with s_waitcnt vmcnt(0) at the head of the steady-state loop below, and
     //  these conditional stamp STORES are one of its reasons (stores count in vmcnt on gfx9).  Compiling them out, moving the
     //  scalar-zero load above the priming and dropping the in-loop stamp turned the wait into vmcnt(6) + a vmcnt(0) a few
     //  instructions later AND changed the schedule for the worse: 16384^2 23.7 -> 28.0 us, 8192^2 10.4 -> 11.3 us, 4096^2 4.80 ->
     //  4.95 us (profiles/r03/probe_gemv3_v8*.log).  The version with the stamps is the one that ships.)
-    const bool probe = (p.flags & 4) && p.counters && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0;
+    const bool probe = (p.flags & GEMLITE_TF_TIMELINE) && p.counters && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0;
     unsigned long long* stamps = (unsigned long long*)(p.counters + MAX_SPLITK_COUNTERS) + wave * 16;
     auto stamp = [&](int i) {
         if (probe) stamps[i] = __builtin_readcyclecounter();
@@ -620,10 +620,10 @@ __global__ __launch_bounds__(NW * 64, 1) void gemv_w4_decode_kernel(const WnPara
         }
     };
 
-    // opt-in timeline (tuning[3] & 4, needs a workspace): wave 0 of EVERY block stores the constant-rate global clock
+    // opt-in timeline (GEMLITE_TF_TIMELINE, needs a workspace): wave 0 of EVERY block stores the constant-rate global clock
     // (s_memrealtime, 100 MHz) at four points, slot [block][i] — when blocks start, how long they wait for their data, when the
     // last one leaves
-    const bool probe = (p.flags & 4) && p.counters && wave == 0 && lane == 0 && blockIdx.x < 1024;
+    const bool probe = (p.flags & GEMLITE_TF_TIMELINE) && p.counters && wave == 0 && lane == 0 && blockIdx.x < 1024;
     unsigned long long* stamps = (unsigned long long*)(p.counters + MAX_SPLITK_COUNTERS) + blockIdx.x * 4;
     auto stamp = [&](int i) {
         if (probe && i < 4) stamps[i] = __builtin_amdgcn_s_memrealtime();
@@ -839,7 +839,7 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
         // K = 11008 / 8960 (Llama-2-7B down_proj, Qwen2.5-1.5B): 16-column tiles need 64-row chunks with 4 rows per
         // lane; the 16-wave direct-x variant takes 2 rows per lane (32-row chunks: 43 / 35 of them)
         bool force_xd16 = false;
-        if (!r && cq == 2 && nbits == 4 && mb == 1 && rows % (G * 2) == 0 && rpg % 2 == 0 && (a.tuning[3] & 3) != 1) {
+        if (!r && cq == 2 && nbits == 4 && mb == 1 && rows % (G * 2) == 0 && rpg % 2 == 0 && (caller_flags(a) & GEMLITE_TF_GEMV_X_MODE_MASK) != GEMLITE_TF_GEMV_X_THROUGH_LDS) {
             r = 2;
             force_xd16 = true;
         }
@@ -868,7 +868,7 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
         if (tiles > MAX_SPLITK_COUNTERS && splitk > 1) return false;
         // tuning[3]: 0 auto | 1 stage x in LDS | 2 load x directly.  Direct x pays when a wave has <= 2 steps.
         const int steps = (units / splitk + 3) / 4;  // chunks per wave (4 waves)
-        const int xmode = a.tuning[3] & 3;
+        const int xmode = caller_flags(a) & GEMLITE_TF_GEMV_X_MODE_MASK;
         bool xd = force_xd16 || (nbits == 4 && mb == 1 && r == 4 && (xmode == 2 || (xmode == 0 && steps <= 2)));
         // tuning[2]: 0 auto | 4 | 8 waves per block.  8 waves: one chunk per wave, two waves per SIMD (short K only)
         int nw = force_xd16 ? 16 : 4;
@@ -910,9 +910,9 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
         p.rows_per_slice = rows / splitk;
         lp.fn = fn;
         // round 3: the short-K decode kernel (quad-shared x dwords, non-temporal weights, DPP + one-wave reduction) takes the
-        // direct-x 16-column shapes; tuning[3] & 16 keeps the round-2 kernel (A/B runs), & 32 = default-policy weight loads
-        if (xd && cq == 2 && splitk == 1 && mb == 1 && nbits == 4 && !(a.tuning[3] & 16) && ((nw == 16 && r == 2) || (nw == 8 && r == 4))) {
-            const bool f16 = a.input_dtype == GEMLITE_DT_FP16, nt = !(a.tuning[3] & 32);
+        // direct-x 16-column shapes; GEMLITE_TF_GEMV_ROUND2_KERNEL keeps the round-2 kernel (A/B runs), GEMLITE_TF_GEMV_DEFAULT_POLICY_LOADS = default-policy weight loads
+        if (xd && cq == 2 && splitk == 1 && mb == 1 && nbits == 4 && !(caller_flags(a) & GEMLITE_TF_GEMV_ROUND2_KERNEL) && ((nw == 16 && r == 2) || (nw == 8 && r == 4))) {
+            const bool f16 = a.input_dtype == GEMLITE_DT_FP16, nt = !(caller_flags(a) & GEMLITE_TF_GEMV_DEFAULT_POLICY_LOADS);
             typedef void (*kfn)(const WnParams);
             kfn k;
             if (nw == 16) k = f16 ? (nt ? gemv_w4_decode_kernel<half_tag, 2, 16, true> : gemv_w4_decode_kernel<half_tag, 2, 16, false>)
@@ -927,9 +927,9 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
             lp.slab_bytes = 0;
             lp.ws_bytes = 0;
             // round 4: the same arithmetic behind preloaded scalar arguments, weights requested first (gemv_decode.hip); the common
-            // case only — no channel scales in the epilogue, contiguous output row, group size a power of two.  tuning[3] & 4096
+            // case only — no channel scales in the epilogue, contiguous output row, group size a power of two.  GEMLITE_TF_GEMV_ROUND3_DECODE
             // keeps the round-3 kernel (A/B runs).
-            if (nw == 16 && !(a.tuning[3] & 4096) && a.channel_scale_mode == 0 && a.stride_on == 1 && p.gs_shift >= 0 && p.gs_shift < 32 &&
+            if (nw == 16 && !(caller_flags(a) & GEMLITE_TF_GEMV_ROUND3_DECODE) && a.channel_scale_mode == 0 && a.stride_on == 1 && p.gs_shift >= 0 && p.gs_shift < 32 &&
                 (int64_t)rows * 16 < (1ll << 31)) {
                 // (the scalar-zero bit and pointer only when the mode HAS a zero point — a C-ABI caller may pass zero_is_scalar
                 //  with zeros = NULL for W_group_mode 0 / 2, and the kernel reads zp[0] whenever the bit is set)
@@ -947,7 +947,7 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
                 lp.d3.sw4 = (uint32_t)p.stride_wk * 4u;
                 lp.d3.mstride2 = (need_s2 || need_z2) ? (uint32_t)p.stride_meta_g * 2u : 0u;
                 lp.d3.nch_total = rows / 32;
-                lp.d3.modes = (uint32_t)p.w_mode | (z_scalar2 ? 16u : 0u) | (((tiles & 15) == 0) ? 32u : 0u) | ((a.tuning[3] & 4) ? 64u : 0u) |
+                lp.d3.modes = (uint32_t)p.w_mode | (z_scalar2 ? 16u : 0u) | (((tiles & 15) == 0) ? 32u : 0u) | ((caller_flags(a) & GEMLITE_TF_TIMELINE) ? 64u : 0u) |
                               ((uint32_t)p.gs_shift << 8);
                 lp.d3.counters = nullptr;
             }

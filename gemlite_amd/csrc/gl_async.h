@@ -63,7 +63,7 @@ __device__ __forceinline__ void req_lds4(srd_t rs, uint32_t lds_addr, uint32_t v
                  : : "v"(voff), "s"(rs), "s"(soff), "s"(lds_addr) : "memory", "m0");
 }
 #pragma clang diagnostic pop
-// K order of the row tiles that share a weight column tile (round 6; gemm_a8w8_sq_kernel has the reasoning).  flags bit 30 = on; bits 24 .. 27 = 0: row tile
+// K order of the row tiles that share a weight column tile (round 6; gemm_a8w8_sq_kernel has the reasoning).  flags & K_ORDER_ON = on (gl_common.h); group field = 0: row tile
 // mt starts at step mt nsteps / mtiles (whole-K rotation); = 1 + log2(G): the K steps form groups of G, and inside every run of mtiles groups row tile mt takes
 // them in the order mt, mt + 1, ... — each tile LEADS (pulls HBM-cold lines) on one group of the run and follows its siblings on the others, so the lines only have
 // to survive mtiles - 1 groups in L2 instead of a whole rotation.  A tail of fewer than mtiles groups keeps the plain order.
@@ -76,8 +76,8 @@ struct KOrder {
     uint32_t magic;  // ceil(2^32 / P)
     __device__ __forceinline__ void init(int mt_, int mtiles, int nsteps_, int flags) {
         mode = 0; rot = 0; nsteps = nsteps_; gsh = 0; P = mtiles; mt = mt_; ngroups = 0; magic = 0u;
-        if (!(flags & (1 << 30)) || mtiles < 2) return;
-        const int gm = (flags >> 24) & 15;
+        if (!(flags & K_ORDER_ON) || mtiles < 2) return;
+        const int gm = (flags >> K_ORDER_GROUP_SHIFT) & 15;
         if (gm == 0) {
             mode = 1;
             rot = __builtin_amdgcn_readfirstlane((mt_ * nsteps_) / mtiles);

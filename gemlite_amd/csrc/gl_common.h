@@ -308,11 +308,22 @@ __device__ __forceinline__ void group_affine(float s, float z, int w_mode, float
 
 // Workspace layout: [arrival counters: MAX_SPLITK_COUNTERS x u32 | slabs].  The counters sit at a FIXED
 // place so that slab payload of one shape can never alias the counters of another; kernels leave them zero.
-// The last 4096 words of the block belong to the opt-in timeline probes (tuning[3] & 4): never used as tickets.
+// The last 4096 words of the block belong to the opt-in timeline probes (GEMLITE_TF_TIMELINE): never used as tickets.
 constexpr int COUNTER_WORDS = 65536;
 constexpr int PROBE_WORDS = 4096;
 constexpr int MAX_SPLITK_COUNTERS = COUNTER_WORDS - PROBE_WORDS;
 constexpr uint64_t COUNTER_BYTES = (uint64_t)COUNTER_WORDS * 4;
+
+// tuning[3] as the kernels see it (WnParams::flags / GenericParams::flags): the caller's public bits (GEMLITE_TF_*), then what the planner adds.
+// The planner's own bits: K_ORDER_ON turns on the K order of the row tiles of a column tile (KOrder, gl_async.h); its group field is bits 24 .. 27,
+// the same bits as the public GEMLITE_TF_K_ORDER_GROUP_MASK override: 1 + log2(steps per group), 0 = whole-K rotation.
+constexpr int K_ORDER_ON = 1 << 30;
+constexpr int K_ORDER_GROUP_SHIFT = 24;
+constexpr int K_ORDER_GROUPS_OF_1 = 1 << K_ORDER_GROUP_SHIFT;  // group field value 1: groups of one K step
+static inline int caller_flags(const gemlite_hip_forward_args& a) { return a.tuning[3] & GEMLITE_TF_PUBLIC_MASK; }
+#if defined(GL_MMA_EXPERIMENTS) || defined(GL_TILED_EXPERIMENTS)  // development builds: the EXP of the K-loop ablation kernels
+static inline int dev_ablation() { const char* s = getenv("GEMLITE_DEV_ABLATION"); return s ? atoi(s) : 0; }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // split-K hand-off words: write-through (sc1) stores / loads at agent scope

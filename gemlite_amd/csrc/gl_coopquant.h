@@ -27,7 +27,6 @@ namespace gl {
 namespace cq {
 
 constexpr int STEAL_AFTER = 24;   // polls (~0.6 us each) before a waiting block quantises a missing row itself
-constexpr int TEST_NO_PRODUCE = 32768;  // GenericParams::flags (tuning[3]) bit, tests only: no block quantises its own rows — every row is stolen
 constexpr int MAX_ROWS = 1024;    // flags live in the ticket words of the workspace: [0, M) row flags, [M] departures
 
 // workspace bytes behind the counters: [M x K quantised bytes, padded to 256][M fp32 scales, padded to 256]
@@ -98,7 +97,7 @@ __device__ __forceinline__ void quantise_row(const GenericParams& p, int m, floa
 // dispatcher places, hold no weight requests and leave as soon as their flags are up.
 template <int QDT>
 __device__ __forceinline__ void produce(const GenericParams& p, int nprod, float* lds) {
-    if (p.flags & TEST_NO_PRODUCE) return;
+    if (p.flags & GEMLITE_TF_QUANT_NO_PRODUCER_TEST) return;  // (tests only: every row is stolen)
     for (int m = blockIdx.x; m < p.M; m += nprod) quantise_row<QDT>(p, m, lds);
 }
 

@@ -221,7 +221,6 @@ typedef struct gemlite_hip_forward_args {
      *                              through LDS-DMA, one request per wave and step); groups of 32 run on 32-row tiles with two metadata pairs per
      *                              sub-block ("<32x128,g32>": [1] K slices, [0] and [2] must be 0)
      *   [3] & 4: development timeline stamps (needs a workspace)   [3] & 8: XCD-aware (tile, K slice) map (opt-in).
-     *   [3] >> 20: K-loop ablation of development builds (make MMA_EXTRA=-DGL_MMA_EXPERIMENTS); ignored by the shipped library.
      *   A value that does not apply to the shape makes the planner fall through to its own choice or to another family;
      *   it never produces a wrong result. */
     int32_t tuning[4];
@@ -256,16 +255,23 @@ enum gemlite_hip_tuning2 {                 /* tuning[2]: tile geometry of the 8-
     GEMLITE_T2_GEMV_8WAVES_2ROWS = 82, GEMLITE_T2_GEMV_4WAVES_8ROWS = 48
 };
 enum gemlite_hip_tuning_flags {            /* tuning[3]: bit flags (A/B switches and test hooks; 0 = the shipped defaults) */
-    GEMLITE_TF_GEMV_X_THROUGH_LDS = 1, GEMLITE_TF_GEMV_X_DIRECT = 2,        /* (& 3) */
+    GEMLITE_TF_GEMV_X_THROUGH_LDS = 1, GEMLITE_TF_GEMV_X_DIRECT = 2,
+    GEMLITE_TF_GEMV_X_MODE_MASK = 3,             /* field: 0 = auto, else one of the two values above */
+    /* the same two bits in other families: the wave count of the block-scaled decode kernel (a field, & 3: 1 = 4 waves, 2 = 16 waves,
+     * 0 = auto) and s_setprio around the MFMAs of the round-1 4-wave tiled kernel (bit 0) */
+    GEMLITE_TF_MX_GEMV_WAVES_MASK = 3, GEMLITE_TF_MX_GEMV_4_WAVES = 1, GEMLITE_TF_MX_GEMV_16_WAVES = 2,
+    GEMLITE_TF_TILED_SETPRIO = 1,
     GEMLITE_TF_TIMELINE = 4,                     /* development stamps (needs a workspace) */
     GEMLITE_TF_XCD_SLICE_MAP = 8,                /* XCD-aware (tile, K slice) map of the tile kernel */
     GEMLITE_TF_GEMV_ROUND2_KERNEL = 16, GEMLITE_TF_GEMV_DEFAULT_POLICY_LOADS = 32,
+    GEMLITE_TF_MX_PLAIN_TILE_ORDER = 16,         /* same bit: plain M-fastest tile order of the block-scaled 256 x 256 tiles */
     GEMLITE_TF_A8W8_WEIGHTS_FROM_MEMORY = 64,
     GEMLITE_TF_COMBINE_TICKET = 128, GEMLITE_TF_COMBINE_HANDOVER_TEST = 256,
     GEMLITE_TF_NO_MFMA_GEMV = 512, GEMLITE_TF_FORCE_MFMA_GEMV = 1024,
     GEMLITE_TF_COMBINE_REDUCE_SCATTER_2 = 2048,
     GEMLITE_TF_GEMV_ROUND3_DECODE = 4096,
     GEMLITE_TF_NO_NARROW_TILES = 16384,
+    GEMLITE_TF_MX_NO_SLICE_RULE = 16384,         /* same bit: the block-scaled 128-row tiles keep the fill-the-chip K slice count */
     GEMLITE_TF_QUANT_NO_PRODUCER_TEST = 32768,
     GEMLITE_TF_NO_ROWS_KERNEL = 65536,           /* the round-4 choice for 2 .. 64 rows */
     GEMLITE_TF_WORDS_AS_REGISTER_LOADS = 131072, /* round 6: the round-5 weight path of the 64 x 64 / 128 x 128 4-bit tiles */
@@ -275,7 +281,8 @@ enum gemlite_hip_tuning_flags {            /* tuning[3]: bit flags (A/B switches
     GEMLITE_TF_W8_ROWS_LDS_BELOW_4_ROWS = 1048576, /* A16W8: take w8_rows_lds_kernel at 1 .. 3 rows too (default: from 4) */
     GEMLITE_TF_A8W8_TILE_REQUESTS_FIRST = 2097152, /* round 6: the round-4 order of a K step of the 64 x 64 A8W8 tile (DMA requests in front of the LDS reads) */
     GEMLITE_TF_NO_K_ROTATION = 4194304,            /* round 6: every row tile of the unsplit tiles of 8-bit weights walks K in the plain order */
-    GEMLITE_TF_K_ORDER_GROUP_MASK = 0x0F000000     /* round 6: bits 24 .. 27 = 1 + log2(steps per group) of the grouped K order between the row tiles of a column tile (0 = the planner's choice) */
+    GEMLITE_TF_K_ORDER_GROUP_MASK = 0x0F000000,    /* round 6: bits 24 .. 27 = 1 + log2(steps per group) of the grouped K order between the row tiles of a column tile (0 = the planner's choice) */
+    GEMLITE_TF_PUBLIC_MASK = 0x0FFFDFFF            /* every bit named above (0 .. 12, 14 .. 27).  The library ignores the others: bits 28 .. 31 are its own */
 };
 
 /* Library / ABI identification (host only, no device access). */

@@ -1,5 +1,6 @@
-"""K-loop ablation of the 8-wave MFMA kernel (needs `make -C gemlite_amd/csrc MMA_EXTRA=-DGL_MMA_EXPERIMENTS`):
-EXP bits — 1 barrier + counted wait, 2 dequant VALU (and with it the weight requests), 4 A-fragment reads, 8 x DMA, 16 weight requests."""
+"""K-loop ablation of the 8-wave MFMA kernel (needs `make -C gemlite_amd/csrc MMA_EXTRA=-DGL_MMA_EXPERIMENTS`), selected by the
+environment variable GEMLITE_DEV_ABLATION: EXP bits — 1 barrier + counted wait, 2 dequant VALU, 4 A-fragment reads, 8 x DMA, 16 weight
+requests (the values the library builds: 1, 2, 4, 6, 8, 18, 30, 31; 128 x 128 tiles only)."""
 import json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,10 +21,11 @@ for tag, N, K, nl, cfgs in (("cfgB", 8192, 8192, 8, ((2, 4), (1, 4), (4, 8))), (
     x = (torch.randn(256, K, generator=g, device=DEV) / 10).to(bf)
     for sk, mi in cfgs:
         row = {}
-        for E in (0, 32, 2, 34, 31, 63):
-            if mi not in (4, 8) and E:
+        for E in (0, 2, 4, 8, 31):
+            if mi != 4 and E:
                 continue
-            t = (0, sk, mi, E << 8)
+            os.environ["GEMLITE_DEV_ABLATION"] = str(E)
+            t = (0, sk, mi, 0)
             i = [0]
 
             def launch():

@@ -370,6 +370,45 @@ def test_planner_fuzz_never_crashes_and_realistic_shapes_stay_off_the_coverage_k
     assert all(f.endswith("/g32") for f in cov), sorted(cov)
 
 
+def _mx_args(M, N, K, in_dt, nbits, c_mode):
+    """A block-scaled layer (e8m0 scale per 32 k, K-contiguous weights) as GemLiteLinear.pack() lays it out; never dereferenced."""
+    a = _args(M=M, N=N, K=K, nbits=nbits, gs=32, in_dt=in_dt, w_mode=0, c_mode=c_mode, e=1 if nbits == 8 else 2)
+    a.w_pack_bits, a.w_dtype = (0, 3) if nbits == 8 else (8, 5)
+    a.output_dtype, a.meta_dtype = 2, 5
+    a.stride_xm = K // 2 if in_dt == 17 else K
+    a.stride_wk, a.stride_wn = 1, K if nbits == 8 else K // 2
+    a.stride_sx_m = K // 32
+    a.scales_x = 0x1000
+    return a
+
+
+@pytest.mark.parametrize("fam", ["a16w4", "a16w2", "a8w8i", "a8w8f", "a16w8", "mxfp8", "mxfp4"])
+def test_flag_bits_outside_the_public_mask_are_ignored(fam):
+    """tuning[3] bits outside GEMLITE_TF_PUBLIC_MASK (0x0FFFDFFF; 28 .. 31 are the planner's own, e.g. its K-order bit 30) change nothing
+    the C ABI answers: status, kernel name and workspace size stay those of the same request without them."""
+    lib = _hip.load()
+    kw = {"a16w4": dict(), "a16w2": dict(nbits=2),
+          "a8w8i": dict(nbits=8, e=1, in_dt=4, w_mode=0, c_mode=3, out_dt=1, gs=4096),
+          "a8w8f": dict(nbits=8, e=1, in_dt=3, w_mode=0, c_mode=3, out_dt=2, gs=4096),
+          "a16w8": dict(nbits=8, e=1, in_dt=1, w_dtype=4, w_mode=2, gs=4096)}.get(fam)
+    for M in (1, 16, 256, 1024):
+        for t3 in (0, 1 << 16, 1 << 22):
+            answers = []
+            for extra in (0, 1 << 28, 1 << 30, -(1 << 31)):
+                tun = (0, 0, 0, t3 | extra)
+                if kw is None:
+                    a = _mx_args(M, 4096, 4096, 16 if fam == "mxfp8" else 17, 8 if fam == "mxfp8" else 4, 4)
+                    a.tuning[3] = tun[3]
+                else:
+                    a = _args(M=M, tuning=tun, **kw)
+                    if kw.get("c_mode", 0) in (2, 3):
+                        a.scales_x = 0x1000
+                st = lib.gemlite_hip_query(C.byref(a))
+                answers.append((st, lib.gemlite_hip_kernel_name(C.byref(a)), lib.gemlite_hip_workspace_bytes(C.byref(a))))
+            assert answers[0][0] == 0, (fam, M, t3, answers[0])
+            assert answers[1:] == answers[:1] * 3, (fam, M, t3, answers)
+
+
 def test_workspace_sizing_cfgA():
     lib = _hip.load()
     a = _args(M=1)
