@@ -553,7 +553,15 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
                                    (a.M > 32 || (a.M > 16 && a.K >= 2048 && a.N / 16 > gl::resident_block_limit()));
             const bool only_here = (p.gs_shift == 5 && !g32_tiles) || a.N % 64 != 0;
             const bool in_budget = a.W_nbits == 4 ? rows5_pays(a.M, a.N, a.K, p.gs_shift) : rows5_pays_w2(a.M, a.N, a.K, p.gs_shift);
-            if (a.tuning[0] == 9 || only_here || (in_budget && !g32_tiles)) {
+            // the group-32 tiles take the layer only if their planner accepts this request (an output or x alignment it declines would
+            // otherwise drop the layer to the streaming kernel, 5 - 7 x behind the rows kernel): ask it first, keep the rows kernel if not
+            bool tiles_take = false;
+            if (g32_tiles) {
+                WnParams pt = p;
+                LaunchPlan lt{};
+                tiles_take = plan_gemm_wn_mma(a, pt, lt);
+            }
+            if (a.tuning[0] == 9 || only_here || (in_budget && !g32_tiles) || (g32_tiles && !tiles_take)) {
                 WnParams pr = p;
                 LaunchPlan lr{};
                 if (plan_gemm_wn_rows(a, pr, lr)) { r.kind = K_STREAM_WN; r.wn = pr; r.lp = lr; return; }
@@ -678,7 +686,7 @@ coverage:
     // M = 1 of a dynamically quantised layer with the activation quantisation fused into the prologue
     if (wants_fused_quant(&a)) {
         if (a.stride_wk != 1 || a.stride_xk != 1 || a.K % 16 != 0 || a.stride_wn % 16 != 0 || a.K > 65536 ||
-            (((uintptr_t)a.w_q | (uintptr_t)a.x) % 16) != 0) { r.status = GEMLITE_ERR_UNSUPPORTED; return; }
+            (((uintptr_t)a.w_q | (uintptr_t)a.x) % 16) != 0) { r.status = GEMLITE_ERR_NO_FUSED_QUANT; return; }
         r.kind = K_KMAJOR;
         // round 4: one wave per column with the whole weight row requested BEFORE the block quantises x (a8w8_decode_kernel);
         // tuning[0] = 7 keeps the round-2 kernel, which quantises first

@@ -209,6 +209,11 @@ bool plan_gemm_wn_mma_mx(const gemlite_hip_forward_args& a, WnParams& p, LaunchP
     return true;
 }
 
+// The WL forms (packed words global -> LDS in 16-byte DMA pieces) need w_q and its packed-row stride 16-byte aligned
+static bool w_dma_aligned(const gemlite_hip_forward_args& a) {
+    return ((uintptr_t)a.w_q % 16) == 0 && (a.stride_wk * 4) % 16 == 0;
+}
+
 bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp) {
     const int nbits = a.W_nbits;
     if (nbits != 4 && nbits != 2 && nbits != 1 && nbits != 8) return false;
@@ -331,7 +336,8 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
         const bool f16 = tag_dt == GEMLITE_DT_FP16;
         // round 6: the 64 x 64 tiles fetch their packed words through LDS (one DMA request per wave and step instead of four register loads per
         // lane: cfgA M = 256 16.5 -> see profiles/r06/probe_mma_wl.log); GEMLITE_TF_WORDS_AS_REGISTER_LOADS keeps the round-5 register path (A/B runs)
-        const bool wl = v == 0 && x16 && nbits == 4 && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
+        // (the DMA pieces are 16 bytes of the packed rows: a w_q or a row stride that is not 16-byte aligned takes the register path)
+        const bool wl = v == 0 && x16 && nbits == 4 && w_dma_aligned(a) && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
         const void* fn = f16 ? mma_lookup_f16(6, nbits, wl ? 4 : v, xdt) : mma_lookup_bf16(6, nbits, wl ? 4 : v, xdt);
         if (!fn) return false;
         p.splitk = splitk;
@@ -471,7 +477,7 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
                      xdt == 0 && (nbits == 4 || nbits == 2) && tiles * splitk <= resident_block_limit();
     if (use_xch) fn = f16 ? mma_lookup_f16(4, nbits, mi, 0) : mma_lookup_bf16(4, nbits, mi, 0);
     // round 6: the 128 x 128 tiles of 4-bit words under 16-bit activations fetch their packed words through LDS as well (slab + ticket combine)
-    const bool wl128 = !wide && !use_xch && mi == 4 && x16 && nbits == 4 && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
+    const bool wl128 = !wide && !use_xch && mi == 4 && x16 && nbits == 4 && w_dma_aligned(a) && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
     if (wl128) fn = f16 ? mma_lookup_f16(7, nbits, mi, 0) : mma_lookup_bf16(7, nbits, mi, 0);
     if (!fn) return false;
     p.splitk = splitk;

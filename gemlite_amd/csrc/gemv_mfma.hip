@@ -282,20 +282,23 @@ __global__ __launch_bounds__(NW * 64, 1) void gemv_mfma_kernel(const WnParams p)
                         acc[j][ai] = mfma16<Tag>(af, bf, first ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[j][ai]);
                     }
                 }
-            const float live = i0 + gi < my_units ? 1.f : 0.f;
+            // a unit past the wave's end re-read real weights but x from past the row's end (the next row, or whatever lies between
+            // rows of a strided x: NaN * 0 is NaN), so it is left out by a select, not cancelled by a multiply
+            const bool live = i0 + gi < my_units;
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const float s = need_s ? TR::to_float(gmf::meta_of<V>(b.s[gi], j)) : 1.f;
                 const float z = need_z ? TR::to_float(gmf::meta_of<V>(b.z[gi], j)) : scalar_zero;
-                const float a = s * QSCALE * live;
-                const float bb = (bz * z * (b_times_s ? s : 1.f) - s * OFF) * live;
+                const float a = s * QSCALE;
+                const float bb = bz * z * (b_times_s ? s : 1.f) - s * OFF;
                 // C layout: rows 4 kg + r — the tile's rows (< MB <= 4) live in the registers of the kg = 0 lanes
 #pragma unroll
                 for (int r = 0; r < MB; ++r) {
                     float v = acc[j][0][r];
 #pragma unroll
                     for (int ai = 1; ai < NACC; ++ai) v = __builtin_fmaf(acc[j][ai][r], PL::inv_scale(ai), v);
-                    tot[j][r] += a * v + bb * gs[r][gi];
+                    const float t = tot[j][r] + (a * v + bb * gs[r][gi]);
+                    tot[j][r] = live ? t : tot[j][r];
                 }
             }
         }
