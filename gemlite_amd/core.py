@@ -340,15 +340,17 @@ def _hip_matmul(x: Tensor, W_q: Tensor, scales: Tensor, zeros: Tensor, scales_x:
     if rc != 0:
         _hip.raise_for_status(rc, "gemlite_hip_forward")
     # a shape that only the coverage kernel takes is correct but orders of magnitude slower: say so, once per shape
-    wkey = (a.N, a.K, a.W_nbits, a.group_size, a.input_dtype, a.output_dtype, get_closest_m(M), matmul_type)
+    wkey = (a.N, a.K, a.W_nbits, a.group_size, a.w_pack_bits, a.input_dtype, a.output_dtype, get_closest_m(M), matmul_type)
     if wkey not in _COVERAGE_CHECKED:
         _COVERAGE_CHECKED.add(wkey)
         name = lib.gemlite_hip_kernel_name(_hip.C.byref(a))
         if name and name.startswith((b"generic_matmul_kernel", b"mx_generic_kernel")):
             logger.warning(f"gemlite_amd: no specialised MI355X kernel for N={a.N} K={a.K} W_nbits={a.W_nbits} "
-                           f"group_size={a.group_size} input_dtype={DType(a.input_dtype).name} M={M}: running on the coverage "
+                           f"group_size={a.group_size} packing_bitwidth={a.w_pack_bits} input_dtype={DType(a.input_dtype).name} M={M}: running on the coverage "
                            "kernel (correct, slow).  Group sizes that are a multiple of 32 (K % 256 == 0 for odd multiples) and N % 64 == 0 avoid it; block-scaled "
-                           "layers need a K-contiguous W_q (as pack() lays it out), N % 128 == 0 and K % 128 == 0.")
+                           "layers need a K-contiguous W_q (as pack() lays it out), N % 128 == 0 and K % 128 == 0.  8- and 16-bit packing needs 16-bit "
+                           "activations, a 4-byte aligned W_q and a power-of-two group size of at least 64 at M >= 2; 32-bit packing "
+                           "(set_packing_bitwidth(32)) has the most kernels.")
     return out
 
 

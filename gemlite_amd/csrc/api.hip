@@ -10,6 +10,9 @@
 #include <string.h>
 
 #include <atomic>
+#include <mutex>
+#include <set>
+#include <string>
 
 #include "gl_common.h"
 #include "gl_coopquant.h"
@@ -57,6 +60,18 @@ const void* unpack_kernel_fn();
 }  // namespace gl
 
 using namespace gl;
+
+// kernel label of a form for 8- / 16-bit packed words: the 32-bit label with ",b8" / ",b16" before the closing '>' (interned: labels are C strings
+// that live as long as the library)
+const char* gl::pw_label(const char* name, int pack_bits) {
+    if (pack_bits == 32) return name;
+    static std::mutex mu;
+    static std::set<std::string>* names = new std::set<std::string>();
+    std::string s(name);
+    s.insert(s.size() - 1, pack_bits == 8 ? ",b8" : ",b16");
+    std::lock_guard<std::mutex> lock(mu);
+    return names->insert(s).first->c_str();
+}
 
 static thread_local int tl_last_hip_error = 0;
 static thread_local void* tl_evt_start = nullptr;
@@ -483,7 +498,9 @@ static void resolve(const gemlite_hip_forward_args& a, Resolved& r) {
     }
     // ---- specialised packed-weight kernels ---------------------------------------------------------
     const bool x8 = a.input_dtype == GEMLITE_DT_FP8E4 || a.input_dtype == GEMLITE_DT_INT8;  // A8Wn dynamic / BitNet int8
-    if (packed && a.w_pack_bits == 32 && (x16 || x8) && a.stride_wn == 1 && a.stride_xk == 1 && a.stride_on == 1 &&
+    // (8- / 16-bit packed words, round 7: every planner below declines the widths it has no word source for — only gemm_wn_mma.hip and
+    //  gemv_wn.hip take them — so the order of the calls cannot send them to an int32-only kernel; what none takes falls to the coverage kernel)
+    if (packed && (a.w_pack_bits == 32 || a.w_pack_bits == 16 || a.w_pack_bits == 8) && (x16 || x8) && a.stride_wn == 1 && a.stride_xk == 1 && a.stride_on == 1 &&
         (a.stride_meta_n == 1 || !per_group_meta) && (a.K % eff_group == 0)) {
         WnParams p{};
         p.x = a.x; p.w = (const uint32_t*)a.w_q; p.scales = a.scales; p.zeros = a.zeros;

@@ -350,6 +350,7 @@ static const void* dpick_bits(int nbits, int v, int mt, int spg, int nw) {
 // tuning[0]: 0 auto | 1, 2, 4 force the words-per-lane V (16 V columns per block)
 // tuning[1]: 0 auto | n force split-K n;  tuning[2]: 0 auto | 4 / 8 waves per block (8: one row tile, >= 32-column tiles, K slice of whole 8-wave pieces)
 bool plan_gemm_wn_direct(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp) {
+    if (a.w_pack_bits != 32) return false;  // int32 words only (8- / 16-bit words: gemm_wn_mma.hip, gemv_wn.hip)
     const int nbits = a.W_nbits;
     if (nbits != 2 && nbits != 4) return false;
     const int e = 32 / nbits;

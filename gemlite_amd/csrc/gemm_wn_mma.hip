@@ -9,6 +9,16 @@ bool k_rotation_pays(const gemlite_hip_forward_args& a, int64_t tile_bytes);  //
 
 const void* mma_lookup_f16(int kind, int nbits, int mi, int xdt);
 const void* mma_lookup_bf16(int kind, int nbits, int mi, int xdt);
+const void* mma_lookup_pw_f16_b8(int kind, int nbits, int mi);
+const void* mma_lookup_pw_f16_b16(int kind, int nbits, int mi);
+const void* mma_lookup_pw_bf16_b8(int kind, int nbits, int mi);
+const void* mma_lookup_pw_bf16_b16(int kind, int nbits, int mi);
+
+// 8- / 16-bit packed words (w_pack_bits 8 / 16, WBY = 1 / 2 in gemm_wn_mma_kernel.inc): the register-path forms (kind 0 / 1 / 4 / 6 variant 0)
+static const void* mma_lookup_pw(bool f16, int pack_bits, int kind, int nbits, int mi) {
+    if (f16) return pack_bits == 8 ? mma_lookup_pw_f16_b8(kind, nbits, mi) : mma_lookup_pw_f16_b16(kind, nbits, mi);
+    return pack_bits == 8 ? mma_lookup_pw_bf16_b8(kind, nbits, mi) : mma_lookup_pw_bf16_b16(kind, nbits, mi);
+}
 
 // When the narrow 64 x 64 tiles (KH = 4, 256-k steps) are the default: 0 = never, 1 = K unsplit, 2 = two K slices.  From sweeps over 20 LLM
 // layer shapes x M = 40 .. 256 for 4-bit words under 16-bit activations (profiles/r04/probe_mma_narrow_llm_shapes.log, ..._m40_m64.log) and
@@ -217,8 +227,15 @@ static bool w_dma_aligned(const gemlite_hip_forward_args& a) {
 bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp) {
     const int nbits = a.W_nbits;
     if (nbits != 4 && nbits != 2 && nbits != 1 && nbits != 8) return false;
-    const int e = 32 / nbits;
+    const int e = 32 / nbits;  // (elements per word of the 32-bit layout: 8- / 16-bit words are read as the int32 words they concatenate to)
     if (a.N % 64 != 0) return false;  // (128 for everything but the narrow tiles: checked behind them)
+    // 8- / 16-bit packed words: 16-bit activations, the register-path forms; every lane's dword load needs w_q and the row stride 4-byte aligned
+    const int pb = a.w_pack_bits;
+    if (pb != 32 && pb != 16 && pb != 8) return false;
+    const bool pw = pb != 32;
+    if (pw && ((a.input_dtype != GEMLITE_DT_FP16 && a.input_dtype != GEMLITE_DT_BF16) || (nbits == 8 && pb != 16) || ((uintptr_t)a.w_q % 4) != 0 ||
+               (a.stride_wk * (pb / 8)) % 4 != 0 || a.stride_wk < a.N))
+        return false;
     // Activation type: the 16-bit float of the kernel's Tag, or 8 bits (fp8 e4m3 / int8: A8Wn dynamic, BitNet int8) with a
     // 16-bit output.  Tag = the type of the metadata read in the K loop = the output type (any of fp16 / bf16 / fp32 output
     // and fp32 channel scales go through the untyped epilogue store).
@@ -244,6 +261,7 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
         // What reaches this: 1- and 8-bit packed words and fp8 activations x 4- / 2-bit words at M >= 2 (4- / 2-bit words under 16-bit activations
         // have the rows kernel in front) — shapes that ran on the coverage kernel until round 5 (4096^2 M = 64: ~3.8 ms).
         if (p.group_size % 32 != 0 || a.K % 256 != 0 || a.N % mma::BN != 0 || xdt == GEMLITE_DT_INT8) return false;  // (odd multiples of 32 above 32: gs_magic, api.hip)
+        if (pw) return false;  // (no 8- / 16-bit word form of these tiles: the coverage kernel)
         if (a.tuning[0] != 0 || a.tuning[2] != 0) return false;
         const int rows = (int)(a.K / e), units = (int)(a.K / 256);
         const int64_t tiles = (int64_t)(a.N / mma::BN) * ((a.M + 31) / 32);
@@ -325,7 +343,7 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
     if (narrow_v >= 0) {
         static const int V_MI[4] = {2, 2, 4, 4}, V_KS[4] = {256, 512, 256, 256}, V_NST[4] = {3, 2, 2, 2};
         const int v = narrow_v, vmi = V_MI[v], ks = V_KS[v], bm = 32 * vmi;
-        if ((!x16 && v != 0) || (nbits != 4 && nbits != 2) || a.N % 64 != 0 || a.K % ks != 0) return false;  // (8-bit activations: variant 0 only)
+        if ((!x16 && v != 0) || (pw && v != 0) || (nbits != 4 && nbits != 2) || a.N % 64 != 0 || a.K % ks != 0) return false;  // (8-bit activations, 8- / 16-bit words: variant 0 only)
         const int rows = (int)(a.K / e), units = (int)(a.K / ks);
         const int splitk = narrow_sk;
         if (splitk > units) return false;
@@ -337,15 +355,15 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
         // round 6: the 64 x 64 tiles fetch their packed words through LDS (one DMA request per wave and step instead of four register loads per
         // lane: cfgA M = 256 16.5 -> see profiles/r06/probe_mma_wl.log); GEMLITE_TF_WORDS_AS_REGISTER_LOADS keeps the round-5 register path (A/B runs)
         // (the DMA pieces are 16 bytes of the packed rows: a w_q or a row stride that is not 16-byte aligned takes the register path)
-        const bool wl = v == 0 && x16 && nbits == 4 && w_dma_aligned(a) && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
-        const void* fn = f16 ? mma_lookup_f16(6, nbits, wl ? 4 : v, xdt) : mma_lookup_bf16(6, nbits, wl ? 4 : v, xdt);
+        const bool wl = v == 0 && x16 && nbits == 4 && !pw && w_dma_aligned(a) && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
+        const void* fn = pw ? mma_lookup_pw(f16, pb, 6, nbits, v) : (f16 ? mma_lookup_f16(6, nbits, wl ? 4 : v, xdt) : mma_lookup_bf16(6, nbits, wl ? 4 : v, xdt));
         if (!fn) return false;
         p.splitk = splitk;
         p.rows_per_slice = rows;
         p.combine = 0;
         lp.fn = fn;
         static const char* nn[2][2] = {{"gemm_w4_mma_kernel<64x64>", "gemm_w4_mma_kernel<128x64>"}, {"gemm_w2_mma_kernel<64x64>", "gemm_w2_mma_kernel<128x64>"}};
-        lp.name = xdt ? (nbits == 4 ? "gemm_a8w4_mma_kernel<64x64>" : "gemm_a8w2_mma_kernel<64x64>") : nn[nbits == 4 ? 0 : 1][vmi == 2 ? 0 : 1];
+        lp.name = pw_label(xdt ? (nbits == 4 ? "gemm_a8w4_mma_kernel<64x64>" : "gemm_a8w2_mma_kernel<64x64>") : nn[nbits == 4 ? 0 : 1][vmi == 2 ? 0 : 1], pb);
         lp.grid = dim3((unsigned)tiles, splitk, 1);
         lp.block = dim3(512, 1, 1);
         const size_t stages = (size_t)V_NST[v] * (bm * ks * (x16 ? 2 : 1) + (wl ? 8192 : 0));
@@ -465,7 +483,7 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
     if (splitk > 1 && tiles > MAX_SPLITK_COUNTERS) return false;
     if ((uint64_t)splitk * bm * bn * 4 >= (1ull << 31)) return false;  // slab buffer descriptor range
     const bool f16 = tag_dt == GEMLITE_DT_FP16;
-    const void* fn = f16 ? mma_lookup_f16(wide ? 1 : 0, nbits, mi, xdt) : mma_lookup_bf16(wide ? 1 : 0, nbits, mi, xdt);
+    const void* fn = pw ? mma_lookup_pw(f16, pb, wide ? 1 : 0, nbits, mi) : (f16 ? mma_lookup_f16(wide ? 1 : 0, nbits, mi, xdt) : mma_lookup_bf16(wide ? 1 : 0, nbits, mi, xdt));
     // K-slice combine: reduce-scatter between the slices of a tile when they are certain to be co-resident (every block of the
     // launch fits on the device at once: <= one block per CU), the slices divide the tile's row blocks, and the variant exists
     // (4- / 2-bit words, 16-bit activations); else slabs + ticket.  From 4 slices on: with 2 slices the ticket protocol is as fast
@@ -475,9 +493,9 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
     const bool use_xch = !wide && splitk > 1 && (splitk & (splitk - 1)) == 0 && mi >= 2 && splitk <= mi && !(caller_flags(a) & GEMLITE_TF_COMBINE_TICKET) &&
                      (splitk >= 4 || (caller_flags(a) & (GEMLITE_TF_COMBINE_REDUCE_SCATTER_2 | GEMLITE_TF_COMBINE_HANDOVER_TEST))) &&
                      xdt == 0 && (nbits == 4 || nbits == 2) && tiles * splitk <= resident_block_limit();
-    if (use_xch) fn = f16 ? mma_lookup_f16(4, nbits, mi, 0) : mma_lookup_bf16(4, nbits, mi, 0);
+    if (use_xch) fn = pw ? mma_lookup_pw(f16, pb, 4, nbits, mi) : (f16 ? mma_lookup_f16(4, nbits, mi, 0) : mma_lookup_bf16(4, nbits, mi, 0));
     // round 6: the 128 x 128 tiles of 4-bit words under 16-bit activations fetch their packed words through LDS as well (slab + ticket combine)
-    const bool wl128 = !wide && !use_xch && mi == 4 && x16 && nbits == 4 && w_dma_aligned(a) && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
+    const bool wl128 = !wide && !use_xch && mi == 4 && x16 && nbits == 4 && !pw && w_dma_aligned(a) && !(caller_flags(a) & GEMLITE_TF_WORDS_AS_REGISTER_LOADS);
     if (wl128) fn = f16 ? mma_lookup_f16(7, nbits, mi, 0) : mma_lookup_bf16(7, nbits, mi, 0);
     if (!fn) return false;
     p.splitk = splitk;
@@ -497,6 +515,7 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
     static const char* names_wide[2][2] = {{"gemm_w4_mma_kernel<128x256>", "gemm_w4_mma_kernel<256x256>"},
                                            {"gemm_w2_mma_kernel<128x256>", "gemm_w2_mma_kernel<256x256>"}};
     if (wide) lp.name = names_wide[nbits == 4 ? 0 : 1][mi == 8 ? 1 : 0];
+    lp.name = pw_label(lp.name, pb);
     lp.grid = dim3((unsigned)tiles, splitk, 1);
     lp.block = dim3(512, 1, 1);
     const int nst = mi == 8 ? 2 : (mi == 4 ? 3 : (nbits == 8 ? 2 : (mi == 2 ? 3 : 4)));  // LDS stages of x (mma_pick_mi)

@@ -335,6 +335,43 @@ struct ConvertX<Tag, GEMLITE_DT_INT8> {  // integer codes minus an integer zero 
 // (in a __device__ function: a "v" constraint inside a lambda of the kernel body silently drops the kernel's host stub)
 __device__ __forceinline__ void opaque2(uint32_t& a, uint32_t& b) { asm volatile("" : "+v"(a), "+v"(b)); }
 
+// 8- / 16-bit packed words (WB = 1 / 2 bytes per word).  The little-endian concatenation of byte rows 4R .. 4R+3 (short rows 2R, 2R+1)
+// of a column IS that column's int32 word of packed row R (bitpack.py: element i of a word sits at bits [b i, b i + b)), so only the
+// word source differs from WB = 4.  Lanes 4c .. 4c+3 own 4 adjacent columns: lane 4c + q loads byte row 4R + q of the quad's 4 columns
+// (WB = 2: short row 2R + (q & 1), column pair q >> 1) as one dword, and a transpose across the quad — DPP quad_perm + v_perm, selectors
+// per lane from quad_sel() — hands every lane its own column's word.  EXEC is all ones wherever this runs.
+template <int WB>
+__device__ __forceinline__ uint32_t quad_word(uint32_t v, uint32_t sel1, uint32_t sel2) {
+    if constexpr (WB == 1) {
+        const uint32_t t = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);  // quad_perm(2, 3, 0, 1)
+        const uint32_t y = __builtin_amdgcn_perm(t, v, sel1);  // q < 2: columns 0, 1 of rows q, q + 2; q >= 2: columns 2, 3 of rows q - 2, q
+        const uint32_t u = (uint32_t)__builtin_amdgcn_mov_dpp((int)y, 0xB1, 0xF, 0xF, false);  // quad_perm(1, 0, 3, 2)
+        return __builtin_amdgcn_perm(u, y, sel2);
+    } else if constexpr (WB == 2) {
+        const uint32_t t = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
+        return __builtin_amdgcn_perm(t, v, sel1);
+    } else {
+        return v;
+    }
+}
+template <int WB>
+__device__ __forceinline__ void quad_sel(int q, uint32_t& sel1, uint32_t& sel2) {
+    sel1 = WB == 1 ? (q < 2 ? 0x05040100u : 0x03020706u) : ((q & 1) ? 0x03020706u : 0x05040100u);
+    sel2 = (q & 1) ? 0x03070105u : 0x06020400u;
+}
+// byte offset of lane q's dword inside packed row R of the quad at column c4 (a multiple of 4), with sw = the row stride in words
+template <int WB>
+__device__ __forceinline__ uint32_t quad_offset(int q, int c4, int sw) {
+    if constexpr (WB == 1) return (uint32_t)(q * sw + c4);
+    else if constexpr (WB == 2) return (uint32_t)((q & 1) * 2 * sw + c4 * 2 + (q >> 1) * 4);
+    else return (uint32_t)(c4 + q) * 4u;
+}
+// the packed words slice u of a 64-k sub-block reads (Extract<NBITS>)
+template <int NBITS>
+__device__ __forceinline__ constexpr bool word_in_slice(int i, int u) {
+    return NBITS == 4 ? i == u : (NBITS == 2 ? i == (u >> 1) : (NBITS == 1 ? i == 0 : (i >> 1) == u));
+}
+
 // One LDS-DMA piece: 64 lanes x 16 bytes from buffer offset (voff per lane + soff) to LDS [dst, dst + 1024), lane-linear.
 // (A __device__ function: the address-space cast inside a kernel-body lambda silently drops the kernel's host stub.)
 __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* dst, uint32_t voff, uint32_t soff) {
@@ -369,7 +406,9 @@ __device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, unsigned ch
 // 8 k at k_of(u, h): its group inside the sub-block is k_of(u, h) / 32, which for 1-bit words depends on the lane half h (a per-lane select).
 // 32-row tiles only (any M through the grid): it is what takes 1- / 2- / 8-bit words and 8-bit activations with groups of 32 off the
 // coverage kernel at M >= 2 (VERDICT r5 #8); 4- / 2-bit words under 16-bit activations have the rows kernel up to 64 rows per block.
-template <typename Tag, int NBITS, int MI, int KSTEP, int RD, int NST, int EXP = 0, int XDT = 0, int KH = 2, int XCH = 0, int WL = 0, int NGS = 1>
+// WBY = 1 / 2: 8- / 16-bit packed words ([K / e8, N] uint8, [K / e16, N] int16) on the register path: the same requests (one dword per lane and
+// word, voffset from quad_offset()), the words regrouped across the quad (quad_word()) where a slice is dequantised; everything else as WBY = 4.
+template <typename Tag, int NBITS, int MI, int KSTEP, int RD, int NST, int EXP = 0, int XDT = 0, int KH = 2, int XCH = 0, int WL = 0, int NGS = 1, int WBY = 4>
 __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
     using namespace mma;
     using TR = F16Traits<Tag>;  // output / metadata type; also the activation type when XDT == 0
@@ -386,6 +425,8 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
     constexpr bool MXW = NBITS == MXW8 || NBITS == MXW4 || NVW || NOSC;  // K-contiguous weights (16-bit activations only)
     static_assert(!MXW || XDT == 0, "block-scaled weights on this kernel: 16-bit activations");
     static_assert(NGS == 1 || (NGS == 2 && !MXW && !WL && MI == 1), "groups of 32: packed integer words, 32-row tiles");
+    static_assert(WBY == 4 || ((WBY == 1 || WBY == 2) && !MXW && !WL && NGS == 1 && XDT == 0 && (NBITS != 8 || WBY == 2)),
+                  "8- / 16-bit packed words: register path, 16-bit activations");
     constexpr int PITCH = KSTEP * ES, XSTAGE = BM * PITCH;  // bytes per row / per stage of x
     constexpr int WTILE = WL ? (KSTEP / G::E) * BN * 4 : 0;  // WL: the step's packed words [KSTEP / E rows][BN columns] behind the x tile
     constexpr int STAGE = XSTAGE + WTILE;
@@ -499,7 +540,8 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
         brS = make_srd(p.scales, (uint32_t)((int64_t)(p.K / SBK - 1) * p.stride_meta_g + (int64_t)(p.N - 1) * p.stride_meta_n + 1));
         brZ = brS;
     } else {
-        wvoff = (uint32_t)(G::HS * h * sw + n) * 4u;
+        // (WBY < 4: bytes per packed row of the 32-bit layout = 4 sw whatever the word width, so every per-step / per-row offset below is the same)
+        wvoff = (uint32_t)(G::HS * h * sw) * 4u + quad_offset<WBY>(lane & 3, n & ~3, sw);
         mvoff = (uint32_t)n * 2u;
         brW = make_srd((const void*)(p.w + (int64_t)row_s0 * sw), (uint32_t)(nsteps * STEP_ROWS * sw * 4));
         brS = make_srd(need_s ? p.scales : (const void*)p.w, (uint32_t)(need_s ? meta_bytes : 4));
@@ -642,6 +684,8 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
 
     ConvertX<Tag, XDT> cv;
     uint32_t ev = 0, od = 0;  // codes of the slice being dequantised
+    uint32_t qsel1 = 0, qsel2 = 0;  // WBY < 4: the quad transpose's byte selectors of this lane
+    if constexpr (WBY != 4) quad_sel<WBY>(lane & 3, qsel1, qsel2);
     // Dequantisation of one slice (-> 4 registers of a B fragment) is cut into pieces that hide behind the MI MFMAs of
     // the slice before it: piece 0 = (scale, zero) of the sub-block + code extraction, then the 4 pairs.
     float mx_sc = 0.f;  // block scale of the sub-block being dequantised (MX)
@@ -681,7 +725,14 @@ __global__ __launch_bounds__(512, 2) void gemm_wn_mma_kernel(const WnParams p) {
                         cv.set(sc, zr, u13, u4);
                     }
                 }
-                Extract<NBITS>::run(b.w[sb], u, ev, od);
+                if constexpr (WBY == 4) {
+                    Extract<NBITS>::run(b.w[sb], u, ev, od);
+                } else {  // the words this slice reads, regrouped across the quad (a 2-bit word feeds two slices, a 1-bit word four: regrouped each time)
+                    uint32_t wq[WPL];
+#pragma unroll
+                    for (int i = 0; i < WPL; ++i) wq[i] = word_in_slice<NBITS>(i, u) ? quad_word<WBY>(b.w[sb][i], qsel1, qsel2) : 0u;
+                    Extract<NBITS>::run(wq, u, ev, od);
+                }
                 cv.prep(ev, od);
                 // opaque to the optimiser: otherwise byte i becomes v_bfe_u32 + v_cvt_f32_ubyte0 instead of one v_cvt_f32_ubyte<i>
                 opaque2(ev, od);
@@ -1281,6 +1332,64 @@ static const void* mma_pick_wide(int nbits, int mi) {
     if (nbits == 4) f = mi == 8 ? gemm_wn_mma_kernel<Tag, 4, 8, 64, 4, 2, 0, 0, 1> : gemm_wn_mma_kernel<Tag, 4, 4, 64, 6, 3, 0, 0, 1>;
     else if (nbits == 2) f = mi == 8 ? gemm_wn_mma_kernel<Tag, 2, 8, 64, 4, 2, 0, 0, 1> : gemm_wn_mma_kernel<Tag, 2, 4, 64, 6, 3, 0, 0, 1>;
     return (const void*)f;
+}
+
+// 8- / 16-bit packed words (WB = 1 / 2) under 16-bit activations: the register-path forms of the 32-bit words with the same tile, ring and
+// stage parameters — kind 0 (nbits 4 / 2 / 1, and 8 in 16-bit words; mi), 1 wide tiles, 4 reduce-scatter combine (nbits 4 / 2; mi), 6 narrow
+// tiles variant 0 (nbits 4 / 2).  Compiled in gemm_wn_mma_pw_{f16,bf16}_b{8,16}.hip, one translation unit per (Tag, WB).
+template <typename Tag, int NBITS, int WB>
+static const void* mma_pick_mi_pw(int mi) {
+    mma_kernel_fn f = nullptr;
+    constexpr int W8 = mma::Geo<NBITS>::WPL == 8;
+    switch (mi) {
+        case 8: f = gemm_wn_mma_kernel<Tag, NBITS, 8, 128, 4, 2, 0, 0, 2, 0, 0, 1, WB>; break;
+        case 4: f = gemm_wn_mma_kernel<Tag, NBITS, 4, 128, 6, 3, 0, 0, 2, 0, 0, 1, WB>; break;
+        case 2: f = gemm_wn_mma_kernel<Tag, NBITS, 2, 256, 6, (W8 ? 2 : 3), 0, 0, 2, 0, 0, 1, WB>; break;
+        case 1: f = gemm_wn_mma_kernel<Tag, NBITS, 1, 256, (W8 ? 6 : 8), (W8 ? 2 : 4), 0, 0, 2, 0, 0, 1, WB>; break;
+        default: break;
+    }
+    return (const void*)f;
+}
+template <typename Tag, int NBITS, int WB>
+static const void* mma_pick_xch_pw(int mi) {
+    mma_kernel_fn f = nullptr;
+    switch (mi) {
+        case 8: f = gemm_wn_mma_kernel<Tag, NBITS, 8, 128, 4, 2, 0, 0, 2, 1, 0, 1, WB>; break;
+        case 4: f = gemm_wn_mma_kernel<Tag, NBITS, 4, 128, 6, 3, 0, 0, 2, 1, 0, 1, WB>; break;
+        case 2: f = gemm_wn_mma_kernel<Tag, NBITS, 2, 256, 6, 3, 0, 0, 2, 1, 0, 1, WB>; break;
+        default: break;
+    }
+    return (const void*)f;
+}
+template <typename Tag, int NBITS, int WB>
+static const void* mma_pick_wide_pw(int mi) {
+    mma_kernel_fn f = mi == 8 ? gemm_wn_mma_kernel<Tag, NBITS, 8, 64, 4, 2, 0, 0, 1, 0, 0, 1, WB> : gemm_wn_mma_kernel<Tag, NBITS, 4, 64, 6, 3, 0, 0, 1, 0, 0, 1, WB>;
+    return (const void*)f;
+}
+template <typename Tag, int WB>
+static const void* mma_lookup_pw(int kind, int nbits, int mi) {
+    switch (kind) {
+        case 0:
+            switch (nbits) {
+                case 4: return mma_pick_mi_pw<Tag, 4, WB>(mi);
+                case 2: return mma_pick_mi_pw<Tag, 2, WB>(mi);
+                case 1: return mma_pick_mi_pw<Tag, 1, WB>(mi);
+                case 8:
+                    if constexpr (WB == 2) return mma_pick_mi_pw<Tag, 8, WB>(mi);
+                    else return nullptr;
+                default: return nullptr;
+            }
+        case 1:
+            if (mi != 4 && mi != 8) return nullptr;
+            return nbits == 4 ? mma_pick_wide_pw<Tag, 4, WB>(mi) : (nbits == 2 ? mma_pick_wide_pw<Tag, 2, WB>(mi) : nullptr);
+        case 4: return nbits == 4 ? mma_pick_xch_pw<Tag, 4, WB>(mi) : (nbits == 2 ? mma_pick_xch_pw<Tag, 2, WB>(mi) : nullptr);
+        case 6:  // mi = variant: 0 only
+            if (mi != 0) return nullptr;
+            if (nbits == 4) return (const void*)(mma_kernel_fn)gemm_wn_mma_kernel<Tag, 4, 2, 256, 6, 3, 0, 0, 4, 0, 0, 1, WB>;
+            if (nbits == 2) return (const void*)(mma_kernel_fn)gemm_wn_mma_kernel<Tag, 2, 2, 256, 6, 3, 0, 0, 4, 0, 0, 1, WB>;
+            return nullptr;
+        default: return nullptr;
+    }
 }
 
 // One entry point per Tag (each lives in its own translation unit: gemm_wn_mma_f16.hip / gemm_wn_mma_bf16.hip compile the

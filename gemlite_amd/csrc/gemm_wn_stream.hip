@@ -405,6 +405,7 @@ static const void* pick_bits_s(int nbits, int mt, int spg) {
 
 // tuning[1]: 0 auto | n force split-K n
 bool plan_gemm_wn_stream(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp) {
+    if (a.w_pack_bits != 32) return false;  // int32 words only (8- / 16-bit words: gemm_wn_mma.hip, gemv_wn.hip)
     const int nbits = a.W_nbits;
     if (nbits != 1 && nbits != 2 && nbits != 4) return false;
     const int e = 32 / nbits;

@@ -603,6 +603,7 @@ __global__ __launch_bounds__(256, (MI <= 4 ? 2 : 1)) void gemm_w4_pipe_kernel(co
 
 // tuning[1]: 0 auto | n force split-K n
 bool plan_gemm_wn_tiled(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp) {
+    if (a.w_pack_bits != 32) return false;  // int32 words only (8- / 16-bit words: gemm_wn_mma.hip, gemv_wn.hip)
     if (a.W_nbits != 4) return false;  // 2-/1-bit words span more than one MFMA fragment: streaming kernel
     if (a.N % TBN != 0 || a.K % TBK != 0) return false;
     if (a.output_dtype != a.input_dtype) return false;

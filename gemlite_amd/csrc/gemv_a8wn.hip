@@ -286,6 +286,7 @@ static const void* a8wn_pick(int nbits, int xdt, int mb) {
 
 // fq: `a` describes the call AS THE MATMUL SEES IT (8-bit input dtype, placeholder x / scales_x); the launch gets the raw 16-bit row
 bool plan_gemv_a8wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp, bool fq) {
+    if (a.w_pack_bits != 32) return false;  // int32 words only (8- / 16-bit words: gemm_wn_mma.hip, gemv_wn.hip)
     if (fq && (a.M != 1 || a.K > 61440 || a.K % 8 != 0)) return false;
     const int nbits = a.W_nbits;
     if (nbits != 4 && nbits != 2) return false;
@@ -470,6 +471,7 @@ __global__ __launch_bounds__(512) void a8wn_rows_kernel(const WnParams p) {
 
 // 2 <= M <= 64; the conditions of plan_gemv_a8wn plus whole chunks and the x re-read budget of the rows kernels
 bool plan_a8wn_rows(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp) {
+    if (a.w_pack_bits != 32) return false;  // int32 words only (8- / 16-bit words: gemm_wn_mma.hip, gemv_wn.hip)
     const int nbits = a.W_nbits;
     if (nbits != 4 && nbits != 2) return false;
     if (a.M < 2 || a.M > 64) return false;

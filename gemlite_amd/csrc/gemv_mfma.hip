@@ -385,6 +385,7 @@ static gmf_fn gmf_pick(int nbits, int v, int nw, int mb, int spg) {
 }
 
 bool plan_gemv_mfma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp) {
+    if (a.w_pack_bits != 32) return false;  // int32 words only (8- / 16-bit words: gemm_wn_mma.hip, gemv_wn.hip)
     if (a.W_nbits != 4 && a.W_nbits != 2) return false;
     if (a.M < 1 || a.M > 4) return false;
     if (a.output_dtype != a.input_dtype) return false;  // typed epilogue / metadata

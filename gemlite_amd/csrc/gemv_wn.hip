@@ -49,6 +49,9 @@ __device__ __forceinline__ void gld128(u32x4& d, const char* base, uint32_t voff
 __device__ __forceinline__ void gld64(u32x2& d, const char* base, uint32_t voff) {
     asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(d) : "v"(voff), "s"(base) : "memory");
 }
+__device__ __forceinline__ void gld32(uint32_t& d, const char* base, uint32_t voff) {
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(d) : "v"(voff), "s"(base) : "memory");
+}
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 template <typename T>
@@ -116,7 +119,12 @@ struct Window {
 // prologue from the critical path of short K slices (decode shapes such as 4096 x 4096).
 // NW = waves per block (4; 8 for the short-K direct-x variant: with one chunk per wave the only way to overlap the
 // unpack arithmetic of one part of K with the weight stream of another is a second wave on the same SIMD).
-template <typename Tag, int NBITS, int MB, int R, int CQ, bool XD = false, int NW = 4>
+// WBY = 1 / 2: 8- / 16-bit packed words ([K / e8, N] uint8, [K / e16, N] int16).  Byte rows 4r .. 4r+3 (short rows 2r, 2r+1) of a column,
+// concatenated little-endian, are that column's int32 word of packed row r, so a lane fetches its 4 columns of packed row r as 4 dwords
+// (2 dwordx2) — one per byte (short) row — and regroups them into the u32x4 of the 32-bit layout with v_perm (8 / 4 per row) behind the
+// wait; the arithmetic is the 32-bit kernel's.  Row segments of 64 columns are 64 / 128 bytes: the tiles that share a 128-byte line run
+// on one XCD (block b runs on XCD b % 8, each XCD has its own L2).
+template <typename Tag, int NBITS, int MB, int R, int CQ, bool XD = false, int NW = 4, int WBY = 4>
 __global__ __launch_bounds__(NW * 64, ((MB * (16 / NBITS) >= 32 || R * MB >= 32 || NW > 4) ? 1 : 2)) void gemv_wn_kernel(const WnParams p) {
     using TR = F16Traits<Tag>;
     using WN = Window<Tag, NBITS>;
@@ -139,6 +147,7 @@ __global__ __launch_bounds__(NW * 64, ((MB * (16 / NBITS) >= 32 || R * MB >= 32 
     constexpr int NT = NW * 64;           // threads per block
     static_assert(XD || R * E % 32 == 0, "a run of rows must cover whole 32-k spans of x");
     static_assert(!XD || (NBITS == 4 && MB == 1), "direct x loads: one 16-byte x chunk per packed row");
+    static_assert(WBY == 4 || ((WBY == 1 || WBY == 2) && !XD && NBITS <= 4), "8- / 16-bit packed words: x through LDS, asm requests");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -150,11 +159,19 @@ __global__ __launch_bounds__(NW * 64, ((MB * (16 / NBITS) >= 32 || R * MB >= 32 
     float scalar_zero = 0.f;
     if (p.zero_is_scalar) scalar_zero = (float)__builtin_amdgcn_readfirstlane(((const int32_t*)p.zeros)[0]);
     int tile = blockIdx.x;
-    if constexpr (CQ == 2) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
+    if constexpr (CQ == 2 && WBY == 4) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
         const int nb = gridDim.x;
         if ((nb & 15) == 0) {
             const int xcd = tile & 7, idx = tile >> 3;
             tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
+        }
+    }
+    if constexpr (WBY != 4 && 128 / ((4 << CQ) * WBY) >= 2) {  // the GT tiles of one 128-byte line of a byte / short row on one XCD (speed only)
+        constexpr int GT = 128 / ((4 << CQ) * WBY);
+        const int nb = gridDim.x;
+        if (nb % (8 * GT) == 0) {
+            const int xcd = tile & 7, idx = tile >> 3;
+            tile = ((idx / GT) * 8 + xcd) * GT + idx % GT;
         }
     }
     const int slice = blockIdx.y;
@@ -187,14 +204,15 @@ __global__ __launch_bounds__(NW * 64, ((MB * (16 / NBITS) >= 32 || R * MB >= 32 
     const uint32_t sw4 = (uint32_t)p.stride_wk * 4u;
     uint32_t wo[R];  // byte offset of this lane's R rows in chunk 0
 #pragma unroll
-    for (int i = 0; i < R; ++i) wo[i] = (uint32_t)(row_s0 + row_w0 + g * R + i) * sw4 + (uint32_t)n0 * 4u;
+    for (int i = 0; i < R; ++i) wo[i] = (uint32_t)(row_s0 + row_w0 + g * R + i) * sw4 + (uint32_t)n0 * (uint32_t)WBY;  // (bytes per packed row: 4 sw at any word width)
     const uint32_t xo = (uint32_t)(row_s0 + row_w0 + g * R) * (uint32_t)(E * 2);  // XD: byte offset of row 0's x chunk
     const int nch_slice = rows_slice / CHUNK;
     const int nchunks = (nch_slice - wave + NW - 1) / NW;  // may be 0 for the last waves of a short slice
-    struct Chunk { u32x4 w[R]; u32x2 s, z; u32x4 x[XD ? R : 1]; };
+    // WBY < 4: b8 / b16 are the requests' registers (byte rows 4r + t / short rows 2r + t of the lane's 4 columns), w is assembled from them
+    struct Chunk { u32x4 w[R]; u32x2 s, z; u32x4 x[XD ? R : 1]; uint32_t b8[WBY == 1 ? R : 1][4]; u32x2 b16[WBY == 2 ? R : 1][2]; };
     const uint16_t* xg = (const uint16_t*)p.x;
     const char* wb = (const char*)p.w;
-    constexpr int NLC = R + 2 + (XD ? R : 0);  // requests per chunk
+    constexpr int NLC = R * (4 / WBY) + 2 + (XD ? R : 0);  // requests per chunk
     // (8-bit words with 8 rows per lane: 32 weight registers per chunk buffer — with the asm requests the allocator spilled, and a spilled
     //  destination of a request in flight is a wrong result; that one variant keeps the compiler-tracked loads and pipeline2_run)
     constexpr bool ASMQ = !(NBITS == 8 && R == 8);
@@ -218,9 +236,23 @@ __global__ __launch_bounds__(NW * 64, ((MB * (16 / NBITS) >= 32 || R * MB >= 32 
             for (int i = 0; i < R; ++i) gvw::gld128<false>(ck.x[i], (const char*)xg, xc + (uint32_t)(i * E * 2));
         }
         const uint32_t co = (uint32_t)(chunk * CSTRIDE) * sw4;  // uniform
+        if constexpr (WBY == 1) {  // (a line is shared by the tiles of one XCD: default-policy loads)
+            const uint32_t sw1 = (uint32_t)p.stride_wk;
 #pragma unroll
-        for (int i = 0; i < R; ++i)  // streamed once by one CU: non-temporal (guide row nt-weights; strip reads 23.6 -> 20.7 us at 16384^2 with R = 8)
-            gvw::gld128<(GL_GEMV_NT != 0)>(ck.w[i], wb, wo[i] + co);
+            for (int i = 0; i < R; ++i)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) gvw::gld32(ck.b8[i][t], wb, wo[i] + co + (uint32_t)t * sw1);
+        } else if constexpr (WBY == 2) {
+            const uint32_t sw2 = (uint32_t)p.stride_wk * 2u;
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) gvw::gld64(ck.b16[i][t], wb, wo[i] + co + (uint32_t)t * sw2);
+        } else {
+#pragma unroll
+            for (int i = 0; i < R; ++i)  // streamed once by one CU: non-temporal (guide row nt-weights; strip reads 23.6 -> 20.7 us at 16384^2 with R = 8)
+                gvw::gld128<(GL_GEMV_NT != 0)>(ck.w[i], wb, wo[i] + co);
+        }
         gvw::gld64(ck.s, (const char*)sp, mo);
         gvw::gld64(ck.z, (const char*)zp, mo);
     };
@@ -229,8 +261,32 @@ __global__ __launch_bounds__(NW * 64, ((MB * (16 / NBITS) >= 32 || R * MB >= 32 
 #pragma unroll
             for (int i = 0; i < R; ++i) gvw::tie(ck.x[i]);
         }
+        if constexpr (WBY == 1) {
 #pragma unroll
-        for (int i = 0; i < R; ++i) gvw::tie(ck.w[i]);
+            for (int i = 0; i < R; ++i) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) gvw::tie(ck.b8[i][t]);
+                // 4 x 4 byte transpose: word j = byte j of byte rows 0 .. 3
+                const uint32_t* d = ck.b8[i];
+                const uint32_t lo01 = __builtin_amdgcn_perm(d[1], d[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(d[1], d[0], 0x07030602u);
+                const uint32_t lo23 = __builtin_amdgcn_perm(d[3], d[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(d[3], d[2], 0x07030602u);
+                ck.w[i] = (u32x4){__builtin_amdgcn_perm(lo23, lo01, 0x05040100u), __builtin_amdgcn_perm(lo23, lo01, 0x07060302u),
+                                  __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), __builtin_amdgcn_perm(hi23, hi01, 0x07060302u)};
+            }
+        } else if constexpr (WBY == 2) {
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                gvw::tie(ck.b16[i][0]);
+                gvw::tie(ck.b16[i][1]);
+                // word j = short j of short row 0 | short j of short row 1 << 16
+                const u32x2 r0 = ck.b16[i][0], r1 = ck.b16[i][1];
+                ck.w[i] = (u32x4){__builtin_amdgcn_perm(r1[0], r0[0], 0x05040100u), __builtin_amdgcn_perm(r1[0], r0[0], 0x07060302u),
+                                  __builtin_amdgcn_perm(r1[1], r0[1], 0x05040100u), __builtin_amdgcn_perm(r1[1], r0[1], 0x07060302u)};
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < R; ++i) gvw::tie(ck.w[i]);
+        }
         gvw::tie(ck.s);
         gvw::tie(ck.z);
     };
@@ -784,6 +840,27 @@ static const void* pick_bits(int nbits, int mb, int cq, int r, bool xd, int nw =
     }
 }
 
+// 8- / 16-bit packed words (wby = 1 / 2 bytes per word): 32- / 64-column tiles, x through LDS — 4- / 2-bit words 4 rows per lane (4 or 8 waves),
+// 2-bit words also 2 rows, 1-bit words 1 row on 64-column tiles
+template <typename Tag, int WBY>
+static const void* pick_pw_wby(int nbits, int cq, int r, int nw) {
+    if (cq != 3 && cq != 4) return nullptr;
+    if (nbits == 4 && r == 4)
+        return nw == 8 ? (cq == 4 ? (const void*)gemv_wn_kernel<Tag, 4, 1, 4, 4, false, 8, WBY> : (const void*)gemv_wn_kernel<Tag, 4, 1, 4, 3, false, 8, WBY>)
+                       : (cq == 4 ? (const void*)gemv_wn_kernel<Tag, 4, 1, 4, 4, false, 4, WBY> : (const void*)gemv_wn_kernel<Tag, 4, 1, 4, 3, false, 4, WBY>);
+    if (nbits == 2 && r == 4)
+        return nw == 8 ? (cq == 4 ? (const void*)gemv_wn_kernel<Tag, 2, 1, 4, 4, false, 8, WBY> : (const void*)gemv_wn_kernel<Tag, 2, 1, 4, 3, false, 8, WBY>)
+                       : (cq == 4 ? (const void*)gemv_wn_kernel<Tag, 2, 1, 4, 4, false, 4, WBY> : (const void*)gemv_wn_kernel<Tag, 2, 1, 4, 3, false, 4, WBY>);
+    if (nbits == 2 && r == 2 && nw == 4) return cq == 4 ? (const void*)gemv_wn_kernel<Tag, 2, 1, 2, 4, false, 4, WBY> : (const void*)gemv_wn_kernel<Tag, 2, 1, 2, 3, false, 4, WBY>;
+    if (nbits == 1 && r == 1 && nw == 4 && cq == 4) return (const void*)gemv_wn_kernel<Tag, 1, 1, 1, 4, false, 4, WBY>;
+    return nullptr;
+}
+template <typename Tag>
+static const void* pick_pw(int pack_bits, int nbits, int cq, int r, int nw) {
+    if (nbits > F16Traits<Tag>::MAX_QBITS) return nullptr;
+    return pack_bits == 8 ? pick_pw_wby<Tag, 1>(nbits, cq, r, nw) : (pack_bits == 16 ? pick_pw_wby<Tag, 2>(nbits, cq, r, nw) : nullptr);
+}
+
 // measured (profiles/r02/probe_gemv.log): A16W2 16384^2 20.0 -> 17.8 us with 8 waves (16 k per packed word: twice the unpack
 // arithmetic per byte); 4-bit shapes do not gain (16384^2: 24.6 vs 25.8 us, 8192^2: equal) and keep 4 waves
 constexpr bool GEMV_AUTO_8W = true;
@@ -793,6 +870,11 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
     if (nbits != 1 && nbits != 2 && nbits != 4 && nbits != 8) return false;
     const int e = 32 / nbits;
     if (a.M > 1 || a.K % e != 0) return false;  // M >= 2 goes to the MFMA streaming kernel (16-row tiles)
+    // 8- / 16-bit packed words: gemv_wn_kernel<..., WBY = 1 / 2> on 32- / 64-column tiles (x through LDS; not the direct-x and decode kernels)
+    const int pb = a.w_pack_bits;
+    if (pb != 32 && pb != 16 && pb != 8) return false;
+    const bool pw = pb != 32;
+    if (pw && (nbits > 4 || a.stride_wk < a.N)) return false;
     if (a.output_dtype != a.input_dtype) return false;  // typed epilogue
     const bool loop_s = a.W_group_mode >= 2, post_s = a.channel_scale_mode == 1 || a.channel_scale_mode == 3;
     const bool uses_s = loop_s || post_s;
@@ -819,6 +901,7 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
     const int mb = a.M <= 1 ? 1 : (a.M <= 2 ? 2 : 4);
 
     auto try_plan = [&](int cq, int want_splitk) -> bool {
+        if (pw && cq < 3) return false;
         const int tc = 4 << cq, G = 64 >> cq;
         if (a.N % tc != 0) return false;
         // rows per lane and step: must divide a group, cover whole 32-k spans of x, and fit the register budget
@@ -839,7 +922,7 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
         // K = 11008 / 8960 (Llama-2-7B down_proj, Qwen2.5-1.5B): 16-column tiles need 64-row chunks with 4 rows per
         // lane; the 16-wave direct-x variant takes 2 rows per lane (32-row chunks: 43 / 35 of them)
         bool force_xd16 = false;
-        if (!r && cq == 2 && nbits == 4 && mb == 1 && rows % (G * 2) == 0 && rpg % 2 == 0 && (caller_flags(a) & GEMLITE_TF_GEMV_X_MODE_MASK) != GEMLITE_TF_GEMV_X_THROUGH_LDS) {
+        if (!r && !pw && cq == 2 && nbits == 4 && mb == 1 && rows % (G * 2) == 0 && rpg % 2 == 0 && (caller_flags(a) & GEMLITE_TF_GEMV_X_MODE_MASK) != GEMLITE_TF_GEMV_X_THROUGH_LDS) {
             r = 2;
             force_xd16 = true;
         }
@@ -869,7 +952,7 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
         // tuning[3]: 0 auto | 1 stage x in LDS | 2 load x directly.  Direct x pays when a wave has <= 2 steps.
         const int steps = (units / splitk + 3) / 4;  // chunks per wave (4 waves)
         const int xmode = caller_flags(a) & GEMLITE_TF_GEMV_X_MODE_MASK;
-        bool xd = force_xd16 || (nbits == 4 && mb == 1 && r == 4 && (xmode == 2 || (xmode == 0 && steps <= 2)));
+        bool xd = !pw && (force_xd16 || (nbits == 4 && mb == 1 && r == 4 && (xmode == 2 || (xmode == 0 && steps <= 2))));
         // tuning[2]: 0 auto | 4 | 8 waves per block.  8 waves: one chunk per wave, two waves per SIMD (short K only)
         int nw = force_xd16 ? 16 : 4;
         if (force_xd16 && splitk != 1) return false;
@@ -893,8 +976,13 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
             // late round 6, 64-column tiles from 32 chunks per slice: 14336 x 4096 8.05 -> 7.72 us, 5120 x 13824 12.55 -> 11.58, 13824 x 5120 9.17 -> 8.75, 8192 x 28672 24.0 -> 22.5; 32-column tiles
             // LOSE with 8 waves (8192^2 9.13 -> 9.79, 8192 x 4096 6.19 -> 6.72) and keep the 128-chunk rule: profiles/r06/probe_m1_8waves_w4.log)
             nw = 8;
-        const void* fn = a.input_dtype == GEMLITE_DT_FP16 ? pick_bits<half_tag>(nbits, mb, cq, r, xd, nw)
-                                                           : pick_bits<bf16_tag>(nbits, mb, cq, r, xd, nw);
+        const void* fn = pw ? (a.input_dtype == GEMLITE_DT_FP16 ? pick_pw<half_tag>(pb, nbits, cq, r, nw) : pick_pw<bf16_tag>(pb, nbits, cq, r, nw))
+                       : (a.input_dtype == GEMLITE_DT_FP16 ? pick_bits<half_tag>(nbits, mb, cq, r, xd, nw)
+                                                           : pick_bits<bf16_tag>(nbits, mb, cq, r, xd, nw));
+        if (pw && !fn && nw == 8) {
+            nw = 4;
+            fn = a.input_dtype == GEMLITE_DT_FP16 ? pick_pw<half_tag>(pb, nbits, cq, r, nw) : pick_pw<bf16_tag>(pb, nbits, cq, r, nw);
+        }
         if (!fn && !xd && nw == 8) {
             nw = 4;
             fn = a.input_dtype == GEMLITE_DT_FP16 ? pick_bits<half_tag>(nbits, mb, cq, r, false) : pick_bits<bf16_tag>(nbits, mb, cq, r, false);
@@ -961,6 +1049,7 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
                   : xd ? (cq == 2 ? "gemv_wn_kernel<tile16,xdirect>" : (cq == 3 ? "gemv_wn_kernel<tile32,xdirect>" : "gemv_wn_kernel<tile64,xdirect>"))
                      : (nw == 8 ? (cq == 2 ? "gemv_wn_kernel<tile16,8w>" : (cq == 3 ? "gemv_wn_kernel<tile32,8w>" : "gemv_wn_kernel<tile64,8w>"))
                                 : (cq == 2 ? "gemv_wn_kernel<tile16>" : (cq == 3 ? "gemv_wn_kernel<tile32>" : "gemv_wn_kernel<tile64>")));
+        lp.name = pw_label(lp.name, pb);
         lp.grid = dim3(tiles, splitk, 1);
         lp.block = dim3(64 * nw, 1, 1);
         lp.lds_bytes = (size_t)mb * p.rows_per_slice * (e / 2) * 4 + (size_t)2 * mb * (p.rows_per_slice * e / 32) * 4 +

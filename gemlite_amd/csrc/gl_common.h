@@ -458,6 +458,8 @@ enum { MX_F16 = 1, MX_BF16 = 2, MX_FP8 = 3, MX_FP4 = 4 };
 // How many blocks of a one-block-per-CU kernel are resident at once on the current device (its CU count; 256 until a device
 // has been seen).  Kernels whose blocks WAIT for each other (reduce-scatter combine) are only planned within this limit.
 int resident_block_limit();
+// kernel label of a form for 8- / 16-bit packed words (pack_bits 8 / 16): `name` with ",b8" / ",b16" before its closing '>' (api.hip)
+const char* pw_label(const char* name, int pack_bits);
 
 // scalar kernel arguments of gemv_w4_decode3_kernel (gemv_decode.hip): 14 dwords the command processor preloads into SGPRs
 struct Decode3Args {
