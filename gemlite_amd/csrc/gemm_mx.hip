@@ -240,8 +240,10 @@ const void* nvfp4_expand_f16_kernel_fn() { return (const void*)nvfp4_expand_f16_
 // ---------------------------------------------------------------------------------------------------------------------
 // decode kernel (M <= 4): one wave per output column, lanes along K with 16-byte pieces of the K-contiguous weight row (the
 // streaming form of kmajor_matmul_kernel).  A piece is 32 fp4 / 16 fp8 weights of ONE microscaling block: the hardware
-// converters (v_cvt_scalef32_pk_*) turn it into scaled 16-bit pairs (exact: e2m1 / e4m3 times 2^e fits bf16), the same
-// for fp8 / fp4 activations with their block scale, and v_dot2_f32_{bf16,f16} accumulates in fp32.  Replaces the
+// converters (v_cvt_scalef32_pk_*) turn it into scaled bf16 pairs (exact: e2m1 / e4m3 times 2^e fits bf16), the same
+// for fp8 / fp4 activations with their block scale, and v_dot2_f32_{bf16,f16} accumulates in fp32.  Under fp16 activations
+// the weights are converted at scale 1.0 instead (e2m1 / e4m3 values are exact in fp16, e4m3 times 2^e is not: inexact
+// for e <= -16, infinite for e >= 8) and the block's 2^e multiplies the piece's fp32 partial sum.  Replaces the
 // GEMM_SPLITK route the reference takes for MX decode (core.py:100-105).
 // ---------------------------------------------------------------------------------------------------------------------
 template <int XF, int WF, int MB>
@@ -267,15 +269,16 @@ __global__ __launch_bounds__(1024) void mx_gemv_kernel(const GenericParams p) {
         const int64_t k0 = c * CK, kb = k0 >> 5;
         const u32x4 wv = *(const u32x4*)(wrow + c * 16);
         const float sw = __builtin_bit_cast(float, (uint32_t)srow[kb * p.stride_meta_g] << 23);
+        const float cw = H16 ? 1.0f : sw;  // fp16: the block scale is applied to the piece's fp32 sum below
         uint32_t wp[NP];
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             if constexpr (WF == MX_FP4) {
                 if constexpr (H16) {
-                    wp[4 * d + 0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(wv[d], sw, 0));
-                    wp[4 * d + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(wv[d], sw, 1));
-                    wp[4 * d + 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(wv[d], sw, 2));
-                    wp[4 * d + 3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(wv[d], sw, 3));
+                    wp[4 * d + 0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(wv[d], cw, 0));
+                    wp[4 * d + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(wv[d], cw, 1));
+                    wp[4 * d + 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(wv[d], cw, 2));
+                    wp[4 * d + 3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(wv[d], cw, 3));
                 } else {
                     wp[4 * d + 0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wv[d], sw, 0));
                     wp[4 * d + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wv[d], sw, 1));
@@ -284,8 +287,8 @@ __global__ __launch_bounds__(1024) void mx_gemv_kernel(const GenericParams p) {
                 }
             } else {
                 if constexpr (H16) {
-                    wp[2 * d + 0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(wv[d], sw, false));
-                    wp[2 * d + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(wv[d], sw, true));
+                    wp[2 * d + 0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(wv[d], cw, false));
+                    wp[2 * d + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(wv[d], cw, true));
                 } else {
                     wp[2 * d + 0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(wv[d], sw, false));
                     wp[2 * d + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(wv[d], sw, true));
@@ -298,12 +301,14 @@ __global__ __launch_bounds__(1024) void mx_gemv_kernel(const GenericParams p) {
             if (m >= p.M) continue;
             if constexpr (XF == MX_F16 || XF == MX_BF16) {
                 const uint8_t* xr = (const uint8_t*)p.x + (m * p.stride_xm + k0) * 2;
+                float part = H16 ? 0.f : acc[i];
 #pragma unroll
                 for (int q = 0; q < NP / 4; ++q) {
                     const u32x4 xv = *(const u32x4*)(xr + 16 * q);
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) acc[i] = dot(wp[4 * q + t], xv[t], acc[i]);
+                    for (int t = 0; t < 4; ++t) part = dot(wp[4 * q + t], xv[t], part);
                 }
+                acc[i] = H16 ? __builtin_fmaf(sw, part, acc[i]) : part;
             } else {
                 float sx = 1.0f;
                 if (p.sx_blocks) sx = __builtin_bit_cast(float, (uint32_t)((const uint8_t*)p.sx_blocks)[m * p.stride_sx_blk_m + kb] << 23);

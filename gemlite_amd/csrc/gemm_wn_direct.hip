@@ -8,8 +8,8 @@
 // fp32 accumulators), but with NO shared-memory staging and NO barrier before the final reduction:
 //   * the A fragment of lane (m = lane & 15, kb = lane >> 4) is the 8 (E for narrower codes) activations
 //     x[m][8 row .. 8 row + 7] that face the lane's own packed word; they come straight from global memory
-//     (L2-resident after the first touch) with one 16-byte load, are pair-permuted with v_perm_b32 and
-//     pre-scaled with v_pk_mul_f16 in registers;
+//     (L2-resident after the first touch) with one 16-byte load and are pair-permuted with v_perm_b32 in
+//     registers (never rescaled: every code sits at bit 0 of its 16-bit half, see DirWin);
 //   * the per-group sum of x that the zero-point term needs is produced by the matrix core as well: one extra
 //     MFMA per k-step against a constant B fragment (the inverse window scales), which lands in exactly the
 //     accumulator layout of the product — no VALU work, no LDS;
@@ -33,19 +33,14 @@ __device__ __forceinline__ f32x4 mfma16d<bf16_tag>(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8_t, a), __builtin_bit_cast(b8_t, b), c, 0, 0, 0);
 }
 
-// how many bit fields fit the mantissa next to each other (same geometry as the GEMV / streaming kernels)
+// one bit field per 16-bit window (WP = 1), shifted down to bit 0: fp16 uses the masked bits as subnormals (q 2^-24, exact), bf16
+// OR-s them into its magic number.  x enters the matrix core as it lies in memory.  (Earlier, fp16 packed 2 / 4 fields per window and
+// divided the matching x by 2^(NBITS i) in fp16 first, which put every |x| below 2^(NBITS i - 14) on fp16's subnormal grid: 4-bit rows
+// of amplitude 1e-4 came out ~2e-3 off, tests/test_magnitude_range_gpu.py.)
 template <typename Tag, int NBITS>
 struct DirWin {
     static constexpr bool SUBN = F16Traits<Tag>::DT == GEMLITE_DT_FP16;  // fp16: masked bits used as subnormals
-    static constexpr int MANT = SUBN ? 10 : 7;
-    static constexpr int HALF = 16 / NBITS;
-    static constexpr int fit() {
-        int wp = 1;
-        while (wp * 2 <= HALF && (((1 << NBITS) - 1) << (NBITS * (wp * 2 - 1))) < (1 << MANT)) wp *= 2;
-        return wp;
-    }
-    // bf16 keeps one field per window: a second field would need a (missing) packed bf16 multiply for x
-    static constexpr int WP = SUBN ? fit() : 1;
+    static constexpr int WP = 1;
 };
 
 template <int V> struct DirVec;
@@ -179,25 +174,17 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_wn_direct_kernel(const WnPara
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 const int ks = u * NF + f;
-                // A fragments: (x[a], x[a + HALF]) pairs, a = 4f + dd, scaled by 2^-(NBITS * (a % WP))
+                // A fragments: (x[a], x[a + HALF]) pairs, a = 4f + dd, unscaled
                 u32x4 afr[MT], onesb;
 #pragma unroll
                 for (int dd = 0; dd < 4; ++dd) {
-                    const int a = 4 * f + dd, b = a + HALF, wi = a % WP;
+                    const int a = 4 * f + dd, b = a + HALF;
 #pragma unroll
                     for (int t = 0; t < MT; ++t) {
                         const uint32_t lo = pc.x[u][a / 8][t][(a % 8) / 2], hi = pc.x[u][b / 8][t][(b % 8) / 2];
-                        uint32_t r = __builtin_amdgcn_perm(hi, lo, (a & 1) ? 0x07060302u : 0x05040100u);
-                        if constexpr (SUBN) {
-                            if (wi != 0) {
-                                const _Float16 sc = (_Float16)(1.0f / (float)(1u << (NBITS * wi)));
-                                r = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2_t, r) * (h2_t){sc, sc});
-                            }
-                        }
-                        afr[t][dd] = r;
+                        afr[t][dd] = __builtin_amdgcn_perm(hi, lo, (a & 1) ? 0x07060302u : 0x05040100u);
                     }
-                    // constant B fragment that turns the stored x back into x: 2^(NBITS * wi) (fp16) / 1.0 (bf16)
-                    onesb[dd] = SUBN ? (uint32_t)((15 + NBITS * wi) << 10) * 0x00010001u : TR::ONES2;
+                    onesb[dd] = TR::ONES2;  // constant B fragment of 1.0: sum(x) for the zero-point term
                 }
 #pragma unroll
                 for (int t = 0; t < MT; ++t) ones[t] = mfma16d<Tag>(afr[t], onesb, ones[t]);

@@ -12,8 +12,9 @@
 //     v_dot2 keep fp16 subnormals — scripts/ubench/probe_*.hip); the 2^24 is folded into the scale;
 //   * bf16: 7 mantissa bits and no usable subnormal range, so (bits | 0x4300) = 128 + q and the 128 * sum(x)
 //     term is removed together with the zero-point term.
-//   x is staged in LDS pair-permuted and pre-scaled by 2^-(4i) per window position (exact), together with
-//   per-32-k partial sums of x (true and as-stored) that the group epilogue needs.
+//   x is staged in LDS pair-permuted (bf16 2-bit words: pre-scaled by 2^-(2i) per window position, exact in bf16; fp16 takes one
+//   field per window and stages x unscaled), together with per-32-k partial sums of x (true and as-stored) that the group epilogue
+//   needs.
 //
 // Mapping (CDNA4): block = 4 waves, 64-column tile x BM = 16*MT rows x one K slice; a lane loads 16 bytes =
 // 4 adjacent columns x 8 k (4 packed rows x 256 B per wave-level load -> 4 MFMAs with column sets {4n + j});
@@ -50,7 +51,10 @@ struct StreamWin {
         while (wp * 2 <= HALF && (((1 << NBITS) - 1) << (NBITS * (wp * 2 - 1))) < (1 << MANT)) wp *= 2;
         return wp;
     }
-    static constexpr int WP = fit();
+    // fp16 keeps one field per window: a second field needs x divided by 2^(NBITS i), and in fp16 that rounds every |x| below
+    // 2^(NBITS i - 14) to the subnormal grid (4-bit rows of amplitude 1e-4 came out ~3e-3 off, tests/test_magnitude_range_gpu.py).
+    // bf16 has fp32's exponent range, so its pre-scale by 2^-(NBITS i) is exact.
+    static constexpr int WP = SUBN ? 1 : fit();
 };
 
 // SPG = MFMA k-steps (32 k each) per quantisation group inside a wave's 128-k span: 4 (group >= 128), 2, 1
