@@ -9,7 +9,13 @@ layer's stream comes from HBM (cache-cold rotation, SURVEY.md §7 "Hard parts").
 The step is captured once as a hipGraph (the launch-bound regime the reference itself addresses with CUDA
 graphs, config.py:17) and replayed; `value` is whole-job algorithmic GB/s over all ranks.
 
-The JSON line carries BOTH halves of BASELINE.json's metric ("... at M=1 and M=256") and all five BASELINE configs, measured in this
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs: set-up, warm-up, the N timed steps,
+`--dump-outputs`, and the result line — `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the workload's `config`, and in
+`roofline` what follows from the timed region alone (kernel name, time per launch, fraction of peak, committed counters).  Everything below that
+takes GPU or CPU runs of its own — per-launch event timings, the empty-launch period, every `roofline.*` group, `rotation_ab`, `eager`,
+`sustained`, `cpu_baseline` — is measured only with `--full` (after the timed steps and the dump, so the headline is the same either way).
+
+With `--full` the JSON line carries BOTH halves of BASELINE.json's metric ("... at M=1 and M=256") and all five BASELINE configs, measured in this
 process.  Round 5: EVERY block below lives INSIDE the `roofline` object in compact form ({kernel, kernel_us, frac, traffic, mfma_util};
 `achieved` / `unit` per block: --full-out) — the driver's parsed record keeps `roofline` whole and only the NAMES of other top-level keys, so the M = 256
 half of the metric (`roofline.m256`) is now driver-retained evidence.  `--full-out PATH` writes the verbose blocks to a file.  Every block uses ONE clock: wall time of a replayed hipGraph that holds >= 32 back-to-back launches of the workload over
@@ -474,12 +480,16 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="a16w4_4096_m1", choices=sorted(WORKLOADS))
-    ap.add_argument("--single", action="store_true", help="only the named workload (no M=256 / trend / sustained blocks)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: per-launch event timings, the empty-launch "
+                         "period, the other precisions / sizes / M (roofline.* groups), rotation A/B, eager host cost, the sustained leg and "
+                         "the CPU baseline.  Off by default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--single", action="store_true", help="with --full: only the named workload (no M=256 / trend / sustained blocks)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="profiler runs: short blocks (0.03 s each), sustained leg 0.2 s")
-    ap.add_argument("--kernel-samples", type=int, default=256, help="launches timed individually for roofline")
-    ap.add_argument("--full-out", default="", help="also write the verbose per-block records (clock strings, event timings, byte counts) to this file")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--quick", action="store_true", help="with --full, profiler runs: short blocks (0.03 s each), sustained leg 0.2 s")
+    ap.add_argument("--kernel-samples", type=int, default=256, help="with --full: launches timed individually for roofline (0: none)")
+    ap.add_argument("--full-out", default="", help="with --full: also write the verbose per-block records (clock strings, event timings, byte counts) to this file")
     ap.add_argument("--tuning", default="", help="development: comma-separated tuning[] override, e.g. 4,8")
     ap.add_argument("--matmul-type", default="", help="development: force a kernel family (forward_manual)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -487,6 +497,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.full_out and not args.full:
+        ap.error("--full-out writes the blocks that only --full measures: pass --full as well")
 
     from gemlite_amd.bench_utils import ReplicaGroup, timed_steps, whole_job_rate
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -526,19 +538,20 @@ def main():
             "clock": f"the timed region: {launches} launches in {elapsed * 1e3:.3f} ms of hipGraph replays" if main_run.graph is not None else "the timed region (eager launches)",
             "achieved": round(ach, 3), "peak": peak, "unit": unit, "frac": round(ach / peak, 4),
             "algorithmic_bytes_per_launch": main_run.bytes, "flops_per_launch": main_run.flops}
-    if args.kernel_samples > 0:
+    if args.full and args.kernel_samples > 0:
         try:  # secondary: per-launch HIP events (their own floor printed next to them)
             e_us = main_run.kernel_us(min(args.kernel_samples, 1024))
             roof["event_us"] = None if e_us != e_us else round(e_us, 3)
             roof["event_clock_floor_us"] = round(event_clock_floor_us(lib, main_run.stream), 3)
         except Exception as e:
             print(f"[bench] per-kernel event timing unavailable: {e}", file=sys.stderr)
-    try:  # the dependent-launch period of an EMPTY kernel inside a replayed graph, same process: what no kernel can go below
-        e0 = empty_launch_period_us(lib, main_run.stream)
-        roof["empty_launch_us"] = round(e0, 3)
-        roof["kernel_us_minus_empty_launch"] = round(gap_us - e0, 3)
-    except Exception as e:
-        print(f"[bench] empty-launch period unavailable: {e}", file=sys.stderr)
+    if args.full:
+        try:  # the dependent-launch period of an EMPTY kernel inside a replayed graph, same process: what no kernel can go below
+            e0 = empty_launch_period_us(lib, main_run.stream)
+            roof["empty_launch_us"] = round(e0, 3)
+            roof["kernel_us_minus_empty_launch"] = round(gap_us - e0, 3)
+        except Exception as e:
+            print(f"[bench] empty-launch period unavailable: {e}", file=sys.stderr)
     if bound == "hbm":
         roof["frac_vs_measured_copy_6290"] = round(roof["achieved"] / 6290.0, 4)
     else:
@@ -561,7 +574,7 @@ def main():
         "roofline": roof,
     }
 
-    extras = name == "a16w4_4096_m1" and not args.single and not args.tuning and not args.matmul_type
+    extras = args.full and name == "a16w4_4096_m1" and not args.single and not args.tuning and not args.matmul_type
     full = {}  # verbose blocks (--full-out); the printed line carries their compact form inside `roofline`
     if extras:
         def compact(b):
@@ -659,7 +672,7 @@ def main():
         roof = ordered
         line["roofline"] = roof
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.torch_cpu_path import time_cpu_baseline
         r = time_cpu_baseline(M, N, K, nbits, group, budget_s=12.0)
         sec = r["sec_per_call"]

@@ -7,7 +7,7 @@ off = sys.argv[1]
 boxes = sys.argv[sys.argv.index("--boxes") + 1] if "--boxes" in sys.argv else None
 d = json.load(open(os.path.join(root, off, "bench_default.json")))
 r = d["roofline"]
-# round 5: the printed line is compact; `bench.py --full-out bench_full.json` keeps the verbose blocks next to it
+# round 5: the printed line is compact; `bench.py --full --full-out bench_full.json` keeps the verbose blocks next to it
 full = {}
 if os.path.exists(os.path.join(root, off, "bench_full.json")):
     full = json.load(open(os.path.join(root, off, "bench_full.json"))).get("blocks", {})

@@ -12,7 +12,7 @@ grep -h "^{" $O/ref.log | python -c "
 import sys, json
 for l in sys.stdin:
     r = json.loads(l); print('REF', r.get('case'), r.get('first_call_s'), r.get('graph_us'), r.get('error'))"
-timeout 900 python bench.py --full-out $O/bench_full.json > $O/bench_default.json 2> $O/bench_default.err; python - <<'P'
+timeout 900 python bench.py --full --full-out $O/bench_full.json > $O/bench_default.json 2> $O/bench_default.err; python - <<'P'
 import json
 d = json.load(open('gpurun_out/r6a/bench_default.json'))
 r = d['roofline']

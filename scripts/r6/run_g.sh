@@ -8,7 +8,7 @@ for f in $O/probe_m1_shapes_w4_after.log $O/probe_m1_shapes_w2_after.log; do gre
 import sys, json
 for l in sys.stdin:
     r = json.loads(l); print(r['N'], r['K'], 'default', r['default'], 'best', r['best'], 'gain', r['gain'])"; done
-timeout 900 python bench.py --full-out $O/bench_full.json > $O/bench_default.json 2> $O/bench_default.err; python - <<'P'
+timeout 900 python bench.py --full --full-out $O/bench_full.json > $O/bench_default.json 2> $O/bench_default.err; python - <<'P'
 import json
 d = json.load(open('gpurun_out/r6g/bench_default.json'))
 r = d['roofline']

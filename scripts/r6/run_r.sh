@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r6x; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q --maxfail=25 -p no:cacheprovider --timeout 600 > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -15 $O/pytest.log
-timeout 900 python bench.py --full-out $O/bench_full.json > $O/bench_default.json 2> $O/bench_default.err; python - <<'PY'
+timeout 900 python bench.py --full --full-out $O/bench_full.json > $O/bench_default.json 2> $O/bench_default.err; python - <<'PY'
 import json
 d = json.load(open('gpurun_out/r6x/bench_default.json'))
 r = d['roofline']
