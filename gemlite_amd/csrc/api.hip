@@ -56,6 +56,12 @@ const void* act_quant_vec_kernel_fn(int in_dt, int out_dt, int64_t K, int64_t st
 const void* pack_kernel_fn();
 const void* pack32_kernel_fn();
 const void* unpack_kernel_fn();
+// capture_group.hip: independent decode3 launches of one stream capture folded into one grouped launch
+int capture_group_limit();
+void capture_group_stats(uint64_t* seen, uint64_t* joined);
+bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPlan& la, const gemlite_hip_forward_args& b, const LaunchPlan& lb);
+bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st);
+void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st);
 
 }  // namespace gl
 
@@ -951,6 +957,19 @@ void gemlite_hip_set_profile_events(void* start_event, void* stop_event) {
     tl_evt_stop = stop_event;
 }
 
+int gemlite_hip_capture_group_max(void) { return capture_group_limit(); }
+
+void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined) { capture_group_stats(seen, joined); }
+
+int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b) {
+    if (validate(a) != GEMLITE_OK || validate(b) != GEMLITE_OK) return 0;
+    Resolved ra, rb;
+    resolve(*a, ra);
+    resolve(*b, rb);
+    if (ra.status != GEMLITE_OK || rb.status != GEMLITE_OK) return 0;
+    return capture_group_compatible(*a, ra.lp, *b, rb.lp) ? 1 : 0;
+}
+
 int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream) {
     if (blocks <= 0 || threads <= 0 || threads > 1024) return GEMLITE_ERR_BAD_ARGUMENT;
     void* none[1] = {nullptr};
@@ -985,7 +1004,13 @@ int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) {
             d.counters = r.wn.counters;
             void* dargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                              (void*)&d.nch_total, (void*)&d.modes, (void*)&d.counters};
-            return launch(r.lp.fn, r.lp.grid, r.lp.block, dargs, 0, st);
+            // under stream capture an independent neighbour joins the node of the launch before it (capture_group.hip); a launch with
+            // profile events or the timeline probe is always its own
+            const bool plain = tl_evt_start || tl_evt_stop;
+            if (!plain && capture_group_try_join(*args, r.lp, st)) return GEMLITE_OK;
+            const int rc = launch(r.lp.fn, r.lp.grid, r.lp.block, dargs, 0, st);
+            if (!plain && rc == GEMLITE_OK) capture_group_note_launch(*args, r.lp, st);
+            return rc;
         }
         if (r.lp.arg_kind == 2) {  // gemm_wn_rows.hip
             Rows5Args& d = r.lp.r5;

@@ -1,0 +1,221 @@
+// capture_group.hip — host only: back-to-back INDEPENDENT M = 1 decode launches of one stream capture become one grouped launch.
+//
+// At 8.9 MB a gemv_w4_decode3_kernel launch is latency-bound: of ~4.75 us per layer in a replayed graph, ~1.7 us is the dependent-launch
+// boundary and ~1.6 us ramp, first-byte latency and tail, all paid again by the next launch.  Real decode graphs hold runs
+// of launches that do not depend on each other (q / k / v, gate / up, experts; the benchmark step: one x, 64 weights, 64 outputs); they are
+// serialised only because `layer(x)` is a per-layer call.  A stream capture can be looked back into while it is in progress
+// (hipStreamGetCaptureInfo_v2 names the node the next launch would depend on) and its nodes can be edited (hipGraphKernelNodeSetParams), so:
+//
+//   * a decode3 launch under capture that cannot join is launched as always, and the node it became opens a group of one;
+//   * the next decode3 launch joins the open group when NOTHING else was captured on the stream since (the stream's only dependency is the
+//     group's node), kernel / shape / strides / modes agree, and its output overlaps no member's inputs or output and no member's output
+//     overlaps its inputs.  Joining rewrites the node to gemv_w4_decode3_kernel<.., Decode3GroupTable> with grid.y = members; no node is
+//     added and the stream's dependency set stays as it is.
+//
+// The graph stays LINEAR on one queue.  Sound because nothing foreign lies between A and B on the stream: B's stream-order dependencies are
+// A plus A's own, and independence from A makes A's own sufficient; everything captured later depends on the group node and so on every
+// member.  A dependent chain (x_B overlaps out_A) never groups and gets the graph it always got, node for node.  Any HIP error on this path
+// drops the group and the call is launched the plain way: grouping never turns a working capture into a failing one.
+//
+// GEMLITE_HIP_NO_CAPTURE_GROUPS=1 (read once) turns it off; GEMLITE_HIP_CAPTURE_GROUP_MAX=n (development, read once) lowers the member limit.
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+
+#include "gl_common.h"
+
+namespace gl {
+
+const void* gemv_w4_decode3_fn(int tag, bool nt);        // gemv_decode.hip
+const void* gemv_w4_decode3_group_fn(int tag, bool nt);  // gemv_decode.hip
+
+namespace {
+
+struct Span {  // bytes [lo, hi); empty when lo == hi
+    uintptr_t lo, hi;
+};
+struct Footprint {
+    Span rd[4];  // x, W_q, scales, zeros
+    Span wr;     // out
+};
+
+bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi && a.lo != a.hi && b.lo != b.hi; }
+
+int elt_bytes(int dt) {  // (unknown codes: the widest, the footprint only has to be large enough)
+    switch (dt) {
+        case GEMLITE_DT_FP16: case GEMLITE_DT_BF16: case GEMLITE_DT_INT16: case GEMLITE_DT_UINT16: return 2;
+        case GEMLITE_DT_FP32: case GEMLITE_DT_INT32: case GEMLITE_DT_UINT32: return 4;
+        default: return 8;
+    }
+}
+
+// A 2-d view of n0 x n1 elements of `esz` bytes at strides s0 / s1 (elements, either sign): from its lowest byte to the end of its last element
+Span span2d(const void* p, int64_t esz, int64_t n0, int64_t s0, int64_t n1, int64_t s1) {
+    if (!p || n0 <= 0 || n1 <= 0) return Span{0, 0};
+    const int64_t e0 = (n0 - 1) * s0, e1 = (n1 - 1) * s1;
+    const int64_t lo = (e0 < 0 ? e0 : 0) + (e1 < 0 ? e1 : 0), hi = (e0 > 0 ? e0 : 0) + (e1 > 0 ? e1 : 0) + 1;
+    return Span{(uintptr_t)p + (uintptr_t)(lo * esz), (uintptr_t)p + (uintptr_t)(hi * esz)};
+}
+
+// Everything one decode3 launch may touch, from the caller's pointers, shapes and strides (never less than the kernel reads or writes:
+// metadata pointers count whenever they are given, whether the mode reads them or not)
+Footprint footprint(const gemlite_hip_forward_args& a) {
+    Footprint f;
+    const int64_t e = a.elements_per_sample > 0 ? a.elements_per_sample : 1, gs = a.group_size > 0 ? a.group_size : 1;
+    f.rd[0] = span2d(a.x, elt_bytes(a.input_dtype), a.M, a.stride_xm, a.K, a.stride_xk);
+    f.rd[1] = span2d(a.w_q, a.w_pack_bits > 0 ? a.w_pack_bits / 8 : elt_bytes(a.w_dtype), (a.K + e - 1) / e, a.stride_wk, a.N, a.stride_wn);
+    f.rd[2] = span2d(a.scales, elt_bytes(a.meta_dtype), (a.K + gs - 1) / gs, a.stride_meta_g, a.N, a.stride_meta_n);
+    f.rd[3] = a.zero_is_scalar ? span2d(a.zeros, 8, 1, 0, 1, 0)
+                               : span2d(a.zeros, elt_bytes(a.zeros_dtype), (a.K + gs - 1) / gs, a.stride_meta_g, a.N, a.stride_meta_n);
+    f.wr = span2d(a.out, elt_bytes(a.output_dtype), a.M, a.stride_om, a.N, a.stride_on);
+    return f;
+}
+
+bool independent(const Footprint& a, const Footprint& b) {
+    if (overlap(a.wr, b.wr)) return false;
+    for (int i = 0; i < 4; ++i)
+        if (overlap(b.wr, a.rd[i]) || overlap(a.wr, b.rd[i])) return false;
+    return true;
+}
+
+// What a group shares: the kernel, its grid and the four scalars behind the five pointers.  (The timeline probe never groups.)
+bool same_launch(const LaunchPlan& a, const LaunchPlan& b) {
+    return a.arg_kind == 1 && b.arg_kind == 1 && a.fn == b.fn && a.grid.x == b.grid.x && a.grid.y == 1 && b.grid.y == 1 && a.grid.z == 1 &&
+           b.grid.z == 1 && a.block.x == b.block.x && a.d3.sw4 == b.d3.sw4 && a.d3.mstride2 == b.d3.mstride2 &&
+           a.d3.nch_total == b.d3.nch_total && a.d3.modes == b.d3.modes && !(a.d3.modes & 64u);
+}
+
+const void* group_fn_of(const void* fn) {
+    for (int tag = 0; tag < 2; ++tag)
+        for (int nt = 0; nt < 2; ++nt)
+            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_fn(tag, nt != 0);
+    return nullptr;
+}
+
+int env_int(const char* name, int absent) {
+    const char* v = getenv(name);
+    return (v && *v) ? atoi(v) : absent;
+}
+
+std::atomic<uint64_t> g_seen{0}, g_joined{0};
+
+struct Group {
+    bool open = false;
+    bool capturing = false;  // the last try_join() of this thread saw an active capture: note_launch() has a node to pick up
+    unsigned long long cap_id = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphNode_t node = nullptr;
+    LaunchPlan lp{};  // member 0: kernel, grid, block, scalars
+    const void* fn_group = nullptr;
+    Decode3GroupTable tab{};
+    Footprint fp[DECODE3_GMAX];
+    int members = 0;
+};
+thread_local Group tl_group;
+
+bool capture_state(hipStream_t st, unsigned long long* id, hipGraph_t* graph, hipGraphNode_t* only_dep) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    const hipGraphNode_t* deps = nullptr;
+    size_t ndeps = 0;
+    *graph = nullptr;
+    if (hipStreamGetCaptureInfo_v2(st, &status, id, graph, &deps, &ndeps) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (status != hipStreamCaptureStatusActive || !*graph) return false;
+    *only_dep = (ndeps == 1 && deps) ? deps[0] : nullptr;
+    return true;
+}
+
+}  // namespace
+
+int capture_group_limit() {
+    static const int limit = [] {
+        if (env_int("GEMLITE_HIP_NO_CAPTURE_GROUPS", 0) != 0) return 1;
+        const int n = env_int("GEMLITE_HIP_CAPTURE_GROUP_MAX", DECODE3_GMAX);
+        return n < 1 ? 1 : (n > DECODE3_GMAX ? DECODE3_GMAX : n);
+    }();
+    return limit;
+}
+
+void capture_group_stats(uint64_t* seen, uint64_t* joined) {
+    if (seen) *seen = g_seen.load(std::memory_order_relaxed);
+    if (joined) *joined = g_joined.load(std::memory_order_relaxed);
+}
+
+// The host-only rule: may launch B (args b, plan lb) run in the same grouped launch as A?
+bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPlan& la, const gemlite_hip_forward_args& b, const LaunchPlan& lb) {
+    return same_launch(la, lb) && group_fn_of(la.fn) != nullptr && independent(footprint(a), footprint(b));
+}
+
+// Called in front of every decode3 launch that carries no profile events.  true: the call was folded into the open group's node, nothing
+// is left to launch.  false: launch as always, then call capture_group_note_launch().
+bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st) {
+    Group& g = tl_group;
+    g.capturing = false;
+    if (capture_group_limit() < 2 || (lp.d3.modes & 64u)) return false;
+    unsigned long long id = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphNode_t dep = nullptr;
+    if (!capture_state(st, &id, &graph, &dep)) {
+        g.open = false;
+        return false;
+    }
+    g.capturing = true;
+    g_seen.fetch_add(1, std::memory_order_relaxed);
+    if (!g.open || g.cap_id != id || g.graph != graph || !dep || dep != g.node || g.members >= capture_group_limit() || !same_launch(g.lp, lp))
+        return false;
+    const Footprint fb = footprint(a);
+    for (int i = 0; i < g.members; ++i)
+        if (!independent(g.fp[i], fb)) return false;
+    Decode3Member& m = g.tab.m[g.members - 1];
+    m.w = lp.d3.w; m.x = lp.d3.x; m.s = lp.d3.s; m.z = lp.d3.z; m.out = lp.d3.out;
+    Decode3Args& d = g.lp.d3;
+    void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
+                     (void*)&d.nch_total, (void*)&d.modes, (void*)&g.tab};
+    hipKernelNodeParams np;
+    memset(&np, 0, sizeof(np));
+    np.func = (void*)g.fn_group;
+    np.gridDim = dim3(g.lp.grid.x, (unsigned)(g.members + 1), 1);
+    np.blockDim = g.lp.block;
+    np.sharedMemBytes = 0;
+    np.kernelParams = kargs;
+    np.extra = nullptr;
+    if (hipGraphKernelNodeSetParams(g.node, &np) != hipSuccess) {  // the node keeps what it had; this call runs on its own
+        (void)hipGetLastError();
+        g.open = false;
+        return false;
+    }
+    g.fp[g.members++] = fb;
+    g_joined.fetch_add(1, std::memory_order_relaxed);
+    return true;
+}
+
+// After a plain decode3 launch that try_join() declined under capture: the node it became is the stream's single dependency now,
+// and opens a new group of one (which keeps the single-layer kernel until somebody joins).
+void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st) {
+    Group& g = tl_group;
+    if (!g.capturing) return;
+    g.capturing = false;
+    g.open = false;
+    const void* fn_group = group_fn_of(lp.fn);
+    if (!fn_group || lp.arg_kind != 1 || lp.grid.y != 1 || lp.grid.z != 1) return;
+    unsigned long long id = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphNode_t dep = nullptr;
+    if (!capture_state(st, &id, &graph, &dep) || !dep) return;
+    hipGraphNodeType type = hipGraphNodeTypeEmpty;
+    if (hipGraphNodeGetType(dep, &type) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (type != hipGraphNodeTypeKernel) return;
+    g.cap_id = id;
+    g.graph = graph;
+    g.node = dep;
+    g.lp = lp;
+    g.fn_group = fn_group;
+    memset(&g.tab, 0, sizeof(g.tab));
+    g.fp[0] = footprint(a);
+    g.members = 1;
+    g.open = true;
+}
+
+}  // namespace gl

@@ -15,6 +15,8 @@
 //   * grid size / tile pairing come in through the arguments: no implicit-argument loads at all.
 // 16 waves x 64 lanes, lane (g = lane >> 2, c = lane & 3) owns columns 4c .. 4c + 3 of a 16-column tile and packed rows
 // chunk * 512 + wave * 32 + 2 g + {0, 1}.
+#include <type_traits>
+
 #include "gl_common.h"
 
 namespace gl {
@@ -35,11 +37,26 @@ constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
 
 }  // namespace dec3
 
-template <typename Tag, bool NT>
-__global__ __launch_bounds__(1024, 1) void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
-                                                                   uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
-                                                                   unsigned* counters) {
+// Tail = unsigned*: the single-layer kernel, `counters` is the timeline buffer.
+// Tail = Decode3GroupTable: the GROUPED form — grid (N / 16, members), blockIdx.y selects one of up to DECODE3_GMAX independent layers of
+// identical shape, strides, modes and dtype (capture_group.hip folds back-to-back independent launches of a stream capture into one
+// such launch).  blockIdx.x stays fastest, so the chip streams layer 0, then layer 1, ...  Layer 0's pointers are the preloaded scalars;
+// the others come out of the by-value table behind the 14 dwords with scalar loads.  Everything after the pointer fetch is the
+// single-layer code, so every layer's output is bit-identical to its own launch.  No timeline probe in a group.
+template <typename Tag, bool NT, typename Tail = unsigned*>
+__global__ __launch_bounds__(1024, (std::is_same<Tail, Decode3GroupTable>::value ? DECODE3_GROUP_WAVES_PER_SIMD : 1))
+void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
+                            uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
+                            const Tail counters) {
     using namespace dec3;
+    constexpr bool GROUPED = std::is_same<Tail, Decode3GroupTable>::value;
+    if constexpr (GROUPED) {
+        const int layer = (int)blockIdx.y;
+        if (layer > 0) {
+            const Decode3Member& m = counters.m[layer - 1];
+            wb = m.w; xb = m.x; sp = m.s; zp = m.z; out = m.out;
+        }
+    }
     using TR = F16Traits<Tag>;
     constexpr bool SUBN = TR::DT == GEMLITE_DT_FP16;
     constexpr int WP = SUBN ? 2 : 1;  // 4-bit fields per 16-bit window (Window<Tag, 4>::WP of gemv_wn.hip)
@@ -82,9 +99,11 @@ __global__ __launch_bounds__(1024, 1) void gemv_w4_decode3_kernel(const char* wb
     // opt-in timeline (GEMLITE_TF_TIMELINE): the mode bit is a preloaded SGPR, so a normal launch never touches `counters` (the one
     // argument behind the preloaded 14 dwords) and never waits for a kernarg load
     auto stamp = [&](int i) {
-        if (__builtin_expect((modes & M_PROBE) != 0u, 0)) {
-            if (counters && wave == 0 && lane == 0 && blockIdx.x < 1024)
-                ((unsigned long long*)(counters + MAX_SPLITK_COUNTERS))[blockIdx.x * 4 + i] = __builtin_amdgcn_s_memrealtime();
+        if constexpr (!GROUPED) {
+            if (__builtin_expect((modes & M_PROBE) != 0u, 0)) {
+                if (counters && wave == 0 && lane == 0 && blockIdx.x < 1024)
+                    ((unsigned long long*)(counters + MAX_SPLITK_COUNTERS))[blockIdx.x * 4 + i] = __builtin_amdgcn_s_memrealtime();
+            }
         }
     };
     stamp(0);
@@ -190,6 +209,13 @@ const void* gemv_w4_decode3_fn(int tag, bool nt) {
     typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, unsigned*);
     kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true> : gemv_w4_decode3_kernel<half_tag, false>)
                      : (nt ? gemv_w4_decode3_kernel<bf16_tag, true> : gemv_w4_decode3_kernel<bf16_tag, false>);
+    return (const void*)k;
+}
+
+const void* gemv_w4_decode3_group_fn(int tag, bool nt) {
+    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3GroupTable);
+    kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true, Decode3GroupTable> : gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTable>)
+                     : (nt ? gemv_w4_decode3_kernel<bf16_tag, true, Decode3GroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTable>);
     return (const void*)k;
 }
 

@@ -471,6 +471,23 @@ struct Decode3Args {
     unsigned* counters;
 };
 
+// gemv_w4_decode3_group_kernel (gemv_decode.hip): the pointers of layers 1 .. DECODE3_GMAX - 1 of a grouped launch, passed by value behind
+// the 14 preloaded dwords (layer 0's Decode3Args without `counters`).  sw4 / mstride2 / nch_total / modes are shared by the group.
+constexpr int DECODE3_GMAX = 16;
+struct Decode3Member {
+    const char *w, *x, *s, *z;
+    uint16_t* out;
+};
+struct Decode3GroupTable {
+    Decode3Member m[DECODE3_GMAX - 1];
+};
+// Waves per SIMD the compiler must keep resident for the grouped kernel (the second __launch_bounds__ argument of HIP).  One 1024-thread
+// block is 4 waves per SIMD; 8 = two blocks per CU, at most 64 VGPRs per lane (A/B builds only: profiles/r07/capture_groups.log has
+// why the shipped value is what it is)
+#ifndef DECODE3_GROUP_WAVES_PER_SIMD
+#define DECODE3_GROUP_WAVES_PER_SIMD 4
+#endif
+
 // scalar kernel arguments of gemm_w4_rows_kernel (gemm_wn_rows.hip): the same 14 preloaded dwords, then M and the row strides
 struct Rows5Args {
     const char *w, *x, *s, *z;

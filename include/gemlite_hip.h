@@ -316,6 +316,20 @@ void gemlite_hip_set_profile_events(void* start_event, void* stop_event);
  * to every kernel duration it quotes (on MI355X an empty kernel already reads ~4 us). */
 int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
 
+/* Capture-time grouping of the M = 1 decode kernel.  While `stream` is being captured into a graph, a gemlite_hip_forward call that runs
+ * gemv_w4_decode3_kernel and is INDEPENDENT of the decode launches captured directly before it (nothing else captured on the stream in
+ * between; same kernel, shape, strides and modes; its output overlaps none of their inputs or outputs, their outputs none of its inputs)
+ * adds no node: the node before it becomes one grouped launch of up to gemlite_hip_capture_group_max layers.  Every layer's result is
+ * bit-identical to its own launch, the graph stays linear, and a dependent chain is captured node for node as before.  Eager launches,
+ * launches with profile events and GEMLITE_TF_TIMELINE launches never group.  The environment variable GEMLITE_HIP_NO_CAPTURE_GROUPS=1
+ * (read once per process) turns grouping off.
+ *   _max         layers per grouped launch (1 = grouping is off)
+ *   _stats       process-wide counts: decode launches seen under capture, and how many of them joined a node instead of adding one
+ *   _compatible  host only, nothing is dereferenced: 1 if launch `b` captured directly behind launch `a` would join it, else 0 */
+int gemlite_hip_capture_group_max(void);
+void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
+int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
+
 /* Per-token dynamic activation quantisation: for each row m of x[M,K] (fp16/bf16/fp32)
  *   s[m] = max(amax(|x[m,:]|) / qmax, 1e-6) (fp32);  y = clamp(x / s, qmin, qmax);
  *   int8: round half away from zero;  fp8: round-to-nearest-even cast.

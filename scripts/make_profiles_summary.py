@@ -13,7 +13,7 @@ if os.path.exists(os.path.join(root, off, "bench_full.json")):
     full = json.load(open(os.path.join(root, off, "bench_full.json"))).get("blocks", {})
 avg = calls = mn = None
 for row in csv.DictReader(open(os.path.join(root, off, "rocprof_bench_kernel_stats.csv"))):
-    if "gemv_w4_decode3_kernel<gl::half_tag, true>" in row["Name"]:
+    if "gemv_w4_decode3_kernel<gl::half_tag, true>" in row["Name"] or "gemv_w4_decode3_kernel<gl::half_tag, true, unsigned int*>" in row["Name"]:
         avg, calls, mn = float(row["AverageNs"]) / 1000, int(row["Calls"]), float(row["MinNs"]) / 1000
 cb = d["cpu_baseline"]
 
