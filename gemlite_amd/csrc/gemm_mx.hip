@@ -609,6 +609,10 @@ bool plan_mx_rows(const gemlite_hip_forward_args& a, GenericParams& g, LaunchPla
     if (((uintptr_t)a.x | (uintptr_t)a.w_q) % 16 != 0 || a.stride_xm % 16 != 0 || a.stride_wn % 16 != 0) return false;
     if ((int64_t)a.M * a.stride_xm + a.K >= (1ll << 31) || (int64_t)a.N * a.stride_wn + a.K >= (1ll << 31)) return false;
     if ((int64_t)(a.K / 32) * a.stride_meta_g + (int64_t)a.N * a.stride_meta_n >= (1ll << 31)) return false;
+    // the activation block scales: an (int) num_records over M_pad rows, read through the 32-bit offset avoff.  With several row
+    // blocks avoff is also formed for rows past M_pad (M = 65: up to row 127); those stay below 2^32, miss or hit num_records,
+    // and feed only output rows >= M, which are not stored
+    if (!fq && g.sx_blocks && (int64_t)((a.M + 31) / 32 * 32) * g.stride_sx_blk_m + a.K / 32 >= (1ll << 31)) return false;
     const int mt = a.M <= 16 ? 1 : (a.M <= 32 ? 2 : 4);
     const int64_t xrow = g.mx_x == MX_FP8 ? a.K : a.K / 2;
     if (mt > 1 && a.tuning[0] != 4 && !any_m && (int64_t)a.M * xrow * (a.N / 16) > (88ll << 20)) return false;  // every block re-reads its rows of x from L2
@@ -799,6 +803,7 @@ bool plan_nvfp4_rows(const gemlite_hip_forward_args& a, GenericParams& g, Launch
     if (!fq && (((uintptr_t)a.x % 8) != 0 || a.stride_xm % 8 != 0)) return false;
     if ((int64_t)a.M * a.stride_xm + a.K >= (1ll << 31) || (int64_t)a.N * a.stride_wn + a.K >= (1ll << 31)) return false;
     if ((int64_t)(a.K / 16) * a.stride_meta_g + (int64_t)a.N * a.stride_meta_n >= (1ll << 31)) return false;
+    if (!fq && (int64_t)((a.M + 15) / 16 * 16) * g.stride_sx_blk_m + a.K / 16 >= (1ll << 31)) return false;  // activation block scales (avoff, rsA)
     const int mt = a.M <= 16 ? 1 : (a.M <= 32 ? 2 : 4);
     if (mt > 1 && a.tuning[0] != 4 && (int64_t)a.M * (a.K / 2) * (a.N / 16) > (88ll << 20)) return false;
     // round 4 (profiles/r04/probe_rows_vs_tiles*.log): against the fp16 tile kernel the crossover sits at M N K ~ 600 M (4096^2: M = 36 of the

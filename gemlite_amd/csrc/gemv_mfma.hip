@@ -408,7 +408,9 @@ bool plan_gemv_mfma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& 
     else return false;
     if (a.K % (32 * spg) != 0) return false;
     const int64_t rows = a.K / (32 / a.W_nbits);
-    if (rows * a.stride_wk * 4 + a.N * 4 >= (1ll << 32) || (int64_t)(a.K / gs) * p.stride_meta_g + a.N >= (1ll << 32)) return false;  // 32-bit offsets
+    // 32-bit byte offsets into w, the metadata and (2 .. 4 rows: one descriptor over all rows, a scalar offset per row) x
+    if (rows * a.stride_wk * 4 + a.N * 4 >= (1ll << 32) || ((int64_t)(a.K / gs) * p.stride_meta_g + a.N) * 2 >= (1ll << 32)) return false;
+    if (((int64_t)(a.M - 1) * a.stride_xm + a.K) * 2 >= (1ll << 32)) return false;
     const int mb = a.M == 1 ? 1 : 4;
     const int ngroups = (int)(a.K / (32 * spg));
     // tile width: the widest tile that gives >= 256 blocks (one per CU) — K is never split across blocks

@@ -31,7 +31,9 @@
  *   - return value: 0 on success, a negative gemlite_status_t otherwise;
  *     gemlite_hip_status_string() maps it to text.  Nothing is launched on error;
  *   - dtype arguments are the integer codes of gemlite/dtypes.py:8-29 (gemlite_dtype_t);
- *   - strides are in ELEMENTS of the tensor's own dtype (what torch's .stride() returns).
+ *   - strides are in ELEMENTS of the tensor's own dtype (what torch's .stride() returns);
+ *   - strides are 64-bit: an operand whose addressed extent reaches what a kernel's 32-bit offsets cover (2 GiB or 4 GiB, by
+ *     kernel) is routed to a kernel with 64-bit addresses (the planner's side of this is tested: tests/test_addressing_limits_cpu.py).
  */
 #ifndef GEMLITE_HIP_H
 #define GEMLITE_HIP_H
