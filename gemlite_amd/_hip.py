@@ -111,6 +111,8 @@ def load():
         lib.gemlite_hip_capture_group_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         lib.gemlite_hip_capture_group_compatible.restype = C.c_int
         lib.gemlite_hip_capture_group_compatible.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardArgs)]
+        lib.gemlite_hip_capture_group_grid_y.restype = C.c_int
+        lib.gemlite_hip_capture_group_grid_y.argtypes = [C.c_int32, C.c_int32]
         lib.gemlite_hip_scale_activations_per_token.restype = C.c_int
         lib.gemlite_hip_scale_activations_per_token.argtypes = [
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
@@ -139,6 +141,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_pack_over_cols",
     "gemlite_hip_unpack_over_cols",
     "gemlite_hip_capture_group_max", "gemlite_hip_capture_group_stats", "gemlite_hip_capture_group_compatible",
+    "gemlite_hip_capture_group_grid_y",
 )
 
 

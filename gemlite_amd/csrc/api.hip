@@ -60,7 +60,7 @@ const void* unpack_kernel_fn();
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
 bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPlan& la, const gemlite_hip_forward_args& b, const LaunchPlan& lb);
-bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st);
+bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident);
 void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st);
 
 }  // namespace gl
@@ -961,6 +961,10 @@ int gemlite_hip_capture_group_max(void) { return capture_group_limit(); }
 
 void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined) { capture_group_stats(seen, joined); }
 
+int gemlite_hip_capture_group_grid_y(int32_t tiles, int32_t members) {
+    return (tiles > 0 && members > 0) ? decode3_group_grid_y(tiles, members, 256) : 0;
+}
+
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b) {
     if (validate(a) != GEMLITE_OK || validate(b) != GEMLITE_OK) return 0;
     Resolved ra, rb;
@@ -985,6 +989,7 @@ int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) {
     Resolved r;
     tl_plan_dev = dv == GEMLITE_OK ? dev : -1;
     resolve(*args, r);
+    const int resident = gl::resident_block_limit();  // of the device planned for: a capture-group join sizes its grid.y by it
     tl_plan_dev = -1;
     if (r.status != GEMLITE_OK) return r.status;
     if (dv != GEMLITE_OK) return dv;
@@ -1007,7 +1012,7 @@ int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) {
             // under stream capture an independent neighbour joins the node of the launch before it (capture_group.hip); a launch with
             // profile events or the timeline probe is always its own
             const bool plain = tl_evt_start || tl_evt_stop;
-            if (!plain && capture_group_try_join(*args, r.lp, st)) return GEMLITE_OK;
+            if (!plain && capture_group_try_join(*args, r.lp, st, resident)) return GEMLITE_OK;
             const int rc = launch(r.lp.fn, r.lp.grid, r.lp.block, dargs, 0, st);
             if (!plain && rc == GEMLITE_OK) capture_group_note_launch(*args, r.lp, st);
             return rc;

@@ -9,8 +9,9 @@
 //   * a decode3 launch under capture that cannot join is launched as always, and the node it became opens a group of one;
 //   * the next decode3 launch joins the open group when NOTHING else was captured on the stream since (the stream's only dependency is the
 //     group's node), kernel / shape / strides / modes agree, and its output overlaps no member's inputs or output and no member's output
-//     overlaps its inputs.  Joining rewrites the node to gemv_w4_decode3_kernel<.., Decode3GroupTable> with grid.y = members; no node is
-//     added and the stream's dependency set stays as it is.
+//     overlaps its inputs.  Joining rewrites the node to gemv_w4_decode3_kernel<.., Decode3GroupTable>, grid (tiles, Y) with
+//     Y = clamp(resident blocks / tiles, 1, members): one resident block per tile streams its members one after the other, narrow layers
+//     spread them over the CUs their tiles leave idle.  No node is added and the stream's dependency set stays as it is.
 //
 // The graph stays LINEAR on one queue.  Sound because nothing foreign lies between A and B on the stream: B's stream-order dependencies are
 // A plus A's own, and independence from A makes A's own sufficient; everything captured later depends on the group node and so on every
@@ -149,8 +150,9 @@ bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPla
 }
 
 // Called in front of every decode3 launch that carries no profile events.  true: the call was folded into the open group's node, nothing
-// is left to launch.  false: launch as always, then call capture_group_note_launch().
-bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st) {
+// is left to launch.  false: launch as always, then call capture_group_note_launch().  resident: blocks of a one-block-per-CU kernel
+// the stream's device holds at once (its CU count).
+bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident) {
     Group& g = tl_group;
     g.capturing = false;
     if (capture_group_limit() < 2 || (lp.d3.modes & 64u)) return false;
@@ -171,12 +173,15 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     Decode3Member& m = g.tab.m[g.members - 1];
     m.w = lp.d3.w; m.x = lp.d3.x; m.s = lp.d3.s; m.z = lp.d3.z; m.out = lp.d3.out;
     Decode3Args& d = g.lp.d3;
+    // the node as it is after this join: members and grid.y are recomputed every time and travel in `modes` (no implicit grid arguments)
+    const int members = g.members + 1, grid_y = decode3_group_grid_y(g.lp.grid.x, members, resident);
+    uint32_t modes = decode3_group_modes(d.modes, members, grid_y);
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
-                     (void*)&d.nch_total, (void*)&d.modes, (void*)&g.tab};
+                     (void*)&d.nch_total, (void*)&modes, (void*)&g.tab};
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
     np.func = (void*)g.fn_group;
-    np.gridDim = dim3(g.lp.grid.x, (unsigned)(g.members + 1), 1);
+    np.gridDim = dim3(g.lp.grid.x, (unsigned)grid_y, 1);
     np.blockDim = g.lp.block;
     np.sharedMemBytes = 0;
     np.kernelParams = kargs;

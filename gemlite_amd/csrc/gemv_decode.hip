@@ -33,16 +33,20 @@ __device__ __forceinline__ float dpp_movf(float v) {
 }
 
 // modes: bits 0..3 W_group_mode | 4 zero_is_scalar | 5 pair the half-line tiles on one XCD | 6 timeline probe | 8..15 log2(group)
+//        grouped launches only (capture_group.hip): 16..23 members | 24..31 grid.y
 constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
 
 }  // namespace dec3
 
 // Tail = unsigned*: the single-layer kernel, `counters` is the timeline buffer.
-// Tail = Decode3GroupTable: the GROUPED form — grid (N / 16, members), blockIdx.y selects one of up to DECODE3_GMAX independent layers of
-// identical shape, strides, modes and dtype (capture_group.hip folds back-to-back independent launches of a stream capture into one
-// such launch).  blockIdx.x stays fastest, so the chip streams layer 0, then layer 1, ...  Layer 0's pointers are the preloaded scalars;
-// the others come out of the by-value table behind the 14 dwords with scalar loads.  Everything after the pointer fetch is the
-// single-layer code, so every layer's output is bit-identical to its own launch.  No timeline probe in a group.
+// Tail = Decode3GroupTable: the GROUPED form — up to DECODE3_GMAX independent layers of identical shape, strides, modes and dtype
+// (capture_group.hip folds back-to-back independent launches of a stream capture into one such launch).  Grid (N / 16, Y): block
+// (tile, y) stays resident and STREAMS the layers y, y + Y, ... of its tile through a ring of DECODE3_RING chunk buffers, so wave start is
+// paid once per group and a layer's first-byte latency and reduce + store run under the following layers' stream (the comment at the
+// loop has the details).  Member count and Y come in `modes`.  Layer 0's pointers are the preloaded scalars; the others come out of
+// the by-value table behind the 14 dwords with scalar loads.  Per layer the arithmetic is the single-layer code in the same order, so
+// every layer's output is bit-identical to its own launch.  No timeline probe in a group.  The single-layer instantiation is untouched:
+// dependent chains, eager launches and profiled launches run it.
 template <typename Tag, bool NT, typename Tail = unsigned*>
 __global__ __launch_bounds__(1024, (std::is_same<Tail, Decode3GroupTable>::value ? DECODE3_GROUP_WAVES_PER_SIMD : 1))
 void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
@@ -50,18 +54,12 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
                             const Tail counters) {
     using namespace dec3;
     constexpr bool GROUPED = std::is_same<Tail, Decode3GroupTable>::value;
-    if constexpr (GROUPED) {
-        const int layer = (int)blockIdx.y;
-        if (layer > 0) {
-            const Decode3Member& m = counters.m[layer - 1];
-            wb = m.w; xb = m.x; sp = m.s; zp = m.z; out = m.out;
-        }
-    }
     using TR = F16Traits<Tag>;
     constexpr bool SUBN = TR::DT == GEMLITE_DT_FP16;
     constexpr int WP = SUBN ? 2 : 1;  // 4-bit fields per 16-bit window (Window<Tag, 4>::WP of gemv_wn.hip)
     constexpr int R = 2, NW = 16, CHUNK = 32, TC = 16, CSTRIDE = NW * CHUNK;
-    __shared__ __attribute__((aligned(16))) float red[NW * 4 * TC];  // [NW * 4 DPP rows][16 columns]
+    constexpr int RED = NW * 4 * TC;
+    __shared__ __attribute__((aligned(16))) float red[(GROUPED ? 2 : 1) * RED];  // [NW * 4 DPP rows][16 columns] (grouped: x layer parity)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -108,12 +106,15 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
     };
     stamp(0);
     Chunk cur, nxt;
-    if (nchunks > 0) load_chunk(cur, 0);
-    if (nchunks > 1) load_chunk(nxt, 1);
+    if constexpr (!GROUPED) {
+        if (nchunks > 0) load_chunk(cur, 0);
+        if (nchunks > 1) load_chunk(nxt, 1);
+    }
     stamp(1);
 
     float tot[4] = {0.f, 0.f, 0.f, 0.f};
-    const float scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
+    float scalar_zero = 0.f;  // (grouped: taken from the ring, per item)
+    if constexpr (!GROUPED) scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
     const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
     const bool b_times_s = w_mode == 3;
     constexpr float QSCALE = SUBN ? 16777216.0f : 1.0f;
@@ -168,40 +169,161 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             float v = acc[0][j];
             if constexpr (WP > 1) v = __builtin_fmaf(acc[WP - 1][j], 1.0f / 16.0f, v);
             if constexpr (!SUBN) v -= TR::OFF * xsum;
-            tot[j] += a * v + b * xsum;
+            // (spelled out: left to -ffp-contract, hipcc chose fma(b, xsum, a v) in one instantiation and fma(a, v, b xsum) in another,
+            // and a group's outputs must be bit-identical to the single-layer kernel's)
+            tot[j] += __builtin_fmaf(b, xsum, a * v);
         }
     };
+    if constexpr (!GROUPED) {
 #pragma unroll 1
-    for (int ch = 0; ch < nchunks; ++ch) {
-        compute(cur);
-        if (ch + 1 < nchunks) {
-            cur = nxt;
-            if (ch + 2 < nchunks) load_chunk(nxt, ch + 2);
+        for (int ch = 0; ch < nchunks; ++ch) {
+            compute(cur);
+            if (ch + 1 < nchunks) {
+                cur = nxt;
+                if (ch + 2 < nchunks) load_chunk(nxt, ch + 2);
+            }
+        }
+        stamp(2);
+
+        // ---- the 4 row sub-groups of every 16-lane DPP row (lane bits 2, 3): two rotations, every lane ends with the row's sum --
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float v = tot[j];
+            v += dpp_movf<0x124>(v);  // row_ror:4
+            v += dpp_movf<0x128>(v);  // row_ror:8
+            tot[j] = v;
+        }
+        if ((lane & 12) == 0) *(f32x4*)(red + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
+        __syncthreads();
+        if (wave == 0) {
+            constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
+            const int o = lane & 15, part = lane >> 4;
+            float v = 0.f;
+#pragma unroll
+            for (int r = 0; r < PER; ++r) v += red[(part * PER + r) * TC + o];
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            if (lane < 16) out[tile * TC + o] = TR::from_float(v);
+        }
+        stamp(3);
+    } else {
+        // One block streams the layers y, y + Y, ... of its 16-column tile.  A wave's work is the flattened sequence of (layer, chunk)
+        // items; it keeps DECODE3_RING chunk buffers and asks for item i + DECODE3_RING when it is done with item i, so block start is
+        // paid once per group and the first-byte latency of the next layers and the reduce + store of this one run under the stream.
+        // The item loop is unrolled by the ring depth.  The loads are hipcc's own.  What it makes of this: the
+        // waits in front of an item's arithmetic are counted and leave the newer items out; the request is hoisted to the START of the
+        // arithmetic into one more set of registers, and each trip of the unrolled loop ends in copies that rotate the sets behind one
+        // vmcnt(0).  (Requests from inline asm with counted waits met the same rotation, with copies of registers hipcc does not count.)
+        constexpr int D = DECODE3_RING;
+        const int members = (int)((modes >> 16) & 255u), Y = (int)(modes >> 24), y = (int)blockIdx.y;
+        // layer L: the preloaded scalars (L = 0) or the by-value table, scalar loads either way
+        auto fetch_in = [&](int L, const char*& w_, const char*& x_, const char*& s_, const char*& z_) {
+            if (L > 0) {
+                const Decode3Member& m = counters.m[L - 1];
+                w_ = m.w; x_ = m.x; s_ = m.s; z_ = m.z;
+            } else {
+                w_ = wb; x_ = xb; s_ = sp; z_ = zp;
+            }
+        };
+        // (a scalar zero point rides in the ring as well, in the `z` slot no mode with a scalar zero uses: the aligned 8 bytes that hold it
+        // — same page, cannot fault — and `zhi` says which half it is.  Waiting for a scalar load of it would stall every layer.)
+        auto fetch_out = [&](int L, uint16_t*& o_, bool& zhi) {
+            const char* z_ = zp;
+            o_ = out;
+            if (L > 0) {
+                const Decode3Member& m = counters.m[L - 1];
+                o_ = m.out; z_ = m.z;
+            }
+            zhi = ((uintptr_t)z_ & 4u) != 0;
+        };
+        // `live` = false: the sequence has ended; the request still goes out, to the first bytes of the last layer's buffers (one cached
+        // line each), so every item carries exactly one request
+        auto request = [&](Chunk& ck, const char* w_, const char* x_, const char* s_, const char* z_, int chunk, bool live) {
+            const uint32_t wo = wo0 + (uint32_t)(chunk * CSTRIDE) * sw4;
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const u32x4* src = (const u32x4*)(w_ + (live ? wo + (uint32_t)i * sw4 : 0u));
+                ck.w[i] = NT ? __builtin_nontemporal_load(src) : *src;
+            }
+            ck.xq = *(const u32x2*)(x_ + (live ? xo0 + (uint32_t)(chunk * CSTRIDE) * 16u : 0u));
+            const uint32_t row = row0 + (uint32_t)(chunk * CSTRIDE);
+            const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
+            const char* zs_ = (modes & M_ZSCALAR) ? z_ - ((uintptr_t)z_ & 7u) : w_;  // (pointer arithmetic: the address space stays global)
+            ck.s = *(const u32x2*)((need_s ? s_ : w_) + ((need_s && live) ? mo : 0u));
+            ck.z = *(const u32x2*)((need_z ? z_ : zs_) + ((need_z && live) ? mo : 0u));
+        };
+        // a layer's end, the single-layer code on LDS half `rd`: DPP row sums, partials to LDS, one barrier, wave 0 sums and stores
+        auto reduce_store = [&](float* rd, uint16_t* dst) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float v = tot[j];
+                v += dpp_movf<0x124>(v);  // row_ror:4
+                v += dpp_movf<0x128>(v);  // row_ror:8
+                tot[j] = v;
+            }
+            if ((lane & 12) == 0) *(f32x4*)(rd + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
+            __syncthreads();
+            if (wave == 0) {
+                constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
+                const int o = lane & 15, part = lane >> 4;
+                float v = 0.f;
+#pragma unroll
+                for (int r = 0; r < PER; ++r) v += rd[(part * PER + r) * TC + o];
+                v += __shfl_xor(v, 16);
+                v += __shfl_xor(v, 32);
+                if (lane < 16) dst[tile * TC + o] = TR::from_float(v);
+            }
+        };
+
+        uint16_t* lout;
+        bool zhi;
+        int par = 0;  // LDS half of the layer being summed: one barrier per layer is enough (a wave that writes half p again has passed
+                      // the barrier of the layer between, which wave 0 enters only after it has read half p)
+        if (nchunks == 0) {  // a wave without rows (K < 8192): zeros to the sum, and the barrier of every layer
+#pragma unroll 1
+            for (int L = y; L < members; L += Y, par ^= 1) {
+                fetch_out(L, lout, zhi);
+                reduce_store(red + par * RED, lout);
+            }
+            return;
+        }
+        // request cursor: runs D items ahead of the compute cursor
+        int rL = y, rch = 0;
+        const char *rw, *rx, *rs, *rz;
+        fetch_in(rL, rw, rx, rs, rz);
+        Chunk ring[D];
+        auto request_next = [&](Chunk& ck) {
+            request(ck, rw, rx, rs, rz, rch, rL < members);
+            if (++rch == nchunks) {  // the next layer's pointers: asked for one item before they are used
+                rch = 0;
+                rL += Y;
+                if (rL < members) fetch_in(rL, rw, rx, rs, rz);
+            }
+        };
+#pragma unroll
+        for (int b = 0; b < D; ++b) request_next(ring[b]);
+        int cL = y, cch = 0;
+        fetch_out(cL, lout, zhi);
+#pragma unroll 1
+        for (;;) {
+#pragma unroll
+            for (int b = 0; b < D; ++b) {
+                if (modes & M_ZSCALAR) scalar_zero = (float)(int32_t)(zhi ? ring[b].z[1] : ring[b].z[0]);
+                compute(ring[b]);
+                request_next(ring[b]);
+                if (++cch == nchunks) {
+                    reduce_store(red + par * RED, lout);
+                    cch = 0;
+                    par ^= 1;
+                    cL += Y;
+                    if (cL >= members) return;
+                    fetch_out(cL, lout, zhi);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) tot[j] = 0.f;
+                }
+            }
         }
     }
-    stamp(2);
-
-    // ---- the 4 row sub-groups of every 16-lane DPP row (lane bits 2, 3): two rotations, every lane ends with the row's sum --
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float v = tot[j];
-        v += dpp_movf<0x124>(v);  // row_ror:4
-        v += dpp_movf<0x128>(v);  // row_ror:8
-        tot[j] = v;
-    }
-    if ((lane & 12) == 0) *(f32x4*)(red + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
-    __syncthreads();
-    if (wave == 0) {
-        constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
-        const int o = lane & 15, part = lane >> 4;
-        float v = 0.f;
-#pragma unroll
-        for (int r = 0; r < PER; ++r) v += red[(part * PER + r) * TC + o];
-        v += __shfl_xor(v, 16);
-        v += __shfl_xor(v, 32);
-        if (lane < 16) out[tile * TC + o] = TR::from_float(v);
-    }
-    stamp(3);
 }
 
 // tag: 0 fp16 | 1 bf16

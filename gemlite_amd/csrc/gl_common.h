@@ -471,8 +471,9 @@ struct Decode3Args {
     unsigned* counters;
 };
 
-// gemv_w4_decode3_group_kernel (gemv_decode.hip): the pointers of layers 1 .. DECODE3_GMAX - 1 of a grouped launch, passed by value behind
-// the 14 preloaded dwords (layer 0's Decode3Args without `counters`).  sw4 / mstride2 / nch_total / modes are shared by the group.
+// gemv_w4_decode3_kernel<.., Decode3GroupTable> (gemv_decode.hip): the pointers of layers 1 .. DECODE3_GMAX - 1 of a grouped launch, passed
+// by value behind the 14 preloaded dwords (layer 0's Decode3Args without `counters`).  sw4 / mstride2 / nch_total / modes are shared by the
+// group; the member count and grid.y ride in bits 16..23 / 24..31 of `modes` (decode3_group_modes), which no single-layer launch sets.
 constexpr int DECODE3_GMAX = 16;
 struct Decode3Member {
     const char *w, *x, *s, *z;
@@ -481,11 +482,25 @@ struct Decode3Member {
 struct Decode3GroupTable {
     Decode3Member m[DECODE3_GMAX - 1];
 };
+inline uint32_t decode3_group_modes(uint32_t modes, int members, int grid_y) {
+    return (modes & 0xFFFFu) | ((uint32_t)members << 16) | ((uint32_t)grid_y << 24);
+}
+// grid.y of a grouped launch of `members` layers of `tiles` 16-column tiles each: block (tile, y) streams the layers y, y + grid.y, ...
+// one after the other.  One block per CU is resident, so a wide layer (tiles >= resident) gets one block per tile that walks every
+// member; a narrow one spreads its members over the CUs its tiles leave idle.
+inline int decode3_group_grid_y(int64_t tiles, int members, int64_t resident) {
+    const int64_t y = tiles > 0 ? resident / tiles : 1;
+    return (int)(y < 1 ? 1 : (y > members ? (members > 1 ? members : 1) : y));
+}
 // Waves per SIMD the compiler must keep resident for the grouped kernel (the second __launch_bounds__ argument of HIP).  One 1024-thread
-// block is 4 waves per SIMD; 8 = two blocks per CU, at most 64 VGPRs per lane (A/B builds only: profiles/r07/capture_groups.log has
-// why the shipped value is what it is)
+// block is 4 waves per SIMD = 128 VGPRs per lane (two blocks per CU, 64 VGPRs, spill: profiles/r07/capture_groups.log)
 #ifndef DECODE3_GROUP_WAVES_PER_SIMD
 #define DECODE3_GROUP_WAVES_PER_SIMD 4
+#endif
+// Chunk buffers per wave of the grouped kernel in the source: item i + DECODE3_RING is asked for when item i is done (hipcc adds one
+// more register set by hoisting that request).  2 and 3 were measured, 2 is the faster (profiles/r08/decode_group_stream.log §2).
+#ifndef DECODE3_RING
+#define DECODE3_RING 2
 #endif
 
 // scalar kernel arguments of gemm_w4_rows_kernel (gemm_wn_rows.hip): the same 14 preloaded dwords, then M and the row strides

@@ -327,10 +327,13 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
  * (read once per process) turns grouping off.
  *   _max         layers per grouped launch (1 = grouping is off)
  *   _stats       process-wide counts: decode launches seen under capture, and how many of them joined a node instead of adding one
- *   _compatible  host only, nothing is dereferenced: 1 if launch `b` captured directly behind launch `a` would join it, else 0 */
+ *   _compatible  host only, nothing is dereferenced: 1 if launch `b` captured directly behind launch `a` would join it, else 0
+ *   _grid_y      host only: the grid.y rule for a grouped launch of `members` layers of `tiles` 16-column tiles (N / 16), answered for
+ *                a full 256-CU part: clamp(256 / tiles, 1, members) (a launch uses its own device's CU count in place of 256); block (tile, y) streams the layers y, y + grid.y, ...  0 for a non-positive argument */
 int gemlite_hip_capture_group_max(void);
 void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
+int gemlite_hip_capture_group_grid_y(int32_t tiles, int32_t members);
 
 /* Per-token dynamic activation quantisation: for each row m of x[M,K] (fp16/bf16/fp32)
  *   s[m] = max(amax(|x[m,:]|) / qmax, 1e-6) (fp32);  y = clamp(x / s, qmin, qmax);
