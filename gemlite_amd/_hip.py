@@ -66,6 +66,18 @@ class ForwardArgs(C.Structure):
     ]
 
 
+class ForwardExt(C.Structure):
+    """struct gemlite_hip_forward_ext: the optional extension of a launch (a bias the kernel may add in its epilogue)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("bias_dtype", C.c_int32),
+        ("bias", C.c_void_p),
+    ]
+
+
+BIAS_NOT_ADDED = 1  # gemlite_hip_forward_ex: launched without the bias, the caller adds it
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -113,6 +125,15 @@ def load():
         lib.gemlite_hip_capture_group_compatible.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardArgs)]
         lib.gemlite_hip_capture_group_grid_y.restype = C.c_int
         lib.gemlite_hip_capture_group_grid_y.argtypes = [C.c_int32, C.c_int32]
+        lib.gemlite_hip_forward_ex.restype = C.c_int
+        lib.gemlite_hip_forward_ex.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.c_void_p]
+        lib.gemlite_hip_bias_fused.restype = C.c_int
+        lib.gemlite_hip_bias_fused.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt)]
+        lib.gemlite_hip_kernel_name_ex.restype = C.c_char_p
+        lib.gemlite_hip_kernel_name_ex.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt)]
+        lib.gemlite_hip_capture_group_compatible_ex.restype = C.c_int
+        lib.gemlite_hip_capture_group_compatible_ex.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.POINTER(ForwardArgs),
+                                                                 C.POINTER(ForwardExt)]
         lib.gemlite_hip_scale_activations_per_token.restype = C.c_int
         lib.gemlite_hip_scale_activations_per_token.argtypes = [
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
@@ -142,7 +163,16 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_unpack_over_cols",
     "gemlite_hip_capture_group_max", "gemlite_hip_capture_group_stats", "gemlite_hip_capture_group_compatible",
     "gemlite_hip_capture_group_grid_y",
+    "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
 )
+
+
+def forward_ext(bias_ptr: int, bias_dtype: int) -> ForwardExt:
+    e = ForwardExt()
+    e.struct_size = C.sizeof(ForwardExt)
+    e.bias_dtype = int(bias_dtype)
+    e.bias = bias_ptr
+    return e
 
 
 def status_string(code: int) -> str:

@@ -177,6 +177,10 @@ FUSE_ACT_QUANT_M1 = True  # decode of dynamically quantised layers: activation q
 # memory round trips (row load, write-through drain, flag, poll, first read of the quantised rows: 1-2 us each), a launch boundary
 # plus the 2.3-us quantiser is ~4 us — layer(x) measured 3.3-7 us SLOWER fused (profiles/r04/probe_fused_quant_v*.log).
 FUSE_ACT_QUANT_ROWS = False
+# A bias of the output's 16-bit type is added INSIDE the launch where the library's planner picked a kernel with a biased form (the M = 1
+# decode kernel, the 2 .. 64-row kernels): one launch instead of two, bit-identical, and independent biased layers of a stream capture join
+# one grouped launch.  False keeps `out += bias` behind every matmul and never asks the library (A/B runs, tests).
+FUSE_BIAS = True
 TUNING_OVERRIDE = None  # development hook: 4 ints forwarded as gemlite_hip_forward_args.tuning (0 = library default)
 
 # Per-layer launch templates.  A template is the IMMUTABLE byte image of a gemlite_hip_forward_args whose static
@@ -311,12 +315,13 @@ def _call_args(x: Tensor, W_q: Tensor, scales: Tensor, zeros: Tensor, scales_x: 
 
 
 def _hip_matmul(x: Tensor, W_q: Tensor, scales: Tensor, zeros: Tensor, scales_x: Optional[Tensor], meta_args,
-                matmul_type: int, tuning=None, raw_x: bool = False) -> Tensor:
+                matmul_type: int, tuning=None, raw_x: bool = False, bias: Optional[Tensor] = None) -> Tensor:
     """out[M, N] = epilogue(x[M, K] @ dequant(W_q)) — the seam the reference fills with
     GEMLITE_TRITON_MAPPING[...].forward (core.py:184-190).  ONE C call per launch: the library plans, carves the
     caller's per-stream workspace and launches; only if that workspace turns out too small is it regrown.
     raw_x: x holds the UNQUANTISED 16-bit rows of a dynamically quantised layer and the kernel quantises them itself (the caller
-    asked _library_quantises_inside first)."""
+    asked _library_quantises_inside first).
+    bias: added to the result, by the launch itself where the library does that (the caller asked _library_adds_bias first)."""
     lib = _hip.load()
     _hip.require_gpu_tensor(x, "x")
     _hip.require_gpu_tensor(W_q, "W_q")
@@ -331,12 +336,21 @@ def _hip_matmul(x: Tensor, W_q: Tensor, scales: Tensor, zeros: Tensor, scales_x:
         stream = _hip.current_stream_handle(x.device)
         ws = _hip.workspace(x.device, stream, 0)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        rc = lib.gemlite_hip_forward(_hip.C.byref(a), stream)
+        if bias is None:
+            launch = lambda: lib.gemlite_hip_forward(_hip.C.byref(a), stream)  # noqa: E731
+        else:
+            ext = _hip.forward_ext(bias.data_ptr(), TORCH_TO_DTYPE[bias.dtype].value)
+            launch = lambda: lib.gemlite_hip_forward_ex(_hip.C.byref(a), _hip.C.byref(ext), stream)  # noqa: E731
+        rc = launch()
         if rc == _hip.ERR_WORKSPACE:
             need = lib.gemlite_hip_workspace_bytes(_hip.C.byref(a))
             ws = _hip.workspace(x.device, stream, need)
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            rc = lib.gemlite_hip_forward(_hip.C.byref(a), stream)
+            rc = launch()
+    if rc == _hip.BIAS_NOT_ADDED:  # the launch ran without the bias (the cached answer missed a dependency): add it here, ask again next time
+        _FUSED_BIAS_ANSWERS.clear()
+        out += bias
+        rc = 0
     if rc != 0:
         _hip.raise_for_status(rc, "gemlite_hip_forward")
     # a shape that only the coverage kernel takes is correct but orders of magnitude slower: say so, once per shape
@@ -385,6 +399,34 @@ def _library_quantises_inside(x2: Tensor, W_q: Tensor, scales: Tensor, zeros: Te
         if len(_FUSED_QUANT_ANSWERS) >= 4096:
             _FUSED_QUANT_ANSWERS.clear()
         _FUSED_QUANT_ANSWERS[key] = ans
+    return ans
+
+
+# ---- bias inside the launch: the same scheme.  resolve() + apply_bias() in csrc/api.hip decide, gemlite_hip_bias_fused asks them on the
+# arguments the launch would carry; the answer is cached per layer / shape / alignment / bias type / tuning epoch.
+_FUSED_BIAS_ANSWERS: dict = {}
+
+
+def _library_adds_bias(x2: Tensor, W_q: Tensor, scales: Tensor, zeros: Tensor, bias: Tensor, meta_args, matmul_type: int) -> bool:
+    if not FUSE_BIAS or bias.dtype not in (torch.float16, torch.bfloat16) or bias.dim() != 1 or bias.shape[0] != W_q.shape[1] \
+            or not bias.is_contiguous() or bias.device != x2.device or x2.dtype != bias.dtype:
+        return False
+    M = x2.shape[0]
+    key = (tuple(meta_args), tuple(W_q.shape), W_q.stride(), W_q.dtype, W_q.data_ptr() & 15, scales.data_ptr() & 15, zeros.data_ptr() & 15,
+           tuple(scales.shape), scales.stride(), tuple(zeros.shape), zeros.stride(), M, x2.dtype, x2.stride(), x2.data_ptr() & 15,
+           x2.device.index, bias.dtype, bias.data_ptr() & 15, matmul_type, None if TUNING_OVERRIDE is None else tuple(TUNING_OVERRIDE),
+           _CACHE_EPOCH[0])
+    ans = _FUSED_BIAS_ANSWERS.get(key)
+    if ans is None:
+        if not _AUTOLOAD_DONE:
+            autoload_default_config(x2.device.index or 0)
+            key = key[:-1] + (_CACHE_EPOCH[0],)
+        a = _call_args(x2, W_q, scales, zeros, None, meta_args, matmul_type, None, False, 0x1000, (W_q.shape[1], 1))
+        ext = _hip.forward_ext(bias.data_ptr(), TORCH_TO_DTYPE[bias.dtype].value)
+        ans = _hip.load().gemlite_hip_bias_fused(_hip.C.byref(a), _hip.C.byref(ext)) == 1
+        if len(_FUSED_BIAS_ANSWERS) >= 4096:
+            _FUSED_BIAS_ANSWERS.clear()
+        _FUSED_BIAS_ANSWERS[key] = ans
     return ans
 
 
@@ -439,10 +481,12 @@ def _forward_impl(x: Tensor, bias: Optional[Tensor], tensor_args: List[Tensor], 
     x2 = x if x.dim() == 2 else x.view(-1, x.shape[-1])
     # matmul_type < 0 (auto) is resolved inside the library: the HIP kernel families have their own M
     # thresholds (GEMV <= 4 rows, streaming MFMA above), unlike the Triton ones of get_matmul_type()
-    out = _hip_matmul(x2, W_q, scales, zeros, scales_x, meta_args, matmul_type)
+    # a bias the planned kernel adds itself rides in the launch (weight-only 16-bit layers; FUSE_BIAS); every other one is added here
+    fused = bias is not None and FUSE_BIAS and scales_x is None and _library_adds_bias(x2, W_q, scales, zeros, bias, meta_args, matmul_type)
+    out = _hip_matmul(x2, W_q, scales, zeros, scales_x, meta_args, matmul_type, bias=bias if fused else None)
     if len(out_shape) != 2:
         out = out.view(out_shape)
-    if bias is not None:
+    if bias is not None and not fused:
         out += bias
     return out
 
@@ -688,13 +732,13 @@ class GemLiteLinearHIP(torch.nn.Module):
         d = self.__dict__
         f = d.get("_fast")
         if f is not None and TUNING_OVERRIDE is None and not torch.compiler.is_compiling():
-            y = _FAST.forward(f[0], f[1], f[2], f[3], x, f[4], -1, _CACHE_EPOCH[0])
+            y = _FAST.forward(f[0], f[1], f[2], f[3], x, f[4], -1, _CACHE_EPOCH[0], FUSE_BIAS)
             if y is NotImplemented:  # a tuning table is loaded and this M has not been looked up at this epoch yet
                 a = _static_args(f[1], f[2], f[3], self.get_meta_args())
                 M = x.numel() // max(1, x.shape[-1])
                 a.input_dtype = TORCH_TO_DTYPE[x.dtype].value
                 _FAST.set_tuning(f[0], M, lookup_tuning(-1, M, a))
-                y = _FAST.forward(f[0], f[1], f[2], f[3], x, f[4], -1, _CACHE_EPOCH[0])
+                y = _FAST.forward(f[0], f[1], f[2], f[3], x, f[4], -1, _CACHE_EPOCH[0], FUSE_BIAS)
             if y is False:  # the handle is stale (tensors moved, tuning table changed): rebuilt behind the slow call below
                 d["_fast"] = None
                 d["_fast_tried"] = None

@@ -79,6 +79,16 @@ const char* gl::pw_label(const char* name, int pack_bits) {
     return names->insert(s).first->c_str();
 }
 
+// kernel label of a form that adds the bias in its epilogue: ",bias" before the closing '>' (interned like the labels above)
+const char* gl::bias_label(const char* name) {
+    static std::mutex mu;
+    static std::set<std::string>* names = new std::set<std::string>();
+    std::string s(name);
+    s.insert(s.size() - 1, ",bias");
+    std::lock_guard<std::mutex> lock(mu);
+    return names->insert(s).first->c_str();
+}
+
 static thread_local int tl_last_hip_error = 0;
 static thread_local void* tl_evt_start = nullptr;
 static thread_local void* tl_evt_stop = nullptr;
@@ -901,6 +911,29 @@ static int ensure_lds(const void* fn, size_t lds, int dev) {
 
 __global__ void gemlite_noop_kernel() {}
 
+// gemlite_hip_forward_ext: 0 = usable (NULL: no extension), else a negative status
+static int validate_ext(const gemlite_hip_forward_ext* e) {
+    if (e && e->struct_size != sizeof(gemlite_hip_forward_ext)) return GEMLITE_ERR_BAD_ARGUMENT;
+    return GEMLITE_OK;
+}
+
+// The ONE place that decides whether the planned launch adds the caller's bias itself: the planner chose a kernel that has a biased form
+// (gemv_w4_decode3_kernel, gemm_w{4,2}_rows_kernel: LaunchPlan::fn_bias) and still runs it, the bias has the output's 16-bit type and is
+// 2-byte aligned (the kernels load single elements), and the launch is not a timeline probe (the biased decode form has no `counters`).
+// Then the plan is rewritten to the biased form: kernel, label, bias pointer.  Nothing is dereferenced.
+static bool apply_bias(const gemlite_hip_forward_args& a, const gemlite_hip_forward_ext* e, Resolved& r) {
+    if (!e || !e->bias || r.status != GEMLITE_OK) return false;
+    LaunchPlan& lp = r.lp;
+    if ((lp.arg_kind != 1 && lp.arg_kind != 2) || !lp.fn_bias || lp.fn != lp.bias_of) return false;
+    if (e->bias_dtype != a.output_dtype || (a.output_dtype != GEMLITE_DT_FP16 && a.output_dtype != GEMLITE_DT_BF16)) return false;
+    if (((uintptr_t)e->bias & 1u) != 0) return false;
+    if (lp.arg_kind == 1 && (lp.d3.modes & 64u)) return false;
+    lp.fn = lp.fn_bias;
+    lp.name = bias_label(lp.name);
+    lp.bias = (const uint16_t*)e->bias;
+    return true;
+}
+
 extern "C" {
 
 int gemlite_hip_abi_version(void) { return GEMLITE_HIP_ABI_VERSION; }
@@ -974,6 +1007,36 @@ int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, cons
     return capture_group_compatible(*a, ra.lp, *b, rb.lp) ? 1 : 0;
 }
 
+int gemlite_hip_bias_fused(const gemlite_hip_forward_args* args, const gemlite_hip_forward_ext* ext) {
+    const int v = validate(args);
+    if (v != GEMLITE_OK) return v;
+    if (validate_ext(ext) != GEMLITE_OK) return GEMLITE_ERR_BAD_ARGUMENT;
+    Resolved r;
+    resolve(*args, r);
+    if (r.status != GEMLITE_OK) return r.status;
+    return apply_bias(*args, ext, r) ? 1 : 0;
+}
+
+const char* gemlite_hip_kernel_name_ex(const gemlite_hip_forward_args* args, const gemlite_hip_forward_ext* ext) {
+    if (validate(args) != GEMLITE_OK || validate_ext(ext) != GEMLITE_OK) return "invalid";
+    Resolved r;
+    resolve(*args, r);
+    (void)apply_bias(*args, ext, r);
+    return r.status == GEMLITE_OK ? r.lp.name : "unsupported";
+}
+
+int gemlite_hip_capture_group_compatible_ex(const gemlite_hip_forward_args* a, const gemlite_hip_forward_ext* ea,
+                                             const gemlite_hip_forward_args* b, const gemlite_hip_forward_ext* eb) {
+    if (validate(a) != GEMLITE_OK || validate(b) != GEMLITE_OK || validate_ext(ea) != GEMLITE_OK || validate_ext(eb) != GEMLITE_OK) return 0;
+    Resolved ra, rb;
+    resolve(*a, ra);
+    resolve(*b, rb);
+    if (ra.status != GEMLITE_OK || rb.status != GEMLITE_OK) return 0;
+    (void)apply_bias(*a, ea, ra);
+    (void)apply_bias(*b, eb, rb);
+    return capture_group_compatible(*a, ra.lp, *b, rb.lp) ? 1 : 0;
+}
+
 int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream) {
     if (blocks <= 0 || threads <= 0 || threads > 1024) return GEMLITE_ERR_BAD_ARGUMENT;
     void* none[1] = {nullptr};
@@ -981,9 +1044,14 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream) {
                   (hipStream_t)stream);
 }
 
-int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) {
+static int launch_resolved(const gemlite_hip_forward_args* args, Resolved& r, int dev, int resident, hipStream_t st);
+
+int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) { return gemlite_hip_forward_ex(args, nullptr, stream); }
+
+int gemlite_hip_forward_ex(const gemlite_hip_forward_args* args, const gemlite_hip_forward_ext* ext, void* stream) {
     const int v = validate(args);
     if (v != GEMLITE_OK) return v;
+    if (validate_ext(ext) != GEMLITE_OK) return GEMLITE_ERR_BAD_ARGUMENT;
     int dev = 0;
     const int dv = check_device(&dev);  // (before planning: the planners ask for the device's CU count)
     Resolved r;
@@ -993,7 +1061,13 @@ int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) {
     tl_plan_dev = -1;
     if (r.status != GEMLITE_OK) return r.status;
     if (dv != GEMLITE_OK) return dv;
-    hipStream_t st = (hipStream_t)stream;
+    // a bias the launch does not add itself is left to the caller: the launch runs as without it and says so
+    const bool bias_left = ext && ext->bias && !apply_bias(*args, ext, r);
+    const int rc = launch_resolved(args, r, dev, resident, (hipStream_t)stream);
+    return (rc == GEMLITE_OK && bias_left) ? GEMLITE_BIAS_NOT_ADDED : rc;
+}
+
+static int launch_resolved(const gemlite_hip_forward_args* args, Resolved& r, int dev, int resident, hipStream_t st) {
     if (r.kind == K_GEMV_WN || r.kind == K_STREAM_WN || r.kind == K_TILED_WN) {
         if (r.lp.ws_bytes > 0) {
             if (!args->workspace || args->workspace_bytes < r.lp.ws_bytes) return GEMLITE_ERR_WORKSPACE;
@@ -1007,8 +1081,9 @@ int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) {
         if (r.lp.arg_kind == 1) {  // scalar (SGPR-preloaded) arguments: gemv_decode.hip
             Decode3Args& d = r.lp.d3;
             d.counters = r.wn.counters;
+            Decode3BiasTail btail{r.lp.bias};  // (the biased form: the bias pointer in the place of `counters`)
             void* dargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
-                             (void*)&d.nch_total, (void*)&d.modes, (void*)&d.counters};
+                             (void*)&d.nch_total, (void*)&d.modes, r.lp.bias ? (void*)&btail : (void*)&d.counters};
             // under stream capture an independent neighbour joins the node of the launch before it (capture_group.hip); a launch with
             // profile events or the timeline probe is always its own
             const bool plain = tl_evt_start || tl_evt_stop;
@@ -1020,7 +1095,7 @@ int gemlite_hip_forward(const gemlite_hip_forward_args* args, void* stream) {
         if (r.lp.arg_kind == 2) {  // gemm_wn_rows.hip
             Rows5Args& d = r.lp.r5;
             void* dargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
-                             (void*)&d.nch_total, (void*)&d.modes, (void*)&d.M, (void*)&d.sxm2, (void*)&d.som};
+                             (void*)&d.nch_total, (void*)&d.modes, (void*)&d.M, (void*)&d.sxm2, (void*)&d.som, (void*)&r.lp.bias};  // (bias: the biased form only)
             return launch(r.lp.fn, r.lp.grid, r.lp.block, dargs, r.lp.lds_bytes, st);
         }
         void* kargs[] = {(void*)&r.wn};

@@ -9,7 +9,7 @@
 //   * a decode3 launch under capture that cannot join is launched as always, and the node it became opens a group of one;
 //   * the next decode3 launch joins the open group when NOTHING else was captured on the stream since (the stream's only dependency is the
 //     group's node), kernel / shape / strides / modes agree, and its output overlaps no member's inputs or output and no member's output
-//     overlaps its inputs.  Joining rewrites the node to gemv_w4_decode3_kernel<.., Decode3GroupTable>, grid (tiles, Y) with
+//     overlaps its inputs (a bias the kernel adds itself — gemlite_hip_forward_ext — is one more input).  Joining rewrites the node to gemv_w4_decode3_kernel<.., Decode3GroupTable>, grid (tiles, Y) with
 //     Y = clamp(resident blocks / tiles, 1, members): one resident block per tile streams its members one after the other, narrow layers
 //     spread them over the CUs their tiles leave idle.  No node is added and the stream's dependency set stays as it is.
 //
@@ -29,6 +29,8 @@ namespace gl {
 
 const void* gemv_w4_decode3_fn(int tag, bool nt);        // gemv_decode.hip
 const void* gemv_w4_decode3_group_fn(int tag, bool nt);  // gemv_decode.hip
+const void* gemv_w4_decode3_bias_fn(int tag, bool nt);        // the forms that add a bias in the epilogue: a group holds one kind only
+const void* gemv_w4_decode3_bias_group_fn(int tag, bool nt);  // (the kernel functions differ, so same_launch() keeps them apart)
 
 namespace {
 
@@ -36,7 +38,7 @@ struct Span {  // bytes [lo, hi); empty when lo == hi
     uintptr_t lo, hi;
 };
 struct Footprint {
-    Span rd[4];  // x, W_q, scales, zeros
+    Span rd[5];  // x, W_q, scales, zeros, bias (empty unless the launch adds one)
     Span wr;     // out
 };
 
@@ -60,7 +62,7 @@ Span span2d(const void* p, int64_t esz, int64_t n0, int64_t s0, int64_t n1, int6
 
 // Everything one decode3 launch may touch, from the caller's pointers, shapes and strides (never less than the kernel reads or writes:
 // metadata pointers count whenever they are given, whether the mode reads them or not)
-Footprint footprint(const gemlite_hip_forward_args& a) {
+Footprint footprint(const gemlite_hip_forward_args& a, const LaunchPlan& lp) {
     Footprint f;
     const int64_t e = a.elements_per_sample > 0 ? a.elements_per_sample : 1, gs = a.group_size > 0 ? a.group_size : 1;
     f.rd[0] = span2d(a.x, elt_bytes(a.input_dtype), a.M, a.stride_xm, a.K, a.stride_xk);
@@ -68,13 +70,14 @@ Footprint footprint(const gemlite_hip_forward_args& a) {
     f.rd[2] = span2d(a.scales, elt_bytes(a.meta_dtype), (a.K + gs - 1) / gs, a.stride_meta_g, a.N, a.stride_meta_n);
     f.rd[3] = a.zero_is_scalar ? span2d(a.zeros, 8, 1, 0, 1, 0)
                                : span2d(a.zeros, elt_bytes(a.zeros_dtype), (a.K + gs - 1) / gs, a.stride_meta_g, a.N, a.stride_meta_n);
+    f.rd[4] = span2d(lp.bias, 2, 1, 0, a.N, 1);
     f.wr = span2d(a.out, elt_bytes(a.output_dtype), a.M, a.stride_om, a.N, a.stride_on);
     return f;
 }
 
 bool independent(const Footprint& a, const Footprint& b) {
     if (overlap(a.wr, b.wr)) return false;
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 5; ++i)
         if (overlap(b.wr, a.rd[i]) || overlap(a.wr, b.rd[i])) return false;
     return true;
 }
@@ -90,6 +93,9 @@ const void* group_fn_of(const void* fn) {
     for (int tag = 0; tag < 2; ++tag)
         for (int nt = 0; nt < 2; ++nt)
             if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_fn(tag, nt != 0);
+    for (int tag = 0; tag < 2; ++tag)
+        for (int nt = 0; nt < 2; ++nt)
+            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_bias_group_fn(tag, nt != 0);
     return nullptr;
 }
 
@@ -109,6 +115,7 @@ struct Group {
     LaunchPlan lp{};  // member 0: kernel, grid, block, scalars
     const void* fn_group = nullptr;
     Decode3GroupTable tab{};
+    Decode3BiasGroupTable tabb{};  // the table of a biased group (lp.bias set) instead of `tab`
     Footprint fp[DECODE3_GMAX];
     int members = 0;
 };
@@ -146,7 +153,7 @@ void capture_group_stats(uint64_t* seen, uint64_t* joined) {
 
 // The host-only rule: may launch B (args b, plan lb) run in the same grouped launch as A?
 bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPlan& la, const gemlite_hip_forward_args& b, const LaunchPlan& lb) {
-    return same_launch(la, lb) && group_fn_of(la.fn) != nullptr && independent(footprint(a), footprint(b));
+    return same_launch(la, lb) && group_fn_of(la.fn) != nullptr && independent(footprint(a, la), footprint(b, lb));
 }
 
 // Called in front of every decode3 launch that carries no profile events.  true: the call was folded into the open group's node, nothing
@@ -167,17 +174,19 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     g_seen.fetch_add(1, std::memory_order_relaxed);
     if (!g.open || g.cap_id != id || g.graph != graph || !dep || dep != g.node || g.members >= capture_group_limit() || !same_launch(g.lp, lp))
         return false;
-    const Footprint fb = footprint(a);
+    const Footprint fb = footprint(a, lp);
     for (int i = 0; i < g.members; ++i)
         if (!independent(g.fp[i], fb)) return false;
-    Decode3Member& m = g.tab.m[g.members - 1];
+    const bool biased = g.lp.bias != nullptr;  // (lp.bias too: same_launch() compared the kernel functions)
+    Decode3Member& m = biased ? g.tabb.m[g.members - 1] : g.tab.m[g.members - 1];
+    if (biased) g.tabb.bias[g.members] = lp.bias;
     m.w = lp.d3.w; m.x = lp.d3.x; m.s = lp.d3.s; m.z = lp.d3.z; m.out = lp.d3.out;
     Decode3Args& d = g.lp.d3;
     // the node as it is after this join: members and grid.y are recomputed every time and travel in `modes` (no implicit grid arguments)
     const int members = g.members + 1, grid_y = decode3_group_grid_y(g.lp.grid.x, members, resident);
     uint32_t modes = decode3_group_modes(d.modes, members, grid_y);
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
-                     (void*)&d.nch_total, (void*)&modes, (void*)&g.tab};
+                     (void*)&d.nch_total, (void*)&modes, biased ? (void*)&g.tabb : (void*)&g.tab};
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
     np.func = (void*)g.fn_group;
@@ -218,7 +227,9 @@ void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPl
     g.lp = lp;
     g.fn_group = fn_group;
     memset(&g.tab, 0, sizeof(g.tab));
-    g.fp[0] = footprint(a);
+    memset(&g.tabb, 0, sizeof(g.tabb));
+    g.tabb.bias[0] = lp.bias;
+    g.fp[0] = footprint(a, lp);
     g.members = 1;
     g.open = true;
 }

@@ -47,13 +47,21 @@ constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
 // the by-value table behind the 14 dwords with scalar loads.  Per layer the arithmetic is the single-layer code in the same order, so
 // every layer's output is bit-identical to its own launch.  No timeline probe in a group.  The single-layer instantiation is untouched:
 // dependent chains, eager launches and profiled launches run it.
+// Tail = Decode3BiasTail / Decode3BiasGroupTable: the same two forms with the bias add in the epilogue (gl_common.h has the arithmetic).
+// The lanes of wave 0 that store ask for their bias element in front of the layer's barrier, so it arrives under the reduction.
+template <typename Tail>
+struct Decode3TailKind {
+    static constexpr bool grouped = std::is_same<Tail, Decode3GroupTable>::value || std::is_same<Tail, Decode3BiasGroupTable>::value;
+    static constexpr bool biased = std::is_same<Tail, Decode3BiasTail>::value || std::is_same<Tail, Decode3BiasGroupTable>::value;
+};
+
 template <typename Tag, bool NT, typename Tail = unsigned*>
-__global__ __launch_bounds__(1024, (std::is_same<Tail, Decode3GroupTable>::value ? DECODE3_GROUP_WAVES_PER_SIMD : 1))
+__global__ __launch_bounds__(1024, (Decode3TailKind<Tail>::grouped ? DECODE3_GROUP_WAVES_PER_SIMD : 1))
 void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
                             uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
                             const Tail counters) {
     using namespace dec3;
-    constexpr bool GROUPED = std::is_same<Tail, Decode3GroupTable>::value;
+    constexpr bool GROUPED = Decode3TailKind<Tail>::grouped, BIASED = Decode3TailKind<Tail>::biased;
     using TR = F16Traits<Tag>;
     constexpr bool SUBN = TR::DT == GEMLITE_DT_FP16;
     constexpr int WP = SUBN ? 2 : 1;  // 4-bit fields per 16-bit window (Window<Tag, 4>::WP of gemv_wn.hip)
@@ -97,7 +105,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
     // opt-in timeline (GEMLITE_TF_TIMELINE): the mode bit is a preloaded SGPR, so a normal launch never touches `counters` (the one
     // argument behind the preloaded 14 dwords) and never waits for a kernarg load
     auto stamp = [&](int i) {
-        if constexpr (!GROUPED) {
+        if constexpr (!GROUPED && !BIASED) {
             if (__builtin_expect((modes & M_PROBE) != 0u, 0)) {
                 if (counters && wave == 0 && lane == 0 && blockIdx.x < 1024)
                     ((unsigned long long*)(counters + MAX_SPLITK_COUNTERS))[blockIdx.x * 4 + i] = __builtin_amdgcn_s_memrealtime();
@@ -184,6 +192,10 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             }
         }
         stamp(2);
+        uint16_t braw = 0;
+        if constexpr (BIASED) {
+            if (wave == 0 && lane < 16) braw = counters.bias[tile * TC + lane];
+        }
 
         // ---- the 4 row sub-groups of every 16-lane DPP row (lane bits 2, 3): two rotations, every lane ends with the row's sum --
 #pragma unroll
@@ -203,7 +215,10 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             for (int r = 0; r < PER; ++r) v += red[(part * PER + r) * TC + o];
             v += __shfl_xor(v, 16);
             v += __shfl_xor(v, 32);
-            if (lane < 16) out[tile * TC + o] = TR::from_float(v);
+            uint16_t h = TR::from_float(v);
+            // (two roundings, as the matmul launch followed by torch's add has them; a sum of two converted values: nothing to contract)
+            if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));
+            if (lane < 16) out[tile * TC + o] = h;
         }
         stamp(3);
     } else {
@@ -227,13 +242,14 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         };
         // (a scalar zero point rides in the ring as well, in the `z` slot no mode with a scalar zero uses: the aligned 8 bytes that hold it
         // — same page, cannot fault — and `zhi` says which half it is.  Waiting for a scalar load of it would stall every layer.)
-        auto fetch_out = [&](int L, uint16_t*& o_, bool& zhi) {
+        auto fetch_out = [&](int L, uint16_t*& o_, const uint16_t*& b_, bool& zhi) {
             const char* z_ = zp;
             o_ = out;
             if (L > 0) {
                 const Decode3Member& m = counters.m[L - 1];
                 o_ = m.out; z_ = m.z;
             }
+            if constexpr (BIASED) b_ = counters.bias[L];
             zhi = ((uintptr_t)z_ & 4u) != 0;
         };
         // `live` = false: the sequence has ended; the request still goes out, to the first bytes of the last layer's buffers (one cached
@@ -253,7 +269,11 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             ck.z = *(const u32x2*)((need_z ? z_ : zs_) + ((need_z && live) ? mo : 0u));
         };
         // a layer's end, the single-layer code on LDS half `rd`: DPP row sums, partials to LDS, one barrier, wave 0 sums and stores
-        auto reduce_store = [&](float* rd, uint16_t* dst) {
+        auto reduce_store = [&](float* rd, uint16_t* dst, const uint16_t* bsrc) {
+            uint16_t braw = 0;
+            if constexpr (BIASED) {
+                if (wave == 0 && lane < 16) braw = bsrc[tile * TC + lane];
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float v = tot[j];
@@ -271,19 +291,22 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
                 for (int r = 0; r < PER; ++r) v += rd[(part * PER + r) * TC + o];
                 v += __shfl_xor(v, 16);
                 v += __shfl_xor(v, 32);
-                if (lane < 16) dst[tile * TC + o] = TR::from_float(v);
+                uint16_t h = TR::from_float(v);
+                if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));  // (as in the single-layer form)
+                if (lane < 16) dst[tile * TC + o] = h;
             }
         };
 
         uint16_t* lout;
+        const uint16_t* lbias = nullptr;
         bool zhi;
         int par = 0;  // LDS half of the layer being summed: one barrier per layer is enough (a wave that writes half p again has passed
                       // the barrier of the layer between, which wave 0 enters only after it has read half p)
         if (nchunks == 0) {  // a wave without rows (K < 8192): zeros to the sum, and the barrier of every layer
 #pragma unroll 1
             for (int L = y; L < members; L += Y, par ^= 1) {
-                fetch_out(L, lout, zhi);
-                reduce_store(red + par * RED, lout);
+                fetch_out(L, lout, lbias, zhi);
+                reduce_store(red + par * RED, lout, lbias);
             }
             return;
         }
@@ -303,7 +326,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
 #pragma unroll
         for (int b = 0; b < D; ++b) request_next(ring[b]);
         int cL = y, cch = 0;
-        fetch_out(cL, lout, zhi);
+        fetch_out(cL, lout, lbias, zhi);
 #pragma unroll 1
         for (;;) {
 #pragma unroll
@@ -312,12 +335,12 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
                 compute(ring[b]);
                 request_next(ring[b]);
                 if (++cch == nchunks) {
-                    reduce_store(red + par * RED, lout);
+                    reduce_store(red + par * RED, lout, lbias);
                     cch = 0;
                     par ^= 1;
                     cL += Y;
                     if (cL >= members) return;
-                    fetch_out(cL, lout, zhi);
+                    fetch_out(cL, lout, lbias, zhi);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) tot[j] = 0.f;
                 }
@@ -338,6 +361,20 @@ const void* gemv_w4_decode3_group_fn(int tag, bool nt) {
     typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3GroupTable);
     kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true, Decode3GroupTable> : gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTable>)
                      : (nt ? gemv_w4_decode3_kernel<bf16_tag, true, Decode3GroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTable>);
+    return (const void*)k;
+}
+
+const void* gemv_w4_decode3_bias_fn(int tag, bool nt) {
+    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3BiasTail);
+    kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true, Decode3BiasTail> : gemv_w4_decode3_kernel<half_tag, false, Decode3BiasTail>)
+                     : (nt ? gemv_w4_decode3_kernel<bf16_tag, true, Decode3BiasTail> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3BiasTail>);
+    return (const void*)k;
+}
+
+const void* gemv_w4_decode3_bias_group_fn(int tag, bool nt) {
+    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3BiasGroupTable);
+    kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true, Decode3BiasGroupTable> : gemv_w4_decode3_kernel<half_tag, false, Decode3BiasGroupTable>)
+                     : (nt ? gemv_w4_decode3_kernel<bf16_tag, true, Decode3BiasGroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3BiasGroupTable>);
     return (const void*)k;
 }
 

@@ -34,6 +34,7 @@
 namespace gl {
 
 const void* gemv_w4_decode3_fn(int tag, bool nt);  // gemv_decode.hip
+const void* gemv_w4_decode3_bias_fn(int tag, bool nt);
 
 // Round 6 ("GEMV family onto counted asm loads"): the chunk requests of gemv_wn_kernel are inline-asm global loads
 // retired with hand-counted s_waitcnt (gl_async.h has the reasoning; scripts/isa_asmloads.py replays the generated code).  With the loads
@@ -1026,6 +1027,8 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
                 lp.arg_kind = 1;
                 lp.fn = gemv_w4_decode3_fn(f16 ? 0 : 1, nt);
                 lp.name = "gemv_w4_decode3_kernel<tile16,16w>";
+                lp.bias_of = lp.fn;
+                lp.fn_bias = gemv_w4_decode3_bias_fn(f16 ? 0 : 1, nt);
                 lp.lds_bytes = 0;  // static LDS
                 lp.d3.w = (const char*)p.w;
                 lp.d3.x = (const char*)p.x;

@@ -460,6 +460,8 @@ enum { MX_F16 = 1, MX_BF16 = 2, MX_FP8 = 3, MX_FP4 = 4 };
 int resident_block_limit();
 // kernel label of a form for 8- / 16-bit packed words (pack_bits 8 / 16): `name` with ",b8" / ",b16" before its closing '>' (api.hip)
 const char* pw_label(const char* name, int pack_bits);
+// kernel label of a form that adds the bias in its epilogue: `name` with ",bias" before its closing '>' (api.hip)
+const char* bias_label(const char* name);
 
 // scalar kernel arguments of gemv_w4_decode3_kernel (gemv_decode.hip): 14 dwords the command processor preloads into SGPRs
 struct Decode3Args {
@@ -481,6 +483,16 @@ struct Decode3Member {
 };
 struct Decode3GroupTable {
     Decode3Member m[DECODE3_GMAX - 1];
+};
+// The BIASED forms (out = from_float(to_float(from_float(acc)) + to_float(bias[n])): both roundings of "matmul, then out += bias" kept).  The
+// bias pointer travels behind the 14 preloaded dwords like `counters` (a biased launch never carries the timeline probe); a biased group
+// holds one bias pointer per member, layer 0's included.  A group is all-biased or all-unbiased: the kernel functions differ.
+struct Decode3BiasTail {
+    const uint16_t* bias;
+};
+struct Decode3BiasGroupTable {
+    Decode3Member m[DECODE3_GMAX - 1];
+    const uint16_t* bias[DECODE3_GMAX];
 };
 inline uint32_t decode3_group_modes(uint32_t modes, int members, int grid_y) {
     return (modes & 0xFFFFu) | ((uint32_t)members << 16) | ((uint32_t)grid_y << 24);
@@ -524,6 +536,11 @@ struct LaunchPlan {
     int arg_kind;         // 0: the kernel takes its parameter struct by value | 1: the scalar arguments of `d3` | 2: those of `r5`
     Decode3Args d3;
     Rows5Args r5;
+    // the form of `bias_of` that adds a 16-bit bias[N] of the output's type in its epilogue (decode3 and rows kernels only; api.hip swaps
+    // it in when the caller's gemlite_hip_forward_ext qualifies and `fn` is still `bias_of`), and the bias pointer once it has
+    const void* fn_bias = nullptr;
+    const void* bias_of = nullptr;
+    const uint16_t* bias = nullptr;
 };
 
 }  // namespace gl

@@ -134,10 +134,10 @@ PyObject* fast_set_tuning(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
     Py_RETURN_NONE;
 }
 
-// forward(handle, W_q, scales, zeros, x, bias | None, matmul_type, epoch) -> Tensor | None (this call: take the Python path) | False (the
+// forward(handle, W_q, scales, zeros, x, bias | None, matmul_type, epoch[, fuse_bias = False]) -> Tensor | None (this call: take the Python path) | False (the
 // handle is stale: rebuild it) | NotImplemented (the tuning of this M is not known yet: call set_tuning and retry)
 PyObject* fast_forward(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
-    if (nargs != 8) { PyErr_SetString(PyExc_TypeError, "forward(handle, W_q, scales, zeros, x, bias, matmul_type, epoch)"); return nullptr; }
+    if (nargs != 8 && nargs != 9) { PyErr_SetString(PyExc_TypeError, "forward(handle, W_q, scales, zeros, x, bias, matmul_type, epoch[, fuse_bias])"); return nullptr; }
     auto* L = (FastLayer*)PyCapsule_GetPointer(args[0], CAPSULE);
     if (!L) return nullptr;
     if (!THPVariable_Check(args[1]) || !THPVariable_Check(args[2]) || !THPVariable_Check(args[3]) || !THPVariable_Check(args[4])) Py_RETURN_NONE;
@@ -184,6 +184,19 @@ PyObject* fast_forward(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
     a.stride_om = a.N;
     a.stride_on = 1;
     void* stream = (void*)c10::hip::getCurrentHIPStream(L->dev).stream();
+    // fuse_bias (core.FUSE_BIAS): a contiguous [N] bias of the output's 16-bit type goes down with the launch.  The library plans once per
+    // call anyway, so its status IS the answer: GEMLITE_OK = the kernel added it, GEMLITE_BIAS_NOT_ADDED = it ran without and the add
+    // below follows, as for every bias that does not qualify here.
+    gemlite_hip_forward_ext ext{};
+    const gemlite_hip_forward_ext* extp = nullptr;
+    if (bias.defined() && nargs == 9 && PyObject_IsTrue(args[8]) == 1 && bias.is_cuda() && (int)bias.device().index() == L->dev &&
+        bias.dim() == 1 && bias.size(0) == a.N && bias.is_contiguous() && bias.scalar_type() == L->out_dtype &&
+        (L->out_dtype == at::kHalf || L->out_dtype == at::kBFloat16) && !bias.requires_grad()) {
+        ext.struct_size = sizeof(ext);
+        ext.bias_dtype = a.output_dtype;
+        ext.bias = bias.data_ptr();
+        extp = &ext;
+    }
     int rc;
     {
         // thread-local view of the last workspace: no lock on the steady path.  It holds the TENSOR (a reference), not just its pointer,
@@ -202,7 +215,7 @@ PyObject* fast_forward(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
         }
         a.workspace = tl_ptr;
         a.workspace_bytes = tl_bytes;
-        rc = gemlite_hip_forward(&a, stream);
+        rc = gemlite_hip_forward_ex(&a, extp, stream);
         if (rc == GEMLITE_ERR_WORKSPACE) {
             const uint64_t need = gemlite_hip_workspace_bytes(&a);
             tl_ws = workspace_for(L->dev, stream, need);
@@ -211,11 +224,11 @@ PyObject* fast_forward(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
             tl_ptr = ws.data_ptr(); tl_bytes = (uint64_t)ws.numel();
             a.workspace = tl_ptr;
             a.workspace_bytes = tl_bytes;
-            rc = gemlite_hip_forward(&a, stream);
+            rc = gemlite_hip_forward_ex(&a, extp, stream);
         }
     }
-    if (rc != GEMLITE_OK) Py_RETURN_NONE;  // the Python path repeats the call and raises the reference's exception class
-    if (bias.defined()) out.add_(bias);
+    if (rc != GEMLITE_OK && !(extp && rc == GEMLITE_BIAS_NOT_ADDED)) Py_RETURN_NONE;  // the Python path repeats the call and raises the reference's exception class
+    if (bias.defined() && !(extp && rc == GEMLITE_OK)) out.add_(bias);
     return THPVariable_Wrap(std::move(out));
 }
 

@@ -335,6 +335,32 @@ void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
 int gemlite_hip_capture_group_grid_y(int32_t tiles, int32_t members);
 
+/* Bias in the launch (optional extension; gemlite_hip_forward_args and every entry point above are unchanged).  The M = 1 decode kernel
+ * (gemv_w4_decode3_kernel, single and grouped) and the few-row kernels (gemm_w4_rows_kernel / gemm_w2_rows_kernel) have forms that add a
+ * bias[N] in their epilogue:   out[m, n] = round16( float(round16(acc[m, n])) + float(bias[n]) )   — both roundings of "matmul, then
+ * out += bias", so the result is bit-identical to the two launches.  The bias is fused when it is a contiguous [N] vector of the OUTPUT's
+ * dtype (fp16 / bf16), at least 2-byte aligned, and the planner chose one of those kernels for `args` (not a GEMLITE_TF_TIMELINE launch).
+ *   gemlite_hip_forward_ex    with ext == NULL or ext->bias == NULL exactly gemlite_hip_forward.  Otherwise it NEVER fails because of
+ *                             the bias: it returns GEMLITE_OK when the launch added it, and GEMLITE_BIAS_NOT_ADDED (a positive status)
+ *                             when the launch ran WITHOUT it and the caller has to add it (out += bias); negative statuses as ever.
+ *   gemlite_hip_bias_fused    host only, launches and dereferences nothing: 1 = the launch planned for (args, ext) adds the bias itself,
+ *                             0 = the caller must add it (also for ext == NULL / no bias), negative = bad arguments / no kernel
+ *   gemlite_hip_kernel_name_ex   the kernel of (args, ext); a biased form carries ",bias" before the closing '>' of its label
+ *   gemlite_hip_capture_group_compatible_ex   the capture-group rule for two (args, ext) pairs: a fused bias is one more READ span of
+ *                             its launch (an output that overlaps another member's bias does not join, in either order), and a biased
+ *                             and an unbiased launch never share a group.  gemlite_hip_capture_group_compatible(a, b) = both ext NULL. */
+typedef struct gemlite_hip_forward_ext {
+    uint32_t struct_size; /* sizeof(gemlite_hip_forward_ext), ABI guard */
+    int32_t bias_dtype;   /* gemlite_hip_dtype code of bias                */
+    const void* bias;     /* [N] contiguous, device memory, or NULL        */
+} gemlite_hip_forward_ext;
+#define GEMLITE_BIAS_NOT_ADDED 1
+int gemlite_hip_forward_ex(const gemlite_hip_forward_args* args, const gemlite_hip_forward_ext* ext, void* stream);
+int gemlite_hip_bias_fused(const gemlite_hip_forward_args* args, const gemlite_hip_forward_ext* ext);
+const char* gemlite_hip_kernel_name_ex(const gemlite_hip_forward_args* args, const gemlite_hip_forward_ext* ext);
+int gemlite_hip_capture_group_compatible_ex(const gemlite_hip_forward_args* a, const gemlite_hip_forward_ext* ea,
+                                             const gemlite_hip_forward_args* b, const gemlite_hip_forward_ext* eb);
+
 /* Per-token dynamic activation quantisation: for each row m of x[M,K] (fp16/bf16/fp32)
  *   s[m] = max(amax(|x[m,:]|) / qmax, 1e-6) (fp32);  y = clamp(x / s, qmin, qmax);
  *   int8: round half away from zero;  fp8: round-to-nearest-even cast.
