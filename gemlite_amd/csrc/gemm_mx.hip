@@ -42,11 +42,17 @@ __device__ __forceinline__ float e8m0_to_float(uint32_t b) {  // 2^(b - 127); 0 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // activation quantisers.  MODE 0: MXFP8 (e4m3 elements), 1: MXFP4 (e2m1 codes, two per byte), 2: NVFP4 (e2m1 codes, e4m3
-// scale per 16 k, meta scale 0.05).  Arithmetic of the reference kernels, operation by operation:
+// scale per 16 k, meta scale 0.05).  Arithmetic of the reference kernels, operation by operation for every finite block (a block
+// that holds a NaN or an Inf departs from the reference on purpose, see below):
 //   MX:  s = 2^ceil(log2(amax / qmax)) through the exponent bits (next_power_of_2_bitwise_triton, quant_utils.py:383-392),
 //        exponent clamped to [127 - 30, 254];  q = x / s  (clamped to +-448 and rounded to nearest even for fp8)
 //   fp4: code = #{thresholds 0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5, 7 below |q|}, + 8 when q < 0  (quant_utils.py:800-802)
 //   NV:  s8 = e4m3(min(amax / (6 * 0.05), 448));  q = x / max(float(s8) * 0.05, 1e-6)       (quant_utils.py:893-900)
+// Deliberate departure from the reference: a block that holds a NaN or an Inf gets the scale format's NaN code (e8m0 0xFF, e4m3
+// 0x7F).  The reference's bit-twiddled exponent clamps to 254 and its NVFP4 scale to 448, which returns a finite row wherever the
+// weight facing the Inf is zero (and fminf drops a NaN altogether); the scaled MFMA and the software decoders turn the NaN code into a
+// non-finite product, so the row shows what it was fed (absmax16_* / amax_not_finite, gl_common.h; finite blocks are bit for bit
+// what they were).
 // Rows M .. M_pad - 1 of the scale tensor (the reference pads M to a multiple of the group size and its programs store
 // the scale of an all-zero block there) are written with that value; no element output exists for them.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -60,13 +66,13 @@ __device__ __forceinline__ uint8_t mx_quant_block(const float (&v)[MODE == 2 ? 1
     uint8_t sb;
     if (MODE == 2) {
         const float s32 = fminf(__fdiv_rn(amax, 0.3f), 448.f);  // 6 * 0.05 folded to the fp32 constant 0.3f
-        sb = float_to_fp8e4m3(s32);
+        sb = amax_not_finite(amax) ? (uint8_t)0x7F : float_to_fp8e4m3(s32);  // (fminf drops a NaN, and 448 would hide an Inf: e4m3's NaN)
         s = fmaxf(fp8e4m3_to_float(sb) * 0.05f, 1e-6f);
     } else {
         const uint32_t xi = __builtin_bit_cast(uint32_t, __fdiv_rn(amax, MODE == 0 ? 448.f : 6.f));
         int ex = (int)((xi >> 23) & 0xFFu) + ((xi & 0x7FFFFFu) != 0u ? 1 : 0);
         ex = ex > 254 ? 254 : (ex < 97 ? 97 : ex);
-        sb = (uint8_t)ex;
+        sb = amax_not_finite(amax) ? (uint8_t)0xFF : (uint8_t)ex;  // e8m0's NaN, not the clamped 254: the block stays visible
         s = __builtin_bit_cast(float, (uint32_t)ex << 23);
         // (round 3) x / 2^k == x * 2^-k bit for bit — one exact real value, one rounding — so the IEEE division (~12 VALU per
         // element) becomes a multiplication whenever 2^-k is a normal float (ex <= 253; 254 keeps the division)
@@ -115,21 +121,25 @@ __global__ __launch_bounds__(256) void act_quant_mx_kernel(const void* x, uint8_
         const int64_t base = m * stride_xm + g * G;
         const bool vec = (in_dt == GEMLITE_DT_FP16 || in_dt == GEMLITE_DT_BF16) && ((((uintptr_t)x) | (uintptr_t)(stride_xm * 2)) % 16 == 0);
         if (vec) {
+            uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
 #pragma unroll
             for (int q = 0; q < G / 8; ++q) {
                 const u32x4 d = *(const u32x4*)((const uint16_t*)x + base + 8 * q);
+                m16 = absmax16_acc(m16, d);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const uint16_t hb = (uint16_t)(d[e >> 1] >> (16 * (e & 1)));
                     v[8 * q + e] = in_dt == GEMLITE_DT_FP16 ? F16Traits<half_tag>::to_float(hb) : F16Traits<bf16_tag>::to_float(hb);
                 }
             }
+            amax = absmax16_value(m16, in_dt == GEMLITE_DT_FP16);
         } else {
 #pragma unroll
-            for (int e = 0; e < G; ++e) v[e] = load_as_float(x, base + e, in_dt);
+            for (int e = 0; e < G; ++e) {
+                v[e] = load_as_float(x, base + e, in_dt);
+                amax = absmax_keep_nan(amax, v[e]);
+            }
         }
-#pragma unroll
-        for (int e = 0; e < G; ++e) amax = fmaxf(amax, fabsf(v[e]));
     } else {
 #pragma unroll
         for (int e = 0; e < G; ++e) v[e] = 0.f;
@@ -504,21 +514,14 @@ __global__ __launch_bounds__(512) void mx_rows_kernel(const GenericParams p) {
         const bool f16 = p.x_dt == GEMLITE_DT_FP16;
         if constexpr (FQ == 2) {
             float* wmax = (float*)(xlds + ((xk_bytes + 15) & ~15));
-            float amax = 0.f;
-            for (int k = tid * 8; k < p.K; k += 512 * 8) {
-                const u32x4 d = *(const u32x4*)(xr + k);
+            uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
+            for (int k = tid * 8; k < p.K; k += 512 * 8) m16 = absmax16_acc(m16, *(const u32x4*)(xr + k));
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const uint16_t hb = (uint16_t)(d[e >> 1] >> (16 * (e & 1)));
-                    amax = fmaxf(amax, fabsf(f16 ? F16Traits<half_tag>::to_float(hb) : F16Traits<bf16_tag>::to_float(hb)));
-                }
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-            if (lane == 0) wmax[wave] = amax;
+            for (int off = 32; off >= 1; off >>= 1) m16 = absmax16_shfl(m16, off);
+            if (lane == 0) ((uint32_t*)wmax)[wave] = m16;
             __syncthreads();
-            amax = fmaxf(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])), fmaxf(fmaxf(wmax[4], wmax[5]), fmaxf(wmax[6], wmax[7])));
-            sx_row = fmaxf(__fdiv_rn(amax, 448.f), 1e-6f);
+            const float amax = absmax16_value(absmax16_merge<8>((const uint32_t*)wmax), f16);
+            sx_row = token_scale_keep_nan(amax, 448.f);
             for (int k = tid * 8; k < p.K; k += 512 * 8) {
                 const u32x4 d = *(const u32x4*)(xr + k);
                 float tq[8];
@@ -537,17 +540,18 @@ __global__ __launch_bounds__(512) void mx_rows_kernel(const GenericParams p) {
         } else
         for (int b = tid; b < blocks_k; b += 512) {
             float v[32];
-            float amax = 0.f;
+            uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
                 const u32x4 d = *(const u32x4*)(xr + b * 32 + 8 * qd);
+                m16 = absmax16_acc(m16, d);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const uint16_t hb = (uint16_t)(d[e >> 1] >> (16 * (e & 1)));
                     v[8 * qd + e] = f16 ? F16Traits<half_tag>::to_float(hb) : F16Traits<bf16_tag>::to_float(hb);
-                    amax = fmaxf(amax, fabsf(v[8 * qd + e]));
                 }
             }
+            const float amax = absmax16_value(m16, f16);
             uint32_t o[8];
             const uint8_t sb = mx_quant_block<(XF == 0 ? 0 : 1)>(v, amax, o);
             xlds[xk_bytes + b] = sb;
@@ -748,17 +752,18 @@ __global__ __launch_bounds__(512) void nvfp4_rows_kernel(const GenericParams p) 
         const bool f16 = p.x_dt == GEMLITE_DT_FP16;
         for (int b = tid; b < blocks_k; b += 512) {  // thread = one 16-k block: 32 bytes in, 8 code bytes + the scale byte out
             float v[16];
-            float amax = 0.f;
+            uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
 #pragma unroll
             for (int qd = 0; qd < 2; ++qd) {
                 const u32x4 d = *(const u32x4*)(xr + b * 16 + 8 * qd);
+                m16 = absmax16_acc(m16, d);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const uint16_t hb = (uint16_t)(d[e >> 1] >> (16 * (e & 1)));
                     v[8 * qd + e] = f16 ? F16Traits<half_tag>::to_float(hb) : F16Traits<bf16_tag>::to_float(hb);
-                    amax = fmaxf(amax, fabsf(v[8 * qd + e]));
                 }
             }
+            const float amax = absmax16_value(m16, f16);
             uint32_t o[8];
             xlds[row_bytes + b] = mx_quant_block<2>(v, amax, o);
             *(u32x2*)(xlds + b * 8) = (u32x2){o[0], o[1]};

@@ -184,21 +184,18 @@ __global__ __launch_bounds__(1024) void gemv_a8wn_kernel(const WnParams p) {
         if (g + NW < ngroups) request(qb, g + NW);  // both of the wave's first requests are out before x is touched
         float* wmax = (float*)(xq_lds + p.K);
         const uint16_t* xr = (const uint16_t*)p.x;
-        float amax = 0.f;
-        for (int k = tid * 8; k < p.K; k += 1024 * 8) {
-            const u32x4 v = *(const u32x4*)(xr + k);
+        uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
+        for (int k = tid * 8; k < p.K; k += 1024 * 8) m16 = absmax16_acc(m16, *(const u32x4*)(xr + k));
 #pragma unroll
-            for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(TR::to_float((uint16_t)(v[e >> 1] >> (16 * (e & 1))))));
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-        if (lane == 0) wmax[wave] = amax;
+        for (int off = 32; off >= 1; off >>= 1) m16 = absmax16_shfl(m16, off);
+        if (lane == 0) ((uint32_t*)wmax)[wave] = m16;
         __syncthreads();
-        amax = wmax[lane & 15];
+        m16 = ((const uint32_t*)wmax)[lane & 15];
 #pragma unroll
-        for (int off = 8; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+        for (int off = 8; off >= 1; off >>= 1) m16 = absmax16_shfl(m16, off);
+        const float amax = absmax16_value(m16, TR::DT == GEMLITE_DT_FP16);
         constexpr float qmin = INT ? -128.f : -448.f, qmax = INT ? 127.f : 448.f;
-        sx_row = fmaxf(__fdiv_rn(amax, qmax), 1e-6f);
+        sx_row = token_scale_keep_nan(amax, qmax);
         for (int k = tid * 8; k < p.K; k += 1024 * 8) {
             const u32x4 v = *(const u32x4*)(xr + k);
             float tq[8];

@@ -215,26 +215,18 @@ __global__ __launch_bounds__(512) void kmajor_fused_quant_kernel(const GenericPa
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [K] quantised x, then 8 floats
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float* wmax = (float*)(smem + ((p.K + 15) & ~15));
-    float amax = 0.f;
-    for (int k = tid * 8; k < p.K; k += 512 * 8) {  // K % 8 == 0 (planner)
-        const u32x4 v = *(const u32x4*)((const uint16_t*)p.x + k);
+    uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
+    for (int k = tid * 8; k < p.K; k += 512 * 8) m16 = absmax16_acc(m16, *(const u32x4*)((const uint16_t*)p.x + k));  // K % 8 == 0 (planner)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const uint16_t hbits = (uint16_t)(v[e >> 1] >> (16 * (e & 1)));
-            const float f = p.x_dt == GEMLITE_DT_FP16 ? F16Traits<half_tag>::to_float(hbits) : F16Traits<bf16_tag>::to_float(hbits);
-            amax = fmaxf(amax, fabsf(f));
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    if (lane == 0) wmax[wave] = amax;
+    for (int off = 32; off >= 1; off >>= 1) m16 = absmax16_shfl(m16, off);
+    if (lane == 0) ((uint32_t*)wmax)[wave] = m16;
     __syncthreads();
-    amax = fmaxf(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])), fmaxf(fmaxf(wmax[4], wmax[5]), fmaxf(wmax[6], wmax[7])));
+    const float amax = absmax16_value(absmax16_merge<8>((const uint32_t*)wmax), p.x_dt == GEMLITE_DT_FP16);
     float qmin, qmax;
     if (QDT == GEMLITE_DT_INT8) { qmin = -128.f; qmax = 127.f; }
     else if (QDT == GEMLITE_DT_FP8E4) { qmin = -448.f; qmax = 448.f; }
     else { qmin = -57344.f; qmax = 57344.f; }
-    const float sx = fmaxf(__fdiv_rn(amax, qmax), 1e-6f);
+    const float sx = token_scale_keep_nan(amax, qmax);
     for (int k = tid * 8; k < p.K; k += 512 * 8) {
         const u32x4 v = *(const u32x4*)((const uint16_t*)p.x + k);
         float t[8];
@@ -330,25 +322,19 @@ __global__ __launch_bounds__(1024, 1) void a8w8_decode_kernel(const GenericParam
         float* wmax = (float*)(smem + p.K);
         const uint16_t* xr = (const uint16_t*)p.x;
         const bool f16 = p.x_dt == GEMLITE_DT_FP16;
-        float amax = 0.f;
-        for (int k = tid * 8; k < p.K; k += 1024 * 8) {
-            const u32x4 v = *(const u32x4*)(xr + k);
+        uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
+        for (int k = tid * 8; k < p.K; k += 1024 * 8) m16 = absmax16_acc(m16, *(const u32x4*)(xr + k));
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const uint16_t hbits = (uint16_t)(v[e >> 1] >> (16 * (e & 1)));
-                amax = fmaxf(amax, fabsf(f16 ? F16Traits<half_tag>::to_float(hbits) : F16Traits<bf16_tag>::to_float(hbits)));
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-        if (lane == 0) wmax[wave] = amax;
+        for (int off = 32; off >= 1; off >>= 1) m16 = absmax16_shfl(m16, off);
+        if (lane == 0) ((uint32_t*)wmax)[wave] = m16;
         __syncthreads();
-        amax = wmax[lane & 15];
+        m16 = ((const uint32_t*)wmax)[lane & 15];
 #pragma unroll
-        for (int off = 8; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+        for (int off = 8; off >= 1; off >>= 1) m16 = absmax16_shfl(m16, off);
+        const float amax = absmax16_value(m16, f16);
         constexpr float qmin = QDT == GEMLITE_DT_INT8 ? -128.f : (QDT == GEMLITE_DT_FP8E4 ? -448.f : -57344.f);
         constexpr float qmax = QDT == GEMLITE_DT_INT8 ? 127.f : (QDT == GEMLITE_DT_FP8E4 ? 448.f : 57344.f);
-        sx = fmaxf(__fdiv_rn(amax, qmax), 1e-6f);
+        sx = token_scale_keep_nan(amax, qmax);
         for (int k = tid * 8; k < p.K; k += 1024 * 8) {
             const u32x4 v = *(const u32x4*)(xr + k);
             float t[8];
@@ -549,17 +535,17 @@ __global__ __launch_bounds__(256) void act_quant_per_token_kernel(const void* x,
     const int64_t m = blockIdx.x;
     const int tid = threadIdx.x;
     float amax = 0.f;
-    for (int64_t k = tid; k < K; k += 256) amax = fmaxf(amax, fabsf(load_as_float(x, m * stride_xm + k, in_dt)));
+    for (int64_t k = tid; k < K; k += 256) amax = absmax_keep_nan(amax, load_as_float(x, m * stride_xm + k, in_dt));
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+    for (int off = 32; off >= 1; off >>= 1) amax = absmax_keep_nan(amax, __shfl_xor(amax, off));
     if ((tid & 63) == 0) wmax[tid >> 6] = amax;
     __syncthreads();
-    amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    amax = absmax_keep_nan(absmax_keep_nan(wmax[0], wmax[1]), absmax_keep_nan(wmax[2], wmax[3]));
     float qmin, qmax;
     if (out_dt == GEMLITE_DT_INT8) { qmin = -128.f; qmax = 127.f; }
     else if (out_dt == GEMLITE_DT_FP8E4) { qmin = -448.f; qmax = 448.f; }
     else { qmin = -57344.f; qmax = 57344.f; }
-    const float s = fmaxf(__fdiv_rn(amax, qmax), 1e-6f);
+    const float s = token_scale_keep_nan(amax, qmax);
     if (tid == 0) scales[m] = s;
     for (int64_t k = tid; k < K; k += 256) {
         float v = __fdiv_rn(load_as_float(x, m * stride_xm + k, in_dt), s);
@@ -594,20 +580,17 @@ __global__ __launch_bounds__(256) void act_quant_per_token_vec_kernel(const uint
         const int k = (r * 256 + tid) * 8;
         v[r] = k < K ? *(const u32x4*)(row + k) : (u32x4){0u, 0u, 0u, 0u};
     }
-    float amax = 0.f;
+    uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
 #pragma unroll
-    for (int r = 0; r < R; ++r)
+    for (int r = 0; r < R; ++r) m16 = absmax16_acc(m16, v[r]);
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
-            amax = fmaxf(amax, fabsf(F16Traits<Tag>::to_float((uint16_t)(v[r][e >> 1] >> (16 * (e & 1))))));
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    if ((tid & 63) == 0) wmax[tid >> 6] = amax;
+    for (int off = 32; off >= 1; off >>= 1) m16 = absmax16_shfl(m16, off);
+    if ((tid & 63) == 0) ((uint32_t*)wmax)[tid >> 6] = m16;
     __syncthreads();
-    amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    const float amax = absmax16_value(absmax16_merge<4>((const uint32_t*)wmax), F16Traits<Tag>::DT == GEMLITE_DT_FP16);
     constexpr float qmin = ODT == GEMLITE_DT_INT8 ? -128.f : (ODT == GEMLITE_DT_FP8E4 ? -448.f : -57344.f);
     constexpr float qmax = ODT == GEMLITE_DT_INT8 ? 127.f : (ODT == GEMLITE_DT_FP8E4 ? 448.f : 57344.f);
-    const float s = fmaxf(__fdiv_rn(amax, qmax), 1e-6f);
+    const float s = token_scale_keep_nan(amax, qmax);
     if (tid == 0) scales[m] = s;
 #pragma unroll
     for (int r = 0; r < R; ++r) {

@@ -174,6 +174,49 @@ __device__ __forceinline__ f32x4 load_meta4(const void* p, int64_t i, int dt) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// activation quantisers: |x| max and scale that KEEP a NaN (every quantiser of the library goes through these).
+// fmaxf / fminf return the operand that is not NaN, so max(amax, |v|) and max(amax / qmax, 1e-6) turn a NaN activation into an
+// ordinary scale: a finite, wrong row.  The bits of a non-negative float order like unsigned integers — finite < Inf < NaN — in
+// fp16 and bf16 as in fp32, so the first pass runs on the packed 16-bit words as they were loaded: `d & 0x7fff7fff`, one
+// v_pk_max_u16 per two elements, no conversion; the running maximum stays a pair of 16-bit lanes through the shuffles and the LDS
+// merge and becomes a float once per row (or block).  For finite rows that float is the number the fmaxf chain over the converted
+// values gave, bit for bit (the conversions are exact and monotonic).
+// ---------------------------------------------------------------------------------------------
+typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_umax16(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2_t, a), __builtin_bit_cast(u16x2_t, b)));
+}
+// eight packed 16-bit floats into the running pair of lanes (a tree: one dependent step per 16 bytes)
+__device__ __forceinline__ uint32_t absmax16_acc(uint32_t m, const u32x4& d) {
+    constexpr uint32_t ABS = 0x7FFF7FFFu;
+    return pk_umax16(m, pk_umax16(pk_umax16(d[0] & ABS, d[1] & ABS), pk_umax16(d[2] & ABS, d[3] & ABS)));
+}
+__device__ __forceinline__ uint32_t absmax16_shfl(uint32_t m, int off) { return pk_umax16(m, (uint32_t)__shfl_xor((int)m, off)); }
+template <int N>
+__device__ __forceinline__ uint32_t absmax16_merge(const uint32_t* w) {  // N partial maxima (LDS), as a tree
+    if constexpr (N == 1) return w[0];
+    else return pk_umax16(absmax16_merge<N / 2>(w), absmax16_merge<N - N / 2>(w + N / 2));
+}
+// the pair of lanes as the float |x| max: NaN if the row held one, else Inf if it held one
+__device__ __forceinline__ float absmax16_value(uint32_t m, bool f16) {
+    const uint32_t lo = m & 0xFFFFu, hi = m >> 16;
+    const uint16_t h = (uint16_t)(lo > hi ? lo : hi);
+    return f16 ? F16Traits<half_tag>::to_float(h) : F16Traits<bf16_tag>::to_float(h);
+}
+// the same on floats, for the paths that have no packed words (any input type, unaligned rows): max(a, |v|) for a >= 0
+__device__ __forceinline__ float absmax_keep_nan(float a, float v) {
+    const uint32_t x = __builtin_bit_cast(uint32_t, a), y = __builtin_bit_cast(uint32_t, v) & 0x7FFFFFFFu;
+    return __builtin_bit_cast(float, x > y ? x : y);
+}
+// the per-token scale max(amax / qmax, 1e-6); NaN for a NaN amax, Inf for an Inf one (fmaxf would answer 1e-6 for NaN)
+__device__ __forceinline__ float token_scale_keep_nan(float amax, float qmax) {
+    const float s = __fdiv_rn(amax, qmax);
+    return s < 1e-6f ? 1e-6f : s;
+}
+// a block whose |x| max is Inf or NaN: its scale byte becomes the format's NaN code (e8m0 0xFF, e4m3 0x7F)
+__device__ __forceinline__ bool amax_not_finite(float amax) { return (__builtin_bit_cast(uint32_t, amax) & 0x7FFFFFFFu) >= 0x7F800000u; }
+
+// ---------------------------------------------------------------------------------------------
 // epilogue: channel scaling (gemm_kernels.py:392-404), cast, store
 // ---------------------------------------------------------------------------------------------
 struct Epilogue {

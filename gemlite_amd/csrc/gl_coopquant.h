@@ -19,7 +19,8 @@
 // The flags are left zero for the next launch by the last block to leave (departure count), like the split-K tickets.
 //
 // Arithmetic: bit-identical to act_quant_per_token_kernel (generic.hip): s = max(amax / qmax, 1e-6) with IEEE division, x / s with
-// IEEE division, clamp, floor(v + 0.5) for int8 (the reference's AMD rounding, quant_utils.py:259-266) / the hardware fp8 converters.
+// IEEE division (a NaN in the row is kept: absmax16_* / token_scale_keep_nan, gl_common.h), clamp, floor(v + 0.5) for int8 (the
+// reference's AMD rounding, quant_utils.py:259-266) / the hardware fp8 converters.
 #pragma once
 #include "gl_common.h"
 
@@ -39,24 +40,16 @@ __device__ __forceinline__ void quantise_row(const GenericParams& p, int m, floa
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint16_t* row = (const uint16_t*)p.cq_x + (int64_t)m * p.cq_stride_xm;
     const bool f16 = p.cq_xdt == GEMLITE_DT_FP16;
-    float amax = 0.f;
-    for (int k = tid * 8; k < p.K; k += 512 * 8) {
-        const u32x4 v = *(const u32x4*)(row + k);
+    uint32_t m16 = 0u;  // |x| max as a pair of 16-bit lanes (gl_common.h)
+    for (int k = tid * 8; k < p.K; k += 512 * 8) m16 = absmax16_acc(m16, *(const u32x4*)(row + k));
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const uint16_t hbits = (uint16_t)(v[e >> 1] >> (16 * (e & 1)));
-            const float f = f16 ? F16Traits<half_tag>::to_float(hbits) : F16Traits<bf16_tag>::to_float(hbits);
-            amax = fmaxf(amax, fabsf(f));
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    if (lane == 0) wmax[wave] = amax;
+    for (int off = 32; off >= 1; off >>= 1) m16 = absmax16_shfl(m16, off);
+    if (lane == 0) ((uint32_t*)wmax)[wave] = m16;
     __syncthreads();
-    amax = fmaxf(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])), fmaxf(fmaxf(wmax[4], wmax[5]), fmaxf(wmax[6], wmax[7])));
+    const float amax = absmax16_value(absmax16_merge<8>((const uint32_t*)wmax), f16);
     constexpr float qmin = QDT == GEMLITE_DT_INT8 ? -128.f : (QDT == GEMLITE_DT_FP8E4 ? -448.f : -57344.f);
     constexpr float qmax = QDT == GEMLITE_DT_INT8 ? 127.f : (QDT == GEMLITE_DT_FP8E4 ? 448.f : 57344.f);
-    const float sx = fmaxf(__fdiv_rn(amax, qmax), 1e-6f);
+    const float sx = token_scale_keep_nan(amax, qmax);
     uint8_t* yrow = (uint8_t*)p.x + (int64_t)m * p.K;  // the workspace copy the matmul reads (row stride K)
     for (int k = tid * 8; k < p.K; k += 512 * 8) {     // second pass: the row is in this CU's L1 / L2
         const u32x4 v = *(const u32x4*)(row + k);
