@@ -608,7 +608,13 @@ class GemLiteLinearHIP(torch.nn.Module):
             want_contiguous = False if contiguous is None else bool(contiguous)
         else:
             raise Exception("Weights were not packed, please check your W_q.dtype")
+        return self._finish_pack(scales, zeros, bias, fma_mode, want_contiguous, mx)
 
+    def _finish_pack(self, scales: Optional[Tensor], zeros: Union[Tensor, int, None], bias: Optional[Tensor], fma_mode: bool,
+                     want_contiguous: bool, mx: bool = False, meta_by_group: bool = False):
+        """The half of pack() behind the packing: self.W_q / self.elements_per_sample are set; selects the modes, lays the metadata out
+        and registers the parameters.  `meta_by_group`: scales / zeros already are [K/g, N] with the zeros folded where the selected
+        mode folds them (what the fused quantiser writes, quant_utils.quantize_groups_for_layer)."""
         self.device = self.W_q.device
         self.bias = None if bias is None else bias.to(device=self.device)
 
@@ -621,11 +627,13 @@ class GemLiteLinearHIP(torch.nn.Module):
             scaled_activations=self.scaled_activations, fma_mode=fma_mode)
 
         def rows_by_group(t: Tensor) -> Tensor:  # [N * K/g (,1)] -> [K/g, N], N fastest
+            if meta_by_group:  # (one group: the strides the view below gives a [1, N] tensor)
+                return t.view((N, 1)).t() if t.shape[0] == 1 else t
             return t.view((N, -1)).t()
 
         self.scales = None if scales is None else rows_by_group(scales)
         if zeros_kind == "tensor":
-            if fold:  # z' = -z * s, computed in fp32 and rounded to the zeros dtype (core.py:433-436)
+            if fold and not meta_by_group:  # z' = -z * s, computed in fp32 and rounded to the zeros dtype (core.py:433-436)
                 zeros = (-zeros.float() * scales.float()).to(zeros.dtype)
             self.zeros = rows_by_group(zeros)
         elif zeros_kind == "int":

@@ -56,6 +56,7 @@ const void* act_quant_vec_kernel_fn(int in_dt, int out_dt, int64_t K, int64_t st
 const void* pack_kernel_fn();
 const void* pack32_kernel_fn();
 const void* unpack_kernel_fn();
+const void* quantize_groups_kernel_fn(bool onepass);
 // capture_group.hip: independent decode3 launches of one stream capture folded into one grouped launch
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
@@ -940,7 +941,7 @@ int gemlite_hip_abi_version(void) { return GEMLITE_HIP_ABI_VERSION; }
 
 const char* gemlite_hip_build_info(void) {
     return "libgemlite_hip gfx950 (CDNA4) abi=1 kernels: gemv_wn, gemv_decode, gemv_mfma, gemv_a8wn, gemm_wn_rows, gemm_wn_direct, gemm_wn_stream, gemm_wn_mma, gemm_wn_tiled, gemm_a8w8, "
-           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols"
+           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups"
 #ifdef GL_AB_KERNELS
            " +ab_kernels"
 #endif
@@ -1235,6 +1236,35 @@ int gemlite_hip_unpack_over_cols(const void* packed, uint8_t* out, int64_t N, in
     int nb = W_nbits, pb = pack_bits;
     void* kargs[] = {(void*)&packed, (void*)&out, (void*)&N, (void*)&K, (void*)&nb, (void*)&pb};
     return launch(unpack_kernel_fn(), dim3((unsigned)((total + 255) / 256), 1, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
+}
+
+// everything is checked before the launch (host only: testable without a device)
+int gemlite_hip_quantize_groups(const gemlite_hip_quantize_args* a, void* stream) {
+    if (!a || a->struct_size != sizeof(gemlite_hip_quantize_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (!a->w || !a->q_out || !a->scales || !a->zeros) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (a->N <= 0 || a->K <= 0 || a->group_size <= 0 || a->ld_w < a->K) return GEMLITE_ERR_BAD_ARGUMENT;
+    const int nb = a->W_nbits;
+    if (!(nb == 1 || nb == 2 || nb == 4 || nb == 8)) return GEMLITE_ERR_UNSUPPORTED;
+    if (!(a->pack_bits == 0 || a->pack_bits == 32)) return GEMLITE_ERR_UNSUPPORTED;
+    if (!(a->w_dtype == GEMLITE_DT_FP32 || a->w_dtype == GEMLITE_DT_FP16 || a->w_dtype == GEMLITE_DT_BF16)) return GEMLITE_ERR_UNSUPPORTED;
+    if (!(a->meta_dtype == GEMLITE_DT_FP16 || a->meta_dtype == GEMLITE_DT_BF16)) return GEMLITE_ERR_UNSUPPORTED;
+    if (a->pack_bits == 0 && a->ld_q < a->K) return GEMLITE_ERR_BAD_ARGUMENT;
+    const int64_t g = a->group_size;
+    if (g % 32 != 0 || a->K % g != 0) return GEMLITE_ERR_BAD_SHAPE;
+    if (a->pack_bits == 32 && a->K % (32 / nb) != 0) return GEMLITE_ERR_BAD_SHAPE;
+    int64_t gcd = g, t = 256;
+    while (t) { const int64_t r = gcd % t; gcd = t; t = r; }
+    QuantGroupsParams p;
+    p.w = a->w; p.q_out = a->q_out; p.scales = a->scales; p.zeros = a->zeros;
+    p.N = a->N; p.K = a->K; p.ld_w = a->ld_w; p.ld_q = a->ld_q;
+    p.stride_meta_g = a->stride_meta_g; p.stride_meta_n = a->stride_meta_n;
+    p.span = g / gcd * 256;  // lcm(g, 256): whole groups, at most 8 per row
+    p.w_dt = a->w_dtype; p.meta_dt = a->meta_dtype; p.nbits = nb; p.group = (int)g;
+    p.pack32 = a->pack_bits == 32; p.fold = a->fold_zeros != 0;
+    const int64_t gx = (a->N + 63) / 64, gy = (a->K + p.span - 1) / p.span;
+    if (gx > 0x7FFFFFFF || gy > 65535) return GEMLITE_ERR_BAD_SHAPE;
+    void* kargs[] = {(void*)&p};
+    return launch(quantize_groups_kernel_fn(p.span == 256), dim3((unsigned)gx, (unsigned)gy, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

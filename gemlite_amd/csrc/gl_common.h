@@ -497,6 +497,17 @@ struct GenericParams {
 };
 enum { MX_F16 = 1, MX_BF16 = 2, MX_FP8 = 3, MX_FP4 = 4 };
 
+// parameter block of the grouped weight quantiser (quantize_groups.hip)
+struct QuantGroupsParams {
+    const void* w;   // [N, ld_w] fp32 / fp16 / bf16
+    void* q_out;     // pack32: uint32 [K/e, N]; else uint8 [N, ld_q]
+    void* scales;    // 16-bit, element (g, n) at g * stride_meta_g + n * stride_meta_n
+    void* zeros;
+    int64_t N, K, ld_w, ld_q, stride_meta_g, stride_meta_n;
+    int64_t span;    // k owned by one block: lcm(group, 256), whole groups only
+    int w_dt, meta_dt, nbits, group, pack32, fold;
+};
+
 // host-side launch description produced by the dispatcher
 // How many blocks of a one-block-per-CU kernel are resident at once on the current device (its CU count; 256 until a device
 // has been seen).  Kernels whose blocks WAIT for each other (reduce-scatter combine) are only planned within this limit.

@@ -6,15 +6,18 @@ A16W8 / A16W8_INT8 / A16W8_FP8, A16Wn and its ``*_HQQ_INT`` family, A8W8 dynamic
 A4W4_MXFP_dynamic, A4W4_NVFP_dynamic), ``patch_model``, ``cleanup_linear``.  The third-party ``hqq`` package is not part of this build: ``from_hqqlinear`` only
 reads the attributes the reference reads, and the raw-tensor entry points take exactly what
 ``HQQLinear.unpack()`` / ``meta`` hold.
+The ``*_RTN_INT`` subclasses of the ``*_HQQ_INT`` family (not in the reference) quantise an ``nn.Linear`` themselves, on the GPU:
+round to nearest on each group's min / max, HQQ's starting point (``from_linear``, ``quantize_weights``).
 On gfx950 FP8 means OCP e4m3fn (the reference's HIP default e4m3fnuz, helper.py:13-15, is the MI300X format).
 """
 from typing import Optional
 
 import torch
 
-from .core import GemLiteLinear
+from . import _hip
+from .core import GemLiteLinear, select_modes
 from .dtypes import TORCH_TO_DTYPE, DType
-from .quant_utils import WeightQuantizerMXFP
+from .quant_utils import WeightQuantizerINT, WeightQuantizerMXFP, check_group_size
 
 default_fp8 = torch.float8_e4m3fn
 default_post_scale = True  # channel-wise scaling applied after the K reduction (reference HIP default)
@@ -172,6 +175,106 @@ class A8W4_HQQ_INT_dynamic(A8Wn_HQQ_INT_dynamic):
 
 
 class A8W2_HQQ_INT_dynamic(A8Wn_HQQ_INT_dynamic):
+    W_nbits = 2
+
+
+DEFAULT_GROUP_SIZE = 64  # the reference's patch_model / warmup default
+
+
+class _RTNGroupQuant:
+    """``from_linear`` / ``quantize_weights`` for the grouped INT processors: the weights are quantised on the GPU by
+    ``WeightQuantizerINT`` (round to nearest on each group's min / max) and handed to the parent's ``from_weights``.
+    ``group_size=None`` at construction leaves the group size to the caller (``patch_model(..., group_size=)``, default 64)."""
+
+    group_size: Optional[int] = None
+
+    def _group_size_for(self, in_features: int, group_size: Optional[int], what: str) -> int:
+        g = self.group_size if self.group_size is not None else (DEFAULT_GROUP_SIZE if group_size is None else group_size)
+        check_group_size(in_features, g, what)
+        return g
+
+    def quantize_weights(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, group_size: Optional[int] = None,
+                         name: str = "layer") -> GemLiteLinear:
+        weight = weight.data if isinstance(weight, torch.nn.Parameter) else weight
+        bias = bias.data if isinstance(bias, torch.nn.Parameter) else bias
+        _hip.require_gpu_tensor(weight, "weight")
+        self.device = weight.device
+        g = self._group_size_for(weight.shape[1], group_size, f"{name} ({weight.shape[0]} x {weight.shape[1]})")
+        quantizer = WeightQuantizerINT(self.W_nbits, g, dtype=self.dtype, device=weight.device)
+        return self._layer_from_float(weight, bias, quantizer)
+
+    def _layer_from_float(self, weight, bias, quantizer) -> GemLiteLinear:
+        W_q, scales, zeros = quantizer.quantize(weight)
+        return self.from_weights(W_q, scales, zeros, self.W_nbits, quantizer.group_size, bias=bias)
+
+    def from_linear(self, linear: torch.nn.Linear, del_orig: bool = True, group_size: Optional[int] = None,
+                    name: str = "layer") -> GemLiteLinear:
+        assert self.W_nbits is not None, "W_nbits should be given (8, 4, 2, 1)"
+        bias = None if linear.bias is None else linear.bias.data.clone()
+        out = self.quantize_weights(linear.weight.data, bias, group_size=group_size, name=name)
+        cleanup_linear(linear, del_orig)
+        return out
+
+
+class A16Wn_RTN_INT(_RTNGroupQuant, A16Wn_HQQ_INT):
+    """A16Wn quantised here from float weights.  With 32-bit packing (the default) the layer's tensors come out of ONE launch: packed
+    words, scales and (folded) zeros already in the layer's [K/g, N] layout — tensor for tensor what
+    ``from_weights(*WeightQuantizerINT(...).quantize(W), ...)`` builds in three."""
+
+    def __init__(self, device="cuda:0", dtype=None, packing_bitwidth=None, post_scale=default_post_scale, W_nbits=None,
+                 group_size=None):
+        super().__init__(device=device, dtype=dtype, packing_bitwidth=packing_bitwidth, post_scale=post_scale, W_nbits=W_nbits)
+        self.group_size = group_size
+
+    def _layer_from_float(self, weight, bias, quantizer) -> GemLiteLinear:
+        pb = GemLiteLinear.PACKING_BITWIDTH if self.packing_bitwidth is None else self.packing_bitwidth
+        if pb != 32:
+            return super()._layer_from_float(weight, bias, quantizer)
+        dtype = quantizer.meta_dtype(weight) if self.dtype is None else self.dtype  # = scales.dtype in from_weights
+        gdt = _gemlite_dtype(dtype)
+        N, K = weight.shape
+        g = quantizer.group_size
+        fma_mode = not (self.post_scale and g == K)
+        _, _, fold = select_modes(has_scales=True, channelwise=(K // g) == 1, zeros_kind="tensor", scaled_activations=False,
+                                  fma_mode=fma_mode)
+        layer = GemLiteLinear(self.W_nbits, group_size=g, in_features=K, out_features=N, input_dtype=gdt, output_dtype=gdt)
+        W_q, scales, zeros = quantizer.quantize_packed(weight, fold_zeros=fold)
+        layer.W_q, layer.elements_per_sample = W_q, 32 // self.W_nbits
+        bias = None if bias is None else bias.to(device=weight.device, dtype=dtype)
+        return layer._finish_pack(scales, zeros, bias, fma_mode, want_contiguous=True, meta_by_group=True)
+
+
+class A16W8_RTN_INT(A16Wn_RTN_INT):
+    W_nbits = 8
+
+
+class A16W4_RTN_INT(A16Wn_RTN_INT):
+    W_nbits = 4
+
+
+class A16W2_RTN_INT(A16Wn_RTN_INT):
+    W_nbits = 2
+
+
+class A16W1_RTN_INT(A16Wn_RTN_INT):
+    W_nbits = 1
+
+
+class A8Wn_RTN_INT_dynamic(_RTNGroupQuant, A8Wn_HQQ_INT_dynamic):
+    """A8Wn dynamic quantised here from float weights (``quantize()``, then the parent's ``from_weights``)."""
+
+    def __init__(self, device="cuda:0", packing_bitwidth=None, dtype=None, post_scale=default_post_scale, fp8=default_fp8,
+                 fp32_scale=False, W_nbits=None, group_size=None):
+        super().__init__(device=device, packing_bitwidth=packing_bitwidth, dtype=dtype, post_scale=post_scale, fp8=fp8,
+                         fp32_scale=fp32_scale, W_nbits=W_nbits)
+        self.group_size = group_size
+
+
+class A8W4_RTN_INT_dynamic(A8Wn_RTN_INT_dynamic):
+    W_nbits = 4
+
+
+class A8W2_RTN_INT_dynamic(A8Wn_RTN_INT_dynamic):
     W_nbits = 2
 
 
@@ -437,7 +540,9 @@ def patch_model(model: torch.nn.Module, device, processor=None, skip_modules=("l
     """Replace every ``nn.Linear`` whose qualified name contains none of ``skip_modules`` by the processor's layer
     (reference: helper.py:34-85; same argument order).  HQQ processors (``from_hqqlinear``) would first quantise
     with the third-party ``hqq`` package, which this build does not ship: they raise NotImplementedError here — feed
-    ``from_weights`` / ``from_hqqlinear`` with already quantised tensors instead."""
+    ``from_weights`` / ``from_hqqlinear`` with already quantised tensors instead, or take the ``*_RTN_INT`` processors, which
+    quantise the float weights themselves.  ``group_size`` reaches those when they were built without one; a layer whose
+    ``in_features`` it does not divide raises ValueError with the layer's name."""
     if processor is None or hasattr(device, "from_linear") or hasattr(device, "from_hqqlinear"):
         device, processor = (processor if processor is not None else "cuda:0"), device  # (model, processor[, device]) order
     if not hasattr(processor, "from_linear"):
@@ -450,7 +555,11 @@ def patch_model(model: torch.nn.Module, device, processor=None, skip_modules=("l
                 if not any(sk in full for sk in skip_modules):
                     if hasattr(processor, "device"):
                         processor.device = device
-                    setattr(module, name, processor.from_linear(child.to(device)))
+                    if isinstance(processor, _RTNGroupQuant):
+                        new = processor.from_linear(child.to(device), group_size=group_size, name=full)
+                    else:
+                        new = processor.from_linear(child.to(device))
+                    setattr(module, name, new)
             else:
                 _walk(child, full)
 
@@ -464,7 +573,7 @@ def warmup(processor=None, shapes=(), batch_sizes=None, group_size: int = 64, dt
     with a processor and shapes, same call as the reference's `warmup(A8W8_INT8_dynamic(), shapes=[(4096, 4096)], batch_sizes=[1, 8])` —
     one call per (out_features, in_features) and batch size on a random layer of that shape, which sizes the stream's workspace for the
     largest plan, raises the kernels' LDS limits and fills the launch-template caches, so that no request pays for them.
-    (`group_size` belongs to the reference's hqq path; processors that need hqq are skipped.  autotune_layer() below is the measured
+    (`group_size` reaches the `*_RTN_INT` processors built without one; processors that need hqq are skipped.  autotune_layer() below is the measured
     search over the planners' alternatives.)"""
     from . import _hip
     from .core import _M_BUCKETS, autoload_default_config
@@ -482,7 +591,10 @@ def warmup(processor=None, shapes=(), batch_sizes=None, group_size: int = 64, dt
     for out_features, in_features in shapes:
         linear = torch.nn.Linear(in_features, out_features, bias=False, device=dev, dtype=dtype)
         try:
-            layer = processor.from_linear(linear)
+            if isinstance(processor, _RTNGroupQuant):
+                layer = processor.from_linear(linear, group_size=group_size)
+            else:
+                layer = processor.from_linear(linear)
         except Exception as e:  # (a processor that only converts HQQ layers, a shape it rejects: same as the reference — say so, go on)
             logger.warning(f"warmup: {type(processor).__name__} does not take a {out_features} x {in_features} layer: {e}")
             continue

@@ -5,6 +5,9 @@
 int8 rounded with floor(v + 0.5) — the rounding the reference's kernel uses on AMD (quant_utils.py:259-266).
 Runs as one HIP kernel (`gemlite_hip_scale_activations_per_token`).
 
+``WeightQuantizerINT``: float weights -> grouped asymmetric INT codes + (scale, zero) per group, one HIP kernel
+(`gemlite_hip_quantize_groups`; the reference leaves this step to the third-party ``hqq`` package).
+
 Block-scaled formats (reference: gemlite/quant_utils.py:21-225 weight quantiser, :502-954 activation quantisers):
 ``WeightQuantizerMXFP`` (host-side torch code, any device: it runs once per layer) and
 ``scale_activations_mxfp8 / _mxfp4 / _nvfp4`` (one HIP kernel each, `gemlite_hip_scale_activations_*`).
@@ -50,6 +53,70 @@ def scale_activations_per_token(tensor: torch.Tensor, w_dtype: torch.dtype, fp32
 
 
 scale_activations_per_token_triton = scale_activations_per_token  # reference export name
+
+
+# ------------------------------------------------------------------------------------------------------
+# grouped asymmetric INT weights: round to nearest on the group's min / max (one HIP launch)
+# ------------------------------------------------------------------------------------------------------
+def check_group_size(in_features: int, group_size: int, what: str = "weight"):
+    if group_size <= 0 or group_size % 32 != 0 or in_features % group_size != 0:
+        raise ValueError(f"{what}: group_size {group_size} must be a multiple of 32 that divides in_features = {in_features}")
+
+
+def _quantize_groups(W: torch.Tensor, W_nbits: int, group_size: int, meta_dtype: torch.dtype, packed: bool, fold_zeros: bool = False):
+    """One `gemlite_hip_quantize_groups` launch on W's device and current stream.  packed: (int32 words [K/e, N], scales [K/g, N],
+    zeros [K/g, N], folded if asked) — what a packed layer holds; else (uint8 codes [N, K], scales [N * K/g, 1], zeros [N * K/g, 1])."""
+    _hip.require_gpu_tensor(W, "W")
+    assert W.dim() == 2, "W should be [out_features, in_features]"
+    if W.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        W = W.float()
+    if W.stride(1) != 1:
+        W = W.contiguous()
+    N, K = W.shape
+    check_group_size(K, group_size)
+    n_groups = K // group_size
+    dev = W.device
+    a = _hip.QuantizeArgs()
+    if packed:
+        q = torch.empty((K // (32 // W_nbits), N), dtype=torch.int32, device=dev)
+        scales = torch.empty((n_groups, N), dtype=meta_dtype, device=dev)
+        a.pack_bits, a.ld_q, a.stride_meta_g, a.stride_meta_n = 32, 0, N, 1
+    else:
+        q = torch.empty((N, K), dtype=torch.uint8, device=dev)
+        scales = torch.empty((N * n_groups, 1), dtype=meta_dtype, device=dev)
+        a.pack_bits, a.ld_q, a.stride_meta_g, a.stride_meta_n = 0, K, 1, n_groups
+    zeros = torch.empty_like(scales)
+    a.struct_size = _hip.C.sizeof(_hip.QuantizeArgs)
+    a.w, a.w_dtype, a.N, a.K, a.ld_w = W.data_ptr(), TORCH_TO_DTYPE[W.dtype].value, N, K, W.stride(0)
+    a.W_nbits, a.group_size, a.meta_dtype = W_nbits, group_size, TORCH_TO_DTYPE[meta_dtype].value
+    a.q_out, a.scales, a.zeros, a.fold_zeros = q.data_ptr(), scales.data_ptr(), zeros.data_ptr(), int(fold_zeros)
+    with _hip.on_device(dev):
+        rc = _hip.load().gemlite_hip_quantize_groups(_hip.C.byref(a), _hip.current_stream_handle(dev))
+    _hip.raise_for_status(rc, "quantize_groups")
+    return q, scales, zeros
+
+
+class WeightQuantizerINT:
+    """Float weights -> (W_q uint8 [N, K], scales [N * K/g, 1], zeros [N * K/g, 1]): the tensors ``from_weights`` of the ``*_HQQ_INT``
+    processors and HQQ's ``meta`` hold.  Asymmetric round to nearest on each group's min / max (HQQ's starting point, without its
+    optimiser); the codes are taken against the ROUNDED (scale, zero), which is what the layer dequantises with.  ``dtype`` is the
+    metadata type: None = W.dtype if that is fp16 / bf16, else fp16.  GPU tensors only."""
+
+    def __init__(self, W_nbits: int, group_size: int, dtype=None, device="cuda:0"):
+        assert W_nbits in (8, 4, 2, 1), "W_nbits should be 8, 4, 2 or 1"
+        self.W_nbits, self.group_size, self.dtype, self.device = W_nbits, group_size, dtype, device
+
+    def meta_dtype(self, W: torch.Tensor) -> torch.dtype:
+        if self.dtype is not None:
+            return self.dtype
+        return W.dtype if W.dtype in (torch.float16, torch.bfloat16) else torch.float16
+
+    def quantize(self, W: torch.Tensor):
+        return _quantize_groups(W, self.W_nbits, self.group_size, self.meta_dtype(W), packed=False)
+
+    def quantize_packed(self, W: torch.Tensor, fold_zeros: bool):
+        """The layer's own tensors in one launch: 32-bit words [K/e, N], scales and (folded) zeros [K/g, N]."""
+        return _quantize_groups(W, self.W_nbits, self.group_size, self.meta_dtype(W), packed=True, fold_zeros=fold_zeros)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@
  *   gemlite_hip_pack_over_cols     <- pack_weights_over_cols_triton, gemlite/bitpack.py:77-144
  *                                     (bit layout spec: pack_weights_over_cols_torch :36-60)
  *   gemlite_hip_unpack_over_cols   <- unpack_over_cols_triton, gemlite/bitpack.py:175-241
+ *   gemlite_hip_quantize_groups    <- (no counterpart: the reference leaves float -> grouped INT to the third-party hqq package)
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer is a DEVICE pointer unless stated;
@@ -392,6 +393,35 @@ int gemlite_hip_pack_over_cols(const uint8_t* w_q, void* out, int64_t N, int64_t
 /* Inverse: out[N, K] uint8 from packed [K/e, N]. */
 int gemlite_hip_unpack_over_cols(const void* packed, uint8_t* out, int64_t N, int64_t K,
                                  int32_t W_nbits, int32_t pack_bits, void* stream);
+
+/* Quantise float weights W[N, K] (fp32 / fp16 / bf16, row stride ld_w) to grouped asymmetric INT: round to nearest on the min / max of
+ * every group of group_size consecutive k of a row — one (scale, zero) pair per (n, group), T = meta_dtype (fp16 / bf16), rT = round to
+ * T and back, every step a single fp32 IEEE operation:
+ *     s = (hi - lo) / (2^W_nbits - 1), s < 2^-14 -> 1;   s_r = rT(s);   z_r = rT(-lo / s_r);
+ *     q = clamp(rint(w / s_r + z_r), 0, 2^W_nbits - 1)          (rint: half to even; the layer computes (q - z_r) * s_r)
+ *   pack_bits 32: q_out = the packed words [K/e, N] of gemlite_hip_pack_over_cols (ld_q unused);
+ *   pack_bits 0 : q_out = uint8 codes [N, K] with row stride ld_q.
+ *   scales / zeros: element (group j, row n) at j * stride_meta_g + n * stride_meta_n (elements): (N, 1) is the layer's [K/g, N],
+ *   (1, K/g) is [N * K/g, 1].  fold_zeros != 0 stores rT(-z_r * s_r) instead of z_r (what pack() keeps for W_group_mode 4).
+ * group_size % 32 == 0, K % group_size == 0; one launch, no workspace.  Non-finite weights give unspecified codes (and no fault). */
+typedef struct gemlite_hip_quantize_args {
+    uint32_t struct_size; /* = sizeof(gemlite_hip_quantize_args), ABI guard */
+    int32_t w_dtype;      /* GEMLITE_DT_FP32 / FP16 / BF16 */
+    const void* w;
+    int64_t N, K, ld_w;
+    int32_t W_nbits;      /* 1, 2, 4, 8 */
+    int32_t group_size;
+    int32_t pack_bits;    /* 0 or 32 */
+    int32_t meta_dtype;   /* GEMLITE_DT_FP16 / BF16 */
+    void* q_out;
+    int64_t ld_q;
+    void* scales;
+    void* zeros;
+    int64_t stride_meta_g, stride_meta_n;
+    int32_t fold_zeros;
+    int32_t reserved;     /* 0 */
+} gemlite_hip_quantize_args;
+int gemlite_hip_quantize_groups(const gemlite_hip_quantize_args* args, void* stream);
 
 #ifdef __cplusplus
 }
