@@ -101,6 +101,27 @@ class QuantizeArgs(C.Structure):
     ]
 
 
+class QuantizeMxArgs(C.Structure):
+    """struct gemlite_hip_quantize_mx_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("w_dtype", C.c_int32),
+        ("w", C.c_void_p),
+        ("N", C.c_int64),
+        ("K", C.c_int64),
+        ("ld_w", C.c_int64),
+        ("format", C.c_int32),
+        ("pack_nibbles", C.c_int32),
+        ("q_out", C.c_void_p),
+        ("ld_q", C.c_int64),
+        ("scales", C.c_void_p),
+        ("stride_scale_g", C.c_int64),
+        ("stride_scale_n", C.c_int64),
+        ("reserved", C.c_int64),
+    ]
+
+
 BIAS_NOT_ADDED = 1  # gemlite_hip_forward_ex: launched without the bias, the caller adds it
 
 _lib = None
@@ -175,6 +196,8 @@ def load():
             C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
         lib.gemlite_hip_quantize_groups.restype = C.c_int
         lib.gemlite_hip_quantize_groups.argtypes = [C.POINTER(QuantizeArgs), C.c_void_p]
+        lib.gemlite_hip_quantize_mx.restype = C.c_int
+        lib.gemlite_hip_quantize_mx.argtypes = [C.POINTER(QuantizeMxArgs), C.c_void_p]
         if lib.gemlite_hip_abi_version() != ABI_VERSION:
             raise GemliteHipError("libgemlite_hip.so ABI version mismatch; rebuild it")
         _lib = lib
@@ -191,7 +214,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_capture_group_max", "gemlite_hip_capture_group_stats", "gemlite_hip_capture_group_compatible",
     "gemlite_hip_capture_group_grid_y",
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
-    "gemlite_hip_quantize_groups",
+    "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx",
 )
 
 

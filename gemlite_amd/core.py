@@ -614,7 +614,8 @@ class GemLiteLinearHIP(torch.nn.Module):
                      want_contiguous: bool, mx: bool = False, meta_by_group: bool = False):
         """The half of pack() behind the packing: self.W_q / self.elements_per_sample are set; selects the modes, lays the metadata out
         and registers the parameters.  `meta_by_group`: scales / zeros already are [K/g, N] with the zeros folded where the selected
-        mode folds them (what the fused quantiser writes, quant_utils.quantize_groups_for_layer)."""
+        mode folds them (what the fused quantisers write: WeightQuantizerINT.quantize_packed, and — with `mx`, as block-scale bytes —
+        WeightQuantizerMXFP.quantize_packed)."""
         self.device = self.W_q.device
         self.bias = None if bias is None else bias.to(device=self.device)
 

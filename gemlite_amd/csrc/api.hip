@@ -57,6 +57,7 @@ const void* pack_kernel_fn();
 const void* pack32_kernel_fn();
 const void* unpack_kernel_fn();
 const void* quantize_groups_kernel_fn(bool onepass);
+const void* quantize_mx_kernel_fn(int format);
 // capture_group.hip: independent decode3 launches of one stream capture folded into one grouped launch
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
@@ -941,7 +942,7 @@ int gemlite_hip_abi_version(void) { return GEMLITE_HIP_ABI_VERSION; }
 
 const char* gemlite_hip_build_info(void) {
     return "libgemlite_hip gfx950 (CDNA4) abi=1 kernels: gemv_wn, gemv_decode, gemv_mfma, gemv_a8wn, gemm_wn_rows, gemm_wn_direct, gemm_wn_stream, gemm_wn_mma, gemm_wn_tiled, gemm_a8w8, "
-           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups"
+           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups, quantize_mx"
 #ifdef GL_AB_KERNELS
            " +ab_kernels"
 #endif
@@ -1265,6 +1266,27 @@ int gemlite_hip_quantize_groups(const gemlite_hip_quantize_args* a, void* stream
     if (gx > 0x7FFFFFFF || gy > 65535) return GEMLITE_ERR_BAD_SHAPE;
     void* kargs[] = {(void*)&p};
     return launch(quantize_groups_kernel_fn(p.span == 256), dim3((unsigned)gx, (unsigned)gy, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
+}
+
+// everything is checked before the launch (host only: testable without a device)
+int gemlite_hip_quantize_mx(const gemlite_hip_quantize_mx_args* a, void* stream) {
+    if (!a || a->struct_size != sizeof(gemlite_hip_quantize_mx_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (!a->w || !a->q_out || !a->scales) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (a->N <= 0 || a->K <= 0 || a->ld_w < a->K) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (a->format < 0 || a->format > 2) return GEMLITE_ERR_UNSUPPORTED;
+    if (!(a->w_dtype == GEMLITE_DT_FP32 || a->w_dtype == GEMLITE_DT_FP16 || a->w_dtype == GEMLITE_DT_BF16)) return GEMLITE_ERR_UNSUPPORTED;
+    if (!(a->pack_nibbles == 0 || a->pack_nibbles == 1) || (a->pack_nibbles == 1 && a->format == 0)) return GEMLITE_ERR_UNSUPPORTED;
+    if (a->ld_q < (a->pack_nibbles ? a->K / 2 : a->K)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (a->K % 32 != 0) return GEMLITE_ERR_BAD_SHAPE;
+    QuantMxParams p;
+    p.w = a->w; p.q_out = (uint8_t*)a->q_out; p.scales = (uint8_t*)a->scales;
+    p.N = a->N; p.K = a->K; p.ld_w = a->ld_w; p.ld_q = a->ld_q;
+    p.stride_scale_g = a->stride_scale_g; p.stride_scale_n = a->stride_scale_n;
+    p.w_dt = a->w_dtype; p.pack = a->pack_nibbles;
+    const int64_t gx = (a->N + 63) / 64, gy = (a->K + 255) / 256;
+    if (gx > 0x7FFFFFFF || gy > 65535) return GEMLITE_ERR_BAD_SHAPE;
+    void* kargs[] = {(void*)&p};
+    return launch(quantize_mx_kernel_fn(a->format), dim3((unsigned)gx, (unsigned)gy, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -497,6 +497,48 @@ struct GenericParams {
 };
 enum { MX_F16 = 1, MX_BF16 = 2, MX_FP8 = 3, MX_FP4 = 4 };
 
+// 8 consecutive weights of row n from k (k % 8 == 0) of a float matrix w[.., ld_w] as fp32 — the load of the weight quantisers
+// (quantize_groups.hip, quantize_mx.hip).  vec: w and the row pitch are 16-byte aligned (one 16-byte load of a 16-bit input, two for fp32)
+__device__ __forceinline__ void load8_as_float(const void* w, int w_dt, int64_t ld_w, bool vec, int64_t n, int64_t k, float (&v)[8]) {
+    const int64_t off = n * ld_w + k;
+    if (w_dt == GEMLITE_DT_FP32) {
+        const float* s = (const float*)w + off;
+        if (vec) {
+            const f32x4 a = *(const f32x4*)s, b = *(const f32x4*)(s + 4);
+            v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
+            v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = s[e];
+        }
+    } else {
+        const uint16_t* s = (const uint16_t*)w + off;
+        uint32_t d[4];
+        if (vec) {
+            const u32x4 a = *(const u32x4*)s;
+            d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; d[3] = a[3];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d[e] = (uint32_t)s[2 * e] | ((uint32_t)s[2 * e + 1] << 16);
+        }
+        const bool f16 = w_dt == GEMLITE_DT_FP16;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const uint16_t h = (uint16_t)(d[e >> 1] >> (16 * (e & 1)));
+            v[e] = f16 ? F16Traits<half_tag>::to_float(h) : F16Traits<bf16_tag>::to_float(h);
+        }
+    }
+}
+
+// parameter block of the block-scaled weight quantiser (quantize_mx.hip)
+struct QuantMxParams {
+    const void* w;    // [N, ld_w] fp32 / fp16 / bf16
+    uint8_t* q_out;   // bytes [N, ld_q]: e4m3 (K per row), e2m1 codes one per byte (K) or two per byte (K / 2)
+    uint8_t* scales;  // one byte per block, (block j, row n) at j * stride_scale_g + n * stride_scale_n
+    int64_t N, K, ld_w, ld_q, stride_scale_g, stride_scale_n;
+    int w_dt, pack;
+};
+
 // parameter block of the grouped weight quantiser (quantize_groups.hip)
 struct QuantGroupsParams {
     const void* w;   // [N, ld_w] fp32 / fp16 / bf16

@@ -22,34 +22,7 @@ __device__ __forceinline__ float qg_round_meta(float v, bool f16) {
 
 // 8 consecutive weights of row n from k (k % 8 == 0) as fp32
 __device__ __forceinline__ void qg_load8(const QuantGroupsParams& p, bool vec, int64_t n, int64_t k, float (&v)[8]) {
-    const int64_t off = n * p.ld_w + k;
-    if (p.w_dt == GEMLITE_DT_FP32) {
-        const float* s = (const float*)p.w + off;
-        if (vec) {
-            const f32x4 a = *(const f32x4*)s, b = *(const f32x4*)(s + 4);
-            v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-            v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = s[e];
-        }
-    } else {
-        const uint16_t* s = (const uint16_t*)p.w + off;
-        uint32_t d[4];
-        if (vec) {
-            const u32x4 a = *(const u32x4*)s;
-            d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; d[3] = a[3];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) d[e] = (uint32_t)s[2 * e] | ((uint32_t)s[2 * e + 1] << 16);
-        }
-        const bool f16 = p.w_dt == GEMLITE_DT_FP16;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const uint16_t h = (uint16_t)(d[e >> 1] >> (16 * (e & 1)));
-            v[e] = f16 ? F16Traits<half_tag>::to_float(h) : F16Traits<bf16_tag>::to_float(h);
-        }
-    }
+    load8_as_float(p.w, p.w_dt, p.ld_w, vec, n, k, v);
 }
 
 // (lo, hi) of a group -> the rounded scale and zero the layer will dequantise with

@@ -17,7 +17,7 @@ import torch
 from . import _hip
 from .core import GemLiteLinear, select_modes
 from .dtypes import TORCH_TO_DTYPE, DType
-from .quant_utils import WeightQuantizerINT, WeightQuantizerMXFP, check_group_size
+from .quant_utils import WeightQuantizerINT, WeightQuantizerMXFP, _takes_mx_kernel, check_group_size
 
 default_fp8 = torch.float8_e4m3fn
 default_post_scale = True  # channel-wise scaling applied after the K reduction (reference HIP default)
@@ -371,7 +371,9 @@ A8W8_INT8_dynamic, A8W8_FP8_dynamic = A8W8_int8_dynamic, A8W8_fp8_dynamic
 class _BlockScaledProcessor:
     """Shared body of the MXFP / NVFP processors.  ``from_weights(weight, bias, scales)`` takes pre-quantised
     elements (fp8 tensor, or uint8 e2m1 codes ``[N, K]``) with their block scales ``[N, K / group]``;
-    ``from_linear`` quantises an ``nn.Linear`` with ``WeightQuantizerMXFP`` first.  Subclasses fix: W_nbits, group size,
+    ``from_linear`` quantises an ``nn.Linear`` with ``WeightQuantizerMXFP`` first, ``quantize_weights(weight, bias)`` a float weight on the
+    GPU.  A float weight that lives on the GPU becomes the layer in ONE launch (``quantize_packed``: elements already two codes per byte,
+    scales already [K/g, N]) — tensor for tensor what ``from_weights(*quantize(W))`` builds.  Subclasses fix: W_nbits, group size,
     the layer's input format, whether activations are quantised, and the channel_scale_mode set after ``pack()``."""
     W_nbits = None
     group_size = 32
@@ -394,6 +396,53 @@ class _BlockScaledProcessor:
             return self.quantizer_mx.quantize_mxfp8(W, index=True, mx_fp8_dtype=self.mx_fp8_dtype)
         return self.quantizer_mx.quantize_mxfp4(W, index=True)
 
+    def _format(self) -> str:
+        return "mxfp8" if self.W_nbits == 8 else "mxfp4"
+
+    def _layer_dtype(self) -> torch.dtype:
+        if self.dtype is None:
+            assert not self.scaled_activations, "Input dtype should be either torch.float16 or torch.bfloat16, not None."
+            return torch.float16
+        return self.dtype
+
+    def _fused(self, W: torch.Tensor) -> bool:
+        """W can become the layer in one launch: the kernel takes it and the layer is to live where W is."""
+        if not _takes_mx_kernel(W, True) or (self.W_nbits == 8 and self.mx_fp8_dtype != torch.float8_e4m3fn):
+            return False
+        dev = torch.device(self.device)
+        return dev.type == "cuda" and (torch.cuda.current_device() if dev.index is None else dev.index) == W.device.index
+
+    def _layer_from_float(self, W: torch.Tensor, bias: Optional[torch.Tensor]) -> GemLiteLinear:
+        """from_weights(*quantize(W)) without the intermediate tensors: the kernel writes what pack() would store."""
+        dtype = self._layer_dtype()
+        N, K = W.shape
+        layer = GemLiteLinear(self.W_nbits, group_size=self.group_size, in_features=K, out_features=N,
+                              input_dtype=self._input_dtype(dtype),
+                              output_dtype=_gemlite_dtype(dtype) if self.scaled_activations else self._input_dtype(dtype),
+                              scaled_activations=self.scaled_activations)
+        W_q, scales = self.quantizer_mx.quantize_packed(W, self._format())
+        layer.W_q, layer.elements_per_sample = W_q.t(), (1 if self.W_nbits == 8 else 2)  # [K(/2), N] view: K-contiguous per output column
+        bias = None if bias is None else bias.to(device=W.device, dtype=dtype)
+        layer._finish_pack(scales, None, bias, fma_mode=True, want_contiguous=False, mx=True, meta_by_group=True)
+        if self.scaled_activations:
+            layer.W_group_mode, layer.channel_scale_mode = 0, self._channel_scale_mode()
+        return layer
+
+    def quantize_weights(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> GemLiteLinear:
+        """A float weight [out_features, in_features] on the GPU -> the packed layer, on the weight's device."""
+        weight = weight.data if isinstance(weight, torch.nn.Parameter) else weight
+        bias = bias.data if isinstance(bias, torch.nn.Parameter) else bias
+        _hip.require_gpu_tensor(weight, "weight")
+        assert weight.dim() == 2, "weight should be [out_features, in_features]"
+        self.device = weight.device
+        if self.quantizer_mx is None:
+            self.quantizer_mx = WeightQuantizerMXFP(device=self.device, compute_dtype=weight.dtype)
+        if self._fused(weight):
+            return self._layer_from_float(weight, bias)
+        N, K = weight.shape
+        W_q, scales = self._quantize(weight)
+        return _BlockScaledProcessor.from_weights(self, weight=W_q.view(N, K), bias=bias, scales=scales.view(N, K // self.group_size))
+
     # -- API of the reference processors ------------------------------------------------------------
     def from_weights(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                      scales: Optional[torch.Tensor] = None) -> GemLiteLinear:
@@ -410,10 +459,7 @@ class _BlockScaledProcessor:
             assert scales.dtype == torch.float8_e4m3fn, f"Invalid scales.dtype, should be float8_e4m3fn, got {scales.dtype}."
         else:
             assert scales.dtype in (torch.float8_e8m0fnu, torch.uint8), f"Invalid scales.dtype, should be e8m0 / view(uint8), got {scales.dtype}."
-        dtype = self.dtype
-        if dtype is None:
-            assert not self.scaled_activations, "Input dtype should be either torch.float16 or torch.bfloat16, not None."
-            dtype = torch.float16
+        dtype = self._layer_dtype()
         out_features, in_features = weight.shape
         W_q = weight.to(device=self.device)
         scales = scales.to(device=self.device).view(out_features, in_features // self.group_size)
@@ -433,6 +479,10 @@ class _BlockScaledProcessor:
             self.quantizer_mx = WeightQuantizerMXFP(device=self.device, compute_dtype=linear_layer.weight.dtype)
         W = linear_layer.weight.data
         bias = None if linear_layer.bias is None else linear_layer.bias.clone()
+        if self._fused(W):  # GPU weight: the layer's tensors in one launch
+            out = self._layer_from_float(W, bias)
+            cleanup_linear(linear_layer, del_orig)
+            return out
         N, K = W.shape
         W_q, scales = self._quantize(W)
         W_q, scales = W_q.view(N, K), scales.view(N, K // self.group_size)
@@ -523,6 +573,9 @@ class A4W4_NVFP_dynamic(_BlockScaledProcessor):
 
     def _quantize(self, W):
         return self.quantizer_mx.quantize_nvfp4(W, index=True)
+
+    def _format(self):
+        return "nvfp4"
 
 
 def cleanup_linear(linear_layer, del_orig: bool = True):

@@ -9,7 +9,8 @@ Runs as one HIP kernel (`gemlite_hip_scale_activations_per_token`).
 (`gemlite_hip_quantize_groups`; the reference leaves this step to the third-party ``hqq`` package).
 
 Block-scaled formats (reference: gemlite/quant_utils.py:21-225 weight quantiser, :502-954 activation quantisers):
-``WeightQuantizerMXFP`` (host-side torch code, any device: it runs once per layer) and
+``WeightQuantizerMXFP`` (GPU float weights: one HIP kernel, `gemlite_hip_quantize_mx`; CPU tensors, the scale-search
+window and ``index=False``: the reference's torch code) and
 ``scale_activations_mxfp8 / _mxfp4 / _nvfp4`` (one HIP kernel each, `gemlite_hip_scale_activations_*`).
 """
 from __future__ import annotations
@@ -128,6 +129,49 @@ FP4_POS_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)          # e2m1 magnit
 FP4_THRESHOLDS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)          # midpoints: a magnitude ON a midpoint rounds down
 
 
+MX_FORMATS = {"mxfp8": (0, 32), "mxfp4": (1, 32), "nvfp4": (2, 16)}  # name -> (format code of gemlite_hip_quantize_mx, block size)
+_MX_KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _takes_mx_kernel(W: torch.Tensor, index: bool, window_size: int = 0) -> bool:
+    """The inputs `gemlite_hip_quantize_mx` takes; everything else stays on the torch code below."""
+    return (W.is_cuda and index and window_size == 0 and W.dim() == 2 and W.dtype in _MX_KERNEL_DTYPES
+            and W.shape[0] > 0 and W.shape[1] > 0 and W.shape[1] % 32 == 0)
+
+
+def _quantize_mx(W: torch.Tensor, fmt: str, layer_layout: bool):
+    """One `gemlite_hip_quantize_mx` launch on W's device and current stream (contract: DESIGN §2.2, include/gemlite_hip.h).
+    layer_layout: (elements [N, K] fp8 or [N, K/2] uint8 with two codes per byte, scale bytes [K/g, N]) — what a packed layer holds;
+    else (elements [N, K] fp8 / uint8 codes, scale bytes [N * K/g, 1])."""
+    _hip.require_gpu_tensor(W, "W")
+    assert W.dim() == 2, "W should be [out_features, in_features]"
+    code, g = MX_FORMATS[fmt]
+    if W.dtype not in _MX_KERNEL_DTYPES:
+        W = W.float()
+    if W.stride(1) != 1:
+        W = W.contiguous()
+    N, K = W.shape
+    if K % 32 != 0:
+        raise ValueError(f"block-scaled weight quantisation needs in_features % 32 == 0, got {K}")
+    dev = W.device
+    pack = int(layer_layout and code != 0)
+    q = torch.empty((N, K // 2 if pack else K), dtype=torch.float8_e4m3fn if code == 0 else torch.uint8, device=dev)
+    a = _hip.QuantizeMxArgs()
+    if layer_layout:
+        scales = torch.empty((K // g, N), dtype=torch.uint8, device=dev)
+        a.stride_scale_g, a.stride_scale_n = N, 1
+    else:
+        scales = torch.empty((N * (K // g), 1), dtype=torch.uint8, device=dev)
+        a.stride_scale_g, a.stride_scale_n = 1, K // g
+    a.struct_size = _hip.C.sizeof(_hip.QuantizeMxArgs)
+    a.w, a.w_dtype, a.N, a.K, a.ld_w = W.data_ptr(), TORCH_TO_DTYPE[W.dtype].value, N, K, W.stride(0)
+    a.format, a.pack_nibbles, a.q_out, a.ld_q, a.scales, a.reserved = code, pack, q.data_ptr(), q.stride(0), scales.data_ptr(), 0
+    with _hip.on_device(dev):
+        rc = _hip.load().gemlite_hip_quantize_mx(_hip.C.byref(a), _hip.current_stream_handle(dev))
+    _hip.raise_for_status(rc, "quantize_mx")
+    return q, scales
+
+
 def _fp4_tables(device, dtype=torch.float32):
     pos = torch.tensor(FP4_POS_VALUES, dtype=dtype, device=device)
     return pos, torch.tensor(FP4_THRESHOLDS, dtype=dtype, device=device), torch.cat([pos, -pos])
@@ -139,7 +183,10 @@ class WeightQuantizerMXFP:
     ``scale = 2^ceil(log2(amax / qmax))`` floored at 2^-30; NVFP4 = e2m1 elements with an e4m3 scale per 16 weights on
     top of the fixed meta scale 0.05.  ``index=True`` returns what ``GemLiteLinear.pack`` takes (fp8 tensor / uint8
     codes), otherwise the rounded values as floats.  ``window_size`` > 0 searches neighbouring scales for the smallest
-    mean absolute error, like the reference."""
+    mean absolute error, like the reference.
+    A 2-D fp32 / fp16 / bf16 weight on a GPU with ``index=True``, no window and ``in_features % 32 == 0`` is quantised by ONE HIP
+    launch (`gemlite_hip_quantize_mx`; same shapes and dtypes returned, finite blocks equal to this torch code on the CPU, a block that
+    holds a NaN / Inf gets the scale format's NaN code); every other call runs the torch code below unchanged."""
 
     def __init__(self, compute_dtype=torch.bfloat16, device="cuda:0"):
         self.compute_dtype = compute_dtype
@@ -158,7 +205,16 @@ class WeightQuantizerMXFP:
         hit = W_q.reshape(-1, 1) == values.view(1, -1)  # -0.0 == 0.0: both zeros map to code 0 (first match)
         return hit.to(torch.uint8).argmax(dim=1).to(torch.uint8).view(W_q.shape)
 
+    def quantize_packed(self, W: torch.Tensor, fmt: str):
+        """The layer's own tensors in one launch, fmt = "mxfp8" | "mxfp4" | "nvfp4": elements [N, K] float8_e4m3fn or [N, K/2] uint8
+        (two e2m1 codes per byte, even k in the low nibble) and the block scales [K/g, N] (uint8 e8m0 bytes; NVFP4: float8_e4m3fn)."""
+        q, scales = _quantize_mx(W, fmt, layer_layout=True)
+        return q, (scales.view(torch.float8_e4m3fn) if fmt == "nvfp4" else scales)
+
     def quantize_mxfp8(self, W, index: bool = False, mx_fp8_dtype: torch.dtype = torch.float8_e4m3fn):
+        if mx_fp8_dtype == torch.float8_e4m3fn and _takes_mx_kernel(W, index):
+            q, scales = _quantize_mx(W, "mxfp8", layer_layout=False)
+            return q.view(-1, 32), scales.view(torch.float8_e8m0fnu)
         eps = 2.0 ** MX_EPS_EXP
         lo, hi = get_dtype_range(mx_fp8_dtype)
         flat = W.reshape(-1, 32).float()
@@ -176,6 +232,9 @@ class WeightQuantizerMXFP:
         return torch.gather(candidates, 1, torch.argmin(err, dim=1, keepdim=True))
 
     def quantize_mxfp4(self, W, window_size: int = 0, index: bool = False):
+        if _takes_mx_kernel(W, index, window_size):
+            q, scales = _quantize_mx(W, "mxfp4", layer_layout=False)
+            return q.view(-1, 32), scales.view(torch.float8_e8m0fnu)
         eps = 2.0 ** MX_EPS_EXP
         flat = W.reshape(-1, 32).float()
         ideal = flat.abs().amax(dim=1, keepdim=True) / 6
@@ -194,6 +253,9 @@ class WeightQuantizerMXFP:
         return W_q, scales.to(torch.float8_e8m0fnu)
 
     def quantize_nvfp4(self, W, window_size: int = 0, index: bool = False):
+        if _takes_mx_kernel(W, index, window_size):
+            q, scales = _quantize_mx(W, "nvfp4", layer_layout=False)
+            return q.view(-1, 16), scales.view(torch.float8_e4m3fn)
         eps, fp8 = 1e-6, torch.float8_e4m3fn
         flat = W.reshape(-1, 16).float()
         ideal = flat.abs().amax(dim=1, keepdim=True) / 6

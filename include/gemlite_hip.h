@@ -24,6 +24,7 @@
  *                                     (bit layout spec: pack_weights_over_cols_torch :36-60)
  *   gemlite_hip_unpack_over_cols   <- unpack_over_cols_triton, gemlite/bitpack.py:175-241
  *   gemlite_hip_quantize_groups    <- (no counterpart: the reference leaves float -> grouped INT to the third-party hqq package)
+ *   gemlite_hip_quantize_mx        <- gemlite/quant_utils.py  WeightQuantizerMXFP (torch ops there; one kernel here)
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer is a DEVICE pointer unless stated;
@@ -422,6 +423,40 @@ typedef struct gemlite_hip_quantize_args {
     int32_t reserved;     /* 0 */
 } gemlite_hip_quantize_args;
 int gemlite_hip_quantize_groups(const gemlite_hip_quantize_args* args, void* stream);
+
+/* Quantise float weights W[N, K] (fp32 / fp16 / bf16, unit inner stride, row stride ld_w >= K) to a block-scaled format in one launch
+ * on `stream`: no workspace, no atomics, 64-bit indices.  K % 32 == 0.  Every step is ONE fp32 IEEE operation (correctly rounded
+ * divisions, nothing contracts); amax = max |w| over the block:
+ *   format 0 MXFP8 / 1 MXFP4, block = 32 consecutive k of a row:  ideal = amax / qmax (448.f / 6.f);
+ *       ex = exponent_field(ideal) + (mantissa(ideal) != 0), clamped to [97, 254];  scale byte (e8m0) = ex, s = 2^(ex - 127)
+ *       (= the reference's 2^ceil(log2(ideal)) floored at 2^-30, taken from the bits: the bit form is the contract)
+ *     MXFP8 element: e4m3fn_rne(clamp(w / s, -448, 448))
+ *     MXFP4 element: q = w / s, c = #{0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0 strictly below |q|} (a midpoint takes the lower value),
+ *       code = c + 8 if q < 0 and c > 0, else c.  (NOT the activation quantiser's rule: no eighth threshold, and a negative weight
+ *       that rounds to zero is code 0, not 8.)
+ *   format 2 NVFP4, block = 16 k:  t = (amax / 6.f) / 0.05f (two divisions);  scale byte s8 = e4m3fn_rne(min(t, 448));
+ *       full = max(float(s8) * 0.05f, 1e-6f);  codes from q = w / full by the rule above (|q| > 7 under a clamped scale stays 7 / 15).
+ *   A block that holds a NaN or an Inf gets the scale format's NaN code (e8m0 0xFF, e4m3 0x7F); its element bytes are unspecified
+ *   (written, no fault); every other block is unaffected.
+ * q_out: MXFP8 e4m3 bytes [N][K]; fp4 formats: pack_nibbles 0 = one code per byte [N][K], 1 = two per byte [N][K/2], even k in the
+ * low nibble (what a packed layer stores); row stride ld_q bytes.  scales: one byte per block j of row n at
+ * j * stride_scale_g + n * stride_scale_n: (N, 1) is the layer's [K/g, N], (1, K/g) is [N * K/g, 1].
+ * Checked on the host before the launch: BAD_ARGUMENT (null pointers, struct_size, N / K <= 0, ld_w < K, ld_q below a row),
+ * UNSUPPORTED (format, dtype, pack_nibbles with MXFP8), BAD_SHAPE (K % 32 != 0, more than 65535 * 256 k). */
+typedef struct gemlite_hip_quantize_mx_args {
+    uint32_t struct_size; /* = sizeof(gemlite_hip_quantize_mx_args), ABI guard */
+    int32_t w_dtype;      /* GEMLITE_DT_FP32 / FP16 / BF16 */
+    const void* w;
+    int64_t N, K, ld_w;
+    int32_t format;       /* 0 MXFP8, 1 MXFP4, 2 NVFP4 */
+    int32_t pack_nibbles; /* 0 or 1 (fp4 formats only) */
+    void* q_out;
+    int64_t ld_q;
+    void* scales;
+    int64_t stride_scale_g, stride_scale_n;
+    int64_t reserved;     /* 0 */
+} gemlite_hip_quantize_mx_args;
+int gemlite_hip_quantize_mx(const gemlite_hip_quantize_mx_args* args, void* stream);
 
 #ifdef __cplusplus
 }
