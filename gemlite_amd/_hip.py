@@ -122,6 +122,39 @@ class QuantizeMxArgs(C.Structure):
     ]
 
 
+class DequantizeArgs(C.Structure):
+    """struct gemlite_hip_dequantize_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("out_dtype", C.c_int32),
+        ("w_q", C.c_void_p),
+        ("scales", C.c_void_p),
+        ("zeros", C.c_void_p),
+        ("out", C.c_void_p),
+        ("N", C.c_int64),
+        ("K", C.c_int64),
+        ("stride_wk", C.c_int64),
+        ("stride_wn", C.c_int64),
+        ("stride_meta_g", C.c_int64),
+        ("stride_meta_n", C.c_int64),
+        ("ld_out", C.c_int64),
+        ("W_nbits", C.c_int32),
+        ("group_size", C.c_int32),
+        ("elements_per_sample", C.c_int32),
+        ("w_pack_bits", C.c_int32),
+        ("w_dtype", C.c_int32),
+        ("input_dtype", C.c_int32),
+        ("meta_dtype", C.c_int32),
+        ("zeros_dtype", C.c_int32),
+        ("zero_is_scalar", C.c_int32),
+        ("W_group_mode", C.c_int32),
+        ("channel_scale_mode", C.c_int32),
+        ("post_scale", C.c_float),
+        ("reserved", C.c_int64),
+    ]
+
+
 BIAS_NOT_ADDED = 1  # gemlite_hip_forward_ex: launched without the bias, the caller adds it
 
 _lib = None
@@ -198,6 +231,8 @@ def load():
         lib.gemlite_hip_quantize_groups.argtypes = [C.POINTER(QuantizeArgs), C.c_void_p]
         lib.gemlite_hip_quantize_mx.restype = C.c_int
         lib.gemlite_hip_quantize_mx.argtypes = [C.POINTER(QuantizeMxArgs), C.c_void_p]
+        lib.gemlite_hip_dequantize.restype = C.c_int
+        lib.gemlite_hip_dequantize.argtypes = [C.POINTER(DequantizeArgs), C.c_void_p]
         if lib.gemlite_hip_abi_version() != ABI_VERSION:
             raise GemliteHipError("libgemlite_hip.so ABI version mismatch; rebuild it")
         _lib = lib
@@ -214,7 +249,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_capture_group_max", "gemlite_hip_capture_group_stats", "gemlite_hip_capture_group_compatible",
     "gemlite_hip_capture_group_grid_y",
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
-    "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx",
+    "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize",
 )
 
 

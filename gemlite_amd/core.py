@@ -25,7 +25,7 @@ from . import _hip
 from .bitpack import pack_weights_over_cols
 from .config import AUTOTUNE, KERNEL, MATMUL_DTYPES, set_autotune, set_kernel_caching  # noqa: F401 (re-exported)
 from .dtypes import (DTYPE_TO_TORCH, FP8_INT8_DTYPES, TORCH_TO_DTYPE, DType, is_mx_dtype)
-from .quant_utils import (scale_activations_mxfp4, scale_activations_mxfp8, scale_activations_nvfp4,
+from .quant_utils import (NVFP4_META_SCALE, scale_activations_mxfp4, scale_activations_mxfp8, scale_activations_nvfp4,
                           scale_activations_per_token)
 
 # the name the reference's own test file imports from gemlite.core (tests/test_gemlitelineartriton.py:6; the reference itself no
@@ -702,6 +702,42 @@ class GemLiteLinearHIP(torch.nn.Module):
         return [int(self.scaled_activations), self.W_nbits, self.group_size, self.unpack_mask,
                 self.elements_per_sample, self.input_dtype.value, self.output_dtype.value, self.acc_dtype.value,
                 self.meta_dtype.value, self.channel_scale_mode, self.W_group_mode, int(self.data_contiguous)]
+
+    # ------------------------------------------------------------------------------------ dequantize
+    def dequantize(self, dtype: Optional[torch.dtype] = None, out: Optional[Tensor] = None) -> Tensor:
+        """The weights this layer multiplies by, as [out_features, in_features] of `dtype` (fp16 / bf16 / fp32; default: the layer's
+        16-bit compute type): one `gemlite_hip_dequantize` launch on the current stream, from the stored tensors and metadata only
+        (contract: DESIGN §2.3).  For a dynamically quantised layer this is the weight side alone.  `out`: a [out_features, in_features]
+        tensor or row-strided view of `dtype` to write into.  GPU layers only, like forward."""
+        W_q, scales, zeros = self.get_tensor_args()
+        _hip.require_gpu_tensor(W_q, "W_q")
+        meta = self.get_meta_args()
+        if dtype is None and out is not None:
+            dtype = out.dtype
+        elif dtype is None:  # the layer's 16-bit compute type: of its activations, or (dynamically quantised layers) of its output
+            dtype = DTYPE_TO_TORCH[meta[5]]
+            if dtype not in (torch.float16, torch.bfloat16):
+                dtype = DTYPE_TO_TORCH[meta[6]]
+        if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            raise NotImplementedError(f"dequantize to {dtype}: the result is float16, bfloat16 or float32")
+        s = _static_args(W_q, scales, zeros, meta)
+        N, K = int(s.N), int(s.K)
+        if out is None:
+            out = torch.empty((N, K), dtype=dtype, device=W_q.device)
+        elif tuple(out.shape) != (N, K) or out.dtype != dtype or out.device != W_q.device or (K > 1 and out.stride(1) != 1):
+            raise ValueError(f"out should be a [{N}, {K}] {dtype} tensor on {W_q.device} with unit stride along in_features")
+        a = _hip.DequantizeArgs()
+        a.struct_size = _hip.C.sizeof(_hip.DequantizeArgs)
+        for f in ("w_q", "scales", "zeros", "N", "K", "stride_wk", "stride_wn", "stride_meta_g", "stride_meta_n", "W_nbits", "group_size",
+                  "elements_per_sample", "w_pack_bits", "w_dtype", "input_dtype", "meta_dtype", "zeros_dtype", "zero_is_scalar",
+                  "W_group_mode", "channel_scale_mode"):
+            setattr(a, f, getattr(s, f))
+        a.out, a.out_dtype, a.ld_out = out.data_ptr(), TORCH_TO_DTYPE[dtype].value, (out.stride(0) if N > 1 else max(K, out.stride(0)))
+        a.post_scale = NVFP4_META_SCALE if meta[5] == DType.NVFP4.value else 1.0  # the fixed second-level scale of an NVFP4 layer
+        with _hip.on_device(W_q.device):
+            rc = _hip.load().gemlite_hip_dequantize(_hip.C.byref(a), _hip.current_stream_handle(W_q.device))
+        _hip.raise_for_status(rc, "gemlite_hip_dequantize")
+        return out
 
     # --------------------------------------------------------------------------------------- forward
     def _call(self, x: Tensor, matmul_type: int) -> Tensor:

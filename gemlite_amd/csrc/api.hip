@@ -58,6 +58,9 @@ const void* pack32_kernel_fn();
 const void* unpack_kernel_fn();
 const void* quantize_groups_kernel_fn(bool onepass);
 const void* quantize_mx_kernel_fn(int format);
+const void* dequantize_words_kernel_fn(int nbits);
+const void* dequantize_rows_kernel_fn(int fmt);
+const void* dequantize_any_kernel_fn();
 // capture_group.hip: independent decode3 launches of one stream capture folded into one grouped launch
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
@@ -942,7 +945,7 @@ int gemlite_hip_abi_version(void) { return GEMLITE_HIP_ABI_VERSION; }
 
 const char* gemlite_hip_build_info(void) {
     return "libgemlite_hip gfx950 (CDNA4) abi=1 kernels: gemv_wn, gemv_decode, gemv_mfma, gemv_a8wn, gemm_wn_rows, gemm_wn_direct, gemm_wn_stream, gemm_wn_mma, gemm_wn_tiled, gemm_a8w8, "
-           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups, quantize_mx"
+           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups, quantize_mx, dequantize"
 #ifdef GL_AB_KERNELS
            " +ab_kernels"
 #endif
@@ -1287,6 +1290,91 @@ int gemlite_hip_quantize_mx(const gemlite_hip_quantize_mx_args* a, void* stream)
     if (gx > 0x7FFFFFFF || gy > 65535) return GEMLITE_ERR_BAD_SHAPE;
     void* kargs[] = {(void*)&p};
     return launch(quantize_mx_kernel_fn(a->format), dim3((unsigned)gx, (unsigned)gy, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
+}
+
+// everything is checked before the launch (host only: testable without a device)
+int gemlite_hip_dequantize(const gemlite_hip_dequantize_args* a, void* stream) {
+    if (!a || a->struct_size != sizeof(gemlite_hip_dequantize_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (!a->w_q || !a->out) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (a->N <= 0 || a->K <= 0 || a->group_size <= 0 || a->elements_per_sample <= 0 || a->ld_out < a->K) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (!(a->out_dtype == GEMLITE_DT_FP16 || a->out_dtype == GEMLITE_DT_BF16 || a->out_dtype == GEMLITE_DT_FP32)) return GEMLITE_ERR_UNSUPPORTED;
+    const int e = a->elements_per_sample, nb = a->W_nbits;
+    DequantParams p{};
+    bool grouped = false;
+    if (is_mx_input(a->input_dtype)) {
+        const bool nv = a->input_dtype == GEMLITE_DT_NVFP4;
+        if (!a->scales) return GEMLITE_ERR_BAD_ARGUMENT;
+        if (nb == 8) {
+            if (nv || a->input_dtype == GEMLITE_DT_MXFP4 || e != 1 || a->w_dtype != GEMLITE_DT_FP8E4) return GEMLITE_ERR_UNSUPPORTED;
+            p.fmt = DQ_MXFP8;
+        } else if (nb == 4) {
+            if (!(e == 1 || (e == 2 && a->w_pack_bits == 8))) return GEMLITE_ERR_UNSUPPORTED;
+            p.fmt = nv ? DQ_NVFP4 : DQ_MXFP4;
+        } else {
+            return GEMLITE_ERR_UNSUPPORTED;
+        }
+        if (a->group_size != (nv ? 16 : 32)) return GEMLITE_ERR_UNSUPPORTED;
+        if (a->K % 32 != 0) return GEMLITE_ERR_BAD_SHAPE;
+        p.w_dt = e == 1 && nb == 8 ? GEMLITE_DT_FP8E4 : GEMLITE_DT_UINT8;
+        p.pack_bits = e == 2 ? 8 : 0;
+        p.group = a->group_size;
+    } else {
+        if (a->W_group_mode < 0 || a->W_group_mode > 4) return GEMLITE_ERR_UNSUPPORTED;
+        if (a->channel_scale_mode < 0 || a->channel_scale_mode > 3) return GEMLITE_ERR_UNSUPPORTED;
+        p.w_mode = a->W_group_mode;
+        p.chan = a->channel_scale_mode == 1 || a->channel_scale_mode == 3;
+        const bool need_s = p.w_mode >= 2 || p.chan, need_z = p.w_mode == 1 || p.w_mode >= 3;
+        if ((need_s && !a->scales) || (need_z && !a->zeros)) return GEMLITE_ERR_BAD_ARGUMENT;
+        if (e > 1) {
+            if (a->w_pack_bits == 64) return GEMLITE_ERR_UNSUPPORTED;
+            if (!(nb == 1 || nb == 2 || nb == 4 || nb == 8)) return GEMLITE_ERR_UNSUPPORTED;
+            if (!(a->w_pack_bits == 8 || a->w_pack_bits == 16 || a->w_pack_bits == 32) || nb * e != a->w_pack_bits) return GEMLITE_ERR_BAD_ARGUMENT;
+        } else {
+            const int dt = a->w_dtype;
+            if (!(dt == GEMLITE_DT_INT8 || dt == GEMLITE_DT_UINT8 || dt == GEMLITE_DT_FP8E4 || dt == GEMLITE_DT_FP8E5 || dt == GEMLITE_DT_FP16 ||
+                  dt == GEMLITE_DT_BF16 || dt == GEMLITE_DT_FP32))
+                return GEMLITE_ERR_UNSUPPORTED;  // (the *NUZ fp8 types are the MI300X formats)
+        }
+        const auto meta_ok = [](int dt) { return dt == GEMLITE_DT_FP16 || dt == GEMLITE_DT_BF16 || dt == GEMLITE_DT_FP32; };
+        if (need_s && !meta_ok(a->meta_dtype)) return GEMLITE_ERR_UNSUPPORTED;
+        if (need_z && !(a->zero_is_scalar ? (a->zeros_dtype == GEMLITE_DT_INT32 || meta_ok(a->zeros_dtype)) : meta_ok(a->zeros_dtype))) return GEMLITE_ERR_UNSUPPORTED;
+        if (a->K % e != 0) return GEMLITE_ERR_BAD_SHAPE;
+        grouped = p.w_mode >= 2 || (need_z && !a->zero_is_scalar);
+        if (grouped && a->K % a->group_size != 0) return GEMLITE_ERR_BAD_SHAPE;
+        p.fmt = DQ_INT;
+        p.w_dt = a->w_dtype;
+        p.pack_bits = e > 1 ? a->w_pack_bits : 0;
+        p.group = grouped ? a->group_size : (int)(a->K > 0x7FFFFFFF ? 0x7FFFFFFF : a->K);  // no group metadata: one group, never indexed
+    }
+    if (a->N > 0x7FFFFFFFll * 64 || a->K > 65535ll * 256) return GEMLITE_ERR_BAD_SHAPE;
+    p.w = a->w_q; p.scales = a->scales; p.zeros = a->zeros; p.out = a->out;
+    p.N = a->N; p.K = a->K; p.stride_wk = a->stride_wk; p.stride_wn = a->stride_wn;
+    p.stride_meta_g = a->stride_meta_g; p.stride_meta_n = a->stride_meta_n; p.ld_out = a->ld_out;
+    p.nbits = nb; p.e = e;
+    p.meta_dt = a->meta_dtype; p.zeros_dt = a->zeros_dtype; p.zero_is_scalar = a->zero_is_scalar != 0;
+    p.out_dt = a->out_dtype; p.post = a->post_scale;
+
+    const int osz = a->out_dtype == GEMLITE_DT_FP32 ? 4 : 2;
+    const bool out_vec = ((uintptr_t)a->out % 16 == 0) && ((a->ld_out * osz) % 16 == 0) && a->K % 8 == 0;
+    const void* fn = nullptr;
+    if (out_vec && p.fmt == DQ_INT && e > 1 && a->w_pack_bits == 32 && a->stride_wn == 1 && a->stride_wk >= a->N && (uintptr_t)a->w_q % 4 == 0 &&
+        (!grouped || a->group_size % 8 == 0)) {
+        fn = dequantize_words_kernel_fn(nb);
+    } else if (out_vec && a->stride_wk == 1) {
+        const bool bytes8 = (uintptr_t)a->w_q % 8 == 0 && a->stride_wn % 8 == 0, bytes4 = (uintptr_t)a->w_q % 4 == 0 && a->stride_wn % 4 == 0;
+        if (p.fmt == DQ_INT) {
+            const int dt = a->w_dtype;
+            const bool one_byte = e == 1 && (dt == GEMLITE_DT_INT8 || dt == GEMLITE_DT_UINT8 || dt == GEMLITE_DT_FP8E4 || dt == GEMLITE_DT_FP8E5);
+            if (one_byte && bytes8 && a->stride_wn >= a->K && (!grouped || a->group_size % 8 == 0)) fn = dequantize_rows_kernel_fn(DQ_INT);
+        } else if (e == 2 ? (bytes4 && a->stride_wn >= a->K / 2) : (bytes8 && a->stride_wn >= a->K)) {
+            fn = dequantize_rows_kernel_fn(p.fmt);
+        }
+    }
+    void* kargs[] = {(void*)&p};
+    if (fn) return launch(fn, dim3((unsigned)((a->N + 63) / 64), (unsigned)((a->K + 255) / 256), 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
+    const int64_t blocks = (a->N * a->K + 255) / 256;
+    if (blocks > 0x7FFFFFFF) return GEMLITE_ERR_BAD_SHAPE;
+    return launch(dequantize_any_kernel_fn(), dim3((unsigned)blocks, 1, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

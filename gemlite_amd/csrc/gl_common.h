@@ -550,6 +550,22 @@ struct QuantGroupsParams {
     int w_dt, meta_dt, nbits, group, pack32, fold;
 };
 
+// parameter block of the weight dequantiser (dequantize.hip)
+enum { DQ_INT = 0, DQ_MXFP8 = 1, DQ_MXFP4 = 2, DQ_NVFP4 = 3 };
+struct DequantParams {
+    const void* w;       // packed words [K/e, N], or unpacked elements, at j * stride_wk + n * stride_wn (elements of the word / element type)
+    const void* scales;  // element (g, n) at g * stride_meta_g + n * stride_meta_n; block-scaled formats: one byte per block
+    const void* zeros;
+    void* out;           // [N, ld_out] fp16 / bf16 / fp32
+    int64_t N, K, stride_wk, stride_wn, stride_meta_g, stride_meta_n, ld_out;
+    int nbits, e, pack_bits;  // e == 1: unpacked (fp4 codes: one per byte)
+    int w_dt, meta_dt, zeros_dt, zero_is_scalar, group, w_mode;
+    int chan;            // multiply by the channel scale scales[n * stride_meta_n]
+    int fmt;             // DQ_*
+    int out_dt;
+    float post;          // one more multiply when != 1
+};
+
 // host-side launch description produced by the dispatcher
 // How many blocks of a one-block-per-CU kernel are resident at once on the current device (its CU count; 256 until a device
 // has been seen).  Kernels whose blocks WAIT for each other (reduce-scatter combine) are only planned within this limit.

@@ -6,7 +6,8 @@ int8 rounded with floor(v + 0.5) — the rounding the reference's kernel uses on
 Runs as one HIP kernel (`gemlite_hip_scale_activations_per_token`).
 
 ``WeightQuantizerINT``: float weights -> grouped asymmetric INT codes + (scale, zero) per group, one HIP kernel
-(`gemlite_hip_quantize_groups`; the reference leaves this step to the third-party ``hqq`` package).
+(`gemlite_hip_quantize_groups`; the reference leaves this step to the third-party ``hqq`` package), and back (``dequantize``:
+`gemlite_hip_dequantize`, DESIGN §2.3, which ``WeightQuantizerMXFP.dequantize`` takes too for GPU tensors).
 
 Block-scaled formats (reference: gemlite/quant_utils.py:21-225 weight quantiser, :502-954 activation quantisers):
 ``WeightQuantizerMXFP`` (GPU float weights: one HIP kernel, `gemlite_hip_quantize_mx`; CPU tensors, the scale-search
@@ -20,7 +21,7 @@ from typing import Tuple
 import torch
 
 from . import _hip
-from .dtypes import TORCH_TO_DTYPE
+from .dtypes import TORCH_TO_DTYPE, DType
 
 
 def get_dtype_range(dtype: torch.dtype) -> Tuple[float, float]:
@@ -118,6 +119,49 @@ class WeightQuantizerINT:
     def quantize_packed(self, W: torch.Tensor, fold_zeros: bool):
         """The layer's own tensors in one launch: 32-bit words [K/e, N], scales and (folded) zeros [K/g, N]."""
         return _quantize_groups(W, self.W_nbits, self.group_size, self.meta_dtype(W), packed=True, fold_zeros=fold_zeros)
+
+    def dequantize(self, W_q: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor, shape=None, dtype=None, fold_zeros: bool = False):
+        """The float weights [N, K] the tensors of ``quantize()`` (uint8 codes [N, K], metadata [N * K/g, 1]: (q - z) * s) or of
+        ``quantize_packed()`` (int32 words [K/e, N], metadata [K/g, N]; ``fold_zeros`` as it was given there: fma(q, s, z')) stand for,
+        in one `gemlite_hip_dequantize` launch (DESIGN §2.3).  ``dtype``: float16 / bfloat16 / float32, default the metadata's type;
+        ``shape``: (N, K) of flat uint8 codes, and the shape of the result."""
+        _hip.require_gpu_tensor(W_q, "W_q")
+        dev = W_q.device
+        dtype = scales.dtype if dtype is None else dtype
+        a = _hip.DequantizeArgs()
+        if W_q.dtype == torch.int32:
+            assert W_q.dim() == 2, "packed W_q should be [K / elements_per_sample, N]"
+            e = 32 // self.W_nbits
+            N, K = W_q.shape[1], W_q.shape[0] * e
+            g = K // (scales.numel() // N)
+            scales, zeros = scales.view(K // g, N), zeros.view(K // g, N)
+            a.elements_per_sample, a.w_pack_bits, a.w_dtype = e, 32, TORCH_TO_DTYPE[torch.int32].value
+            a.stride_wk, a.stride_wn = W_q.stride(0), W_q.stride(1)
+            a.stride_meta_g, a.stride_meta_n = scales.stride(0), scales.stride(1)
+            a.W_group_mode = 4 if fold_zeros else 3
+        else:
+            assert W_q.dtype == torch.uint8, "W_q should be uint8 codes [N, K] or int32 words [K / elements_per_sample, N]"
+            W_q = W_q.view(tuple(shape)) if (shape is not None and W_q.dim() != 2) else W_q
+            assert W_q.dim() == 2, "flat codes need shape=(N, K)"
+            N, K = W_q.shape
+            g = (N * K) // scales.numel()
+            scales, zeros = scales.reshape(N, K // g), zeros.reshape(N, K // g)
+            a.elements_per_sample, a.w_pack_bits, a.w_dtype = 1, 0, TORCH_TO_DTYPE[torch.uint8].value
+            a.stride_wk, a.stride_wn = W_q.stride(1), W_q.stride(0)
+            a.stride_meta_g, a.stride_meta_n = scales.stride(1), scales.stride(0)
+            a.W_group_mode = 3
+        assert zeros.stride() == scales.stride(), "scales and zeros should share one layout"
+        out = torch.empty((N, K), dtype=dtype, device=dev)
+        a.struct_size = _hip.C.sizeof(_hip.DequantizeArgs)
+        a.w_q, a.scales, a.zeros, a.out = W_q.data_ptr(), scales.data_ptr(), zeros.data_ptr(), out.data_ptr()
+        a.N, a.K, a.ld_out, a.W_nbits, a.group_size = N, K, K, self.W_nbits, g
+        a.out_dtype, a.input_dtype = TORCH_TO_DTYPE[dtype].value, TORCH_TO_DTYPE[dtype].value
+        a.meta_dtype, a.zeros_dtype = TORCH_TO_DTYPE[scales.dtype].value, TORCH_TO_DTYPE[zeros.dtype].value
+        a.post_scale = 1.0
+        with _hip.on_device(dev):
+            rc = _hip.load().gemlite_hip_dequantize(_hip.C.byref(a), _hip.current_stream_handle(dev))
+        _hip.raise_for_status(rc, "gemlite_hip_dequantize")
+        return out if shape is None else out.view(tuple(shape))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -278,7 +322,45 @@ class WeightQuantizerMXFP:
             W_q = self.to_index(W_q)
         return W_q, scales
 
+    def _dequantize_kernel(self, W_q, scales, shape, dtype):
+        """One `gemlite_hip_dequantize` launch for what the kernel takes — GPU e4m3 elements or uint8 e2m1 codes with e8m0 scales per 32
+        or e4m3 scales per 16, to fp16 / bf16 / fp32 — bit-identical to the torch code below; None for everything else.  Elements and
+        scales are walked flat, as rows of a power-of-two length that divides them."""
+        import math
+        if not (W_q.is_cuda and scales.is_cuda and W_q.device == scales.device and dtype in _MX_KERNEL_DTYPES
+                and W_q.is_contiguous() and scales.is_contiguous() and scales.numel() > 0):
+            return None
+        fp8 = W_q.dtype == torch.float8_e4m3fn
+        if not (fp8 or W_q.dtype == torch.uint8) or W_q.numel() % scales.numel() != 0:
+            return None
+        group = W_q.numel() // scales.numel()
+        if scales.dtype == torch.float8_e8m0fnu and group == 32:
+            in_dt = DType.MXFP8.value if fp8 else DType.MXFP4.value
+        elif scales.dtype == torch.float8_e4m3fn and group == 16 and not fp8:
+            in_dt = DType.NVFP4.value
+        else:
+            return None
+        K = math.gcd(W_q.numel(), 8192)
+        if K % 32 != 0:
+            return None
+        N = W_q.numel() // K
+        out = torch.empty((N, K), dtype=dtype, device=W_q.device)
+        a = _hip.DequantizeArgs()
+        a.struct_size = _hip.C.sizeof(_hip.DequantizeArgs)
+        a.w_q, a.scales, a.out = W_q.data_ptr(), scales.data_ptr(), out.data_ptr()
+        a.N, a.K, a.ld_out, a.stride_wk, a.stride_wn, a.stride_meta_g, a.stride_meta_n = N, K, K, 1, K, 1, K // group
+        a.W_nbits, a.group_size, a.elements_per_sample, a.w_pack_bits = (8 if fp8 else 4), group, 1, 0
+        a.w_dtype, a.input_dtype, a.out_dtype = TORCH_TO_DTYPE[W_q.dtype].value, in_dt, TORCH_TO_DTYPE[dtype].value
+        a.meta_dtype, a.post_scale = TORCH_TO_DTYPE[torch.uint8].value, 1.0
+        with _hip.on_device(W_q.device):
+            rc = _hip.load().gemlite_hip_dequantize(_hip.C.byref(a), _hip.current_stream_handle(W_q.device))
+        _hip.raise_for_status(rc, "gemlite_hip_dequantize")
+        return out.view(-1, group) if shape is None else out.view(shape)
+
     def dequantize(self, W_q, scales, shape=None, dtype=None):
+        out = self._dequantize_kernel(W_q, scales, shape, self.compute_dtype if dtype is None else dtype)
+        if out is not None:
+            return out
         if W_q.dtype == torch.uint8:  # e2m1 codes
             _, _, values = _fp4_tables(W_q.device)
             W_q = values[W_q.int()]

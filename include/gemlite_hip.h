@@ -25,6 +25,7 @@
  *   gemlite_hip_unpack_over_cols   <- unpack_over_cols_triton, gemlite/bitpack.py:175-241
  *   gemlite_hip_quantize_groups    <- (no counterpart: the reference leaves float -> grouped INT to the third-party hqq package)
  *   gemlite_hip_quantize_mx        <- gemlite/quant_utils.py  WeightQuantizerMXFP (torch ops there; one kernel here)
+ *   gemlite_hip_dequantize         <- (no counterpart for a packed layer; WeightQuantizerMXFP.dequantize is torch ops on the quantiser's return)
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer is a DEVICE pointer unless stated;
@@ -457,6 +458,47 @@ typedef struct gemlite_hip_quantize_mx_args {
     int64_t reserved;     /* 0 */
 } gemlite_hip_quantize_mx_args;
 int gemlite_hip_quantize_mx(const gemlite_hip_quantize_mx_args* args, void* stream);
+
+/* Dequantise a layer's weights: out[n, k] (fp16 / bf16 / fp32, K-contiguous, row stride ld_out >= K elements) = the weight the layer
+ * multiplies x[:, k] by for output n, from the layer's stored tensors only.  The weight fields mean what they mean in
+ * gemlite_hip_forward_args, so a caller fills both structs from one layer.  Every step is ONE fp32 IEEE operation (nothing contracts),
+ * then one round-to-nearest-even conversion to out_dtype (overflow gives Inf, NaN stays NaN):
+ *   integer / plain layers (q = the code of the packed word, or the int8 / uint8 / fp8 e4m3fn / fp8 e5m2 / 16- / 32-bit float element, exact)
+ *     W_group_mode 0: d = q | 1: d = q - z | 2: d = q * s | 3: d = (q - z) * s | 4: d = fmaf(q, s, z') (z' = the stored folded zero)
+ *       s, z: element (k / group_size, n) of scales / zeros at g * stride_meta_g + n * stride_meta_n; zero_is_scalar: z = zeros[0]
+ *     channel_scale_mode 1 or 3: d = d * c[n], c[n] = scales[n * stride_meta_n] (the layer's [1, N] weight scale); 0 and 2: nothing
+ *   block-scaled layers (input_dtype GEMLITE_DT_MXFP16 .. GEMLITE_DT_NVFP4; W_group_mode / channel_scale_mode / zeros ignored)
+ *     MXFP8 (W_nbits 8, w_dtype FP8E4, group 32) / MXFP4 (W_nbits 4, group 32):  d = elem * 2^(b - 127), b = the e8m0 byte, 0xFF -> NaN
+ *     NVFP4 (input_dtype NVFP4, W_nbits 4, group 16):  d = elem * float(s8), s8 = the e4m3 byte (exact product; a NaN byte -> NaN)
+ *     fp4 codes: elements_per_sample 2 = two per byte, even k in the low nibble (the layer); 1 = one code per byte (the quantiser's return)
+ *   post_scale != 1.0f: d = d * post_scale, one more multiply (0.05f for an NVFP4 layer; 1.0f keeps the quantiser-level value)
+ * Non-finite metadata propagates to the elements it belongs to and nowhere else.  One launch on `stream`, no workspace, no atomics,
+ * 64-bit addresses.  32-bit words with stride_wn == 1, group_size % 8 == 0 and a 16-byte aligned out / row pitch take the tiled
+ * kernel; K-contiguous (stride_wk == 1) 8-bit elements and block-scaled bytes without a zero take the streaming kernel; every other
+ * layout (8- / 16-bit words, any strides, any group size that divides K, 16- / 32-bit float elements, unaligned out) takes a plain
+ * per-element kernel.  Checked on the host before the launch: BAD_ARGUMENT (null pointers, struct_size, N / K / group_size /
+ * elements_per_sample <= 0, ld_out < K, missing scales / zeros for the mode, words that do not hold elements_per_sample codes),
+ * UNSUPPORTED (dtypes, bit width, modes, a *NUZ fp8, 64-bit words, a block-scaled combination that is no format),
+ * BAD_SHAPE (K not a multiple of elements_per_sample / group_size / the block size, grid limits). */
+typedef struct gemlite_hip_dequantize_args {
+    uint32_t struct_size; /* = sizeof(gemlite_hip_dequantize_args), ABI guard */
+    int32_t out_dtype;    /* GEMLITE_DT_FP16 / BF16 / FP32 */
+    const void* w_q;
+    const void* scales;
+    const void* zeros;
+    void* out;
+    int64_t N, K;
+    int64_t stride_wk, stride_wn;
+    int64_t stride_meta_g, stride_meta_n;
+    int64_t ld_out;
+    int32_t W_nbits, group_size, elements_per_sample, w_pack_bits, w_dtype;
+    int32_t input_dtype;  /* selects the block-scaled formats, as for forward; anything else: an integer / plain layer */
+    int32_t meta_dtype, zeros_dtype, zero_is_scalar;
+    int32_t W_group_mode, channel_scale_mode;
+    float post_scale;
+    int64_t reserved;     /* 0 */
+} gemlite_hip_dequantize_args;
+int gemlite_hip_dequantize(const gemlite_hip_dequantize_args* args, void* stream);
 
 #ifdef __cplusplus
 }
