@@ -204,6 +204,8 @@ def load():
         lib.gemlite_hip_capture_group_compatible.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardArgs)]
         lib.gemlite_hip_capture_group_grid_y.restype = C.c_int
         lib.gemlite_hip_capture_group_grid_y.argtypes = [C.c_int32, C.c_int32]
+        lib.gemlite_hip_capture_group_wave_split.restype = None
+        lib.gemlite_hip_capture_group_wave_split.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 3)]
         lib.gemlite_hip_forward_ex.restype = C.c_int
         lib.gemlite_hip_forward_ex.argtypes = [C.POINTER(ForwardArgs), C.POINTER(ForwardExt), C.c_void_p]
         lib.gemlite_hip_bias_fused.restype = C.c_int
@@ -247,7 +249,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_pack_over_cols",
     "gemlite_hip_unpack_over_cols",
     "gemlite_hip_capture_group_max", "gemlite_hip_capture_group_stats", "gemlite_hip_capture_group_compatible",
-    "gemlite_hip_capture_group_grid_y",
+    "gemlite_hip_capture_group_grid_y", "gemlite_hip_capture_group_wave_split",
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
     "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize",
 )

@@ -1003,6 +1003,13 @@ int gemlite_hip_capture_group_grid_y(int32_t tiles, int32_t members) {
     return (tiles > 0 && members > 0) ? decode3_group_grid_y(tiles, members, 256) : 0;
 }
 
+void gemlite_hip_capture_group_wave_split(int32_t layers_in_block, int32_t wave, int32_t out[3]) {
+    if (!out) return;
+    Decode3WaveSplit s{-1, 0, 0};
+    if (layers_in_block >= 1 && layers_in_block <= DECODE3_GMAX && wave >= 0 && wave < 16) s = decode3_wave_split(layers_in_block, wave);
+    out[0] = s.layer; out[1] = s.v0; out[2] = s.v1;
+}
+
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b) {
     if (validate(a) != GEMLITE_OK || validate(b) != GEMLITE_OK) return 0;
     Resolved ra, rb;

@@ -10,8 +10,10 @@
 //   * the next decode3 launch joins the open group when NOTHING else was captured on the stream since (the stream's only dependency is the
 //     group's node), kernel / shape / strides / modes agree, and its output overlaps no member's inputs or output and no member's output
 //     overlaps its inputs (a bias the kernel adds itself — gemlite_hip_forward_ext — is one more input).  Joining rewrites the node to gemv_w4_decode3_kernel<.., Decode3GroupTable>, grid (tiles, Y) with
-//     Y = clamp(resident blocks / tiles, 1, members): one resident block per tile streams its members one after the other, narrow layers
-//     spread them over the CUs their tiles leave idle.  No node is added and the stream's dependency set stays as it is.
+//     Y = clamp(resident blocks / tiles, 1, members): one resident block per tile holds its members ALL AT ONCE — each member gets
+//     16 / (members of the block) of the block's waves and its own 4 KB of LDS, and the block has one barrier (decode3_wave_split,
+//     gl_common.h; gemv_decode.hip) — and narrow layers spread their members over the CUs their tiles leave idle.  No node is added and
+//     the stream's dependency set stays as it is.
 //
 // The graph stays LINEAR on one queue.  Sound because nothing foreign lies between A and B on the stream: B's stream-order dependencies are
 // A plus A's own, and independence from A makes A's own sufficient; everything captured later depends on the group node and so on every
@@ -28,9 +30,9 @@
 namespace gl {
 
 const void* gemv_w4_decode3_fn(int tag, bool nt);        // gemv_decode.hip
-const void* gemv_w4_decode3_group_fn(int tag, bool nt);  // gemv_decode.hip
+const void* gemv_w4_decode3_group_fn(int tag);           // gemv_decode.hip: default-policy weight loads whatever the members' launches use
 const void* gemv_w4_decode3_bias_fn(int tag, bool nt);        // the forms that add a bias in the epilogue: a group holds one kind only
-const void* gemv_w4_decode3_bias_group_fn(int tag, bool nt);  // (the kernel functions differ, so same_launch() keeps them apart)
+const void* gemv_w4_decode3_bias_group_fn(int tag);            // (the kernel functions differ, so same_launch() keeps them apart)
 
 namespace {
 
@@ -92,10 +94,10 @@ bool same_launch(const LaunchPlan& a, const LaunchPlan& b) {
 const void* group_fn_of(const void* fn) {
     for (int tag = 0; tag < 2; ++tag)
         for (int nt = 0; nt < 2; ++nt)
-            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_fn(tag, nt != 0);
+            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_fn(tag);
     for (int tag = 0; tag < 2; ++tag)
         for (int nt = 0; nt < 2; ++nt)
-            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_bias_group_fn(tag, nt != 0);
+            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_bias_group_fn(tag);
     return nullptr;
 }
 

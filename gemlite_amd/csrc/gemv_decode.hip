@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "gl_common.h"
+#include "gl_async.h"  // gvw: counted asm requests, ring2_run (the grouped form)
 
 namespace gl {
 
@@ -41,10 +42,10 @@ constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
 // Tail = unsigned*: the single-layer kernel, `counters` is the timeline buffer.
 // Tail = Decode3GroupTable: the GROUPED form — up to DECODE3_GMAX independent layers of identical shape, strides, modes and dtype
 // (capture_group.hip folds back-to-back independent launches of a stream capture into one such launch).  Grid (N / 16, Y): block
-// (tile, y) stays resident and STREAMS the layers y, y + Y, ... of its tile through a ring of DECODE3_RING chunk buffers, so wave start is
-// paid once per group and a layer's first-byte latency and reduce + store run under the following layers' stream (the comment at the
-// loop has the details).  Member count and Y come in `modes`.  Layer 0's pointers are the preloaded scalars; the others come out of
-// the by-value table behind the 14 dwords with scalar loads.  Per layer the arithmetic is the single-layer code in the same order, so
+// (tile, y) holds the layers y, y + Y, ... of its tile, all at once: each layer gets 16 / (layers in the block) waves and its own 4 KB
+// of LDS, and the block has ONE barrier (the comment at the loop has the details).  Member count and Y come in `modes`.  Layer 0's
+// pointers are the preloaded scalars; the others come out of the by-value table behind the 14 dwords with scalar loads, once per
+// wave.  Per layer the arithmetic is the single-layer code in the same order, so
 // every layer's output is bit-identical to its own launch.  No timeline probe in a group.  The single-layer instantiation is untouched:
 // dependent chains, eager launches and profiled launches run it.
 // Tail = Decode3BiasTail / Decode3BiasGroupTable: the same two forms with the bias add in the epilogue (gl_common.h has the arithmetic).
@@ -67,7 +68,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
     constexpr int WP = SUBN ? 2 : 1;  // 4-bit fields per 16-bit window (Window<Tag, 4>::WP of gemv_wn.hip)
     constexpr int R = 2, NW = 16, CHUNK = 32, TC = 16, CSTRIDE = NW * CHUNK;
     constexpr int RED = NW * 4 * TC;
-    __shared__ __attribute__((aligned(16))) float red[(GROUPED ? 2 : 1) * RED];  // [NW * 4 DPP rows][16 columns] (grouped: x layer parity)
+    __shared__ __attribute__((aligned(16))) float red[(GROUPED ? DECODE3_GMAX : 1) * RED];  // [NW * 4 DPP rows][16 columns] (grouped: x the layers a block can hold, 64 KiB)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -121,7 +122,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
     stamp(1);
 
     float tot[4] = {0.f, 0.f, 0.f, 0.f};
-    float scalar_zero = 0.f;  // (grouped: taken from the ring, per item)
+    float scalar_zero = 0.f;  // (grouped: read once per wave, from its own layer)
     if constexpr (!GROUPED) scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
     const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
     const bool b_times_s = w_mode == 3;
@@ -130,7 +131,9 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
 #pragma unroll
     for (int i = 0; i < WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
 
-    auto compute = [&](const Chunk& ck) {
+    // full = std::true_type: the caller knows need_s && need_z (the grouped loop's common case), the two selects are compiled out
+    auto compute = [&](const Chunk& ck, auto full) {
+        constexpr bool FULL = decltype(full)::value;
         // fp16: the second field of a 16-bit window is read 4 bits up (16 q * 2^-24 as an fp16 subnormal).  Its products go to their
         // own accumulator and the 2^-4 is applied ONCE to the fp32 sum, so nothing is ever rounded: rounds 2-3 (and the first decode3)
         // scaled the matching x pairs by 2^-4 in fp16 instead, which lost mantissa bits for |x| < 2^-10 (1.8e-3 of mean |y|
@@ -170,8 +173,10 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         float z[4] = {TR::to_float((uint16_t)(z0 & 0xFFFFu)), TR::to_float((uint16_t)(z0 >> 16)), TR::to_float((uint16_t)(z1 & 0xFFFFu)), TR::to_float((uint16_t)(z1 >> 16))};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (!need_s) s[j] = 1.f;
-            if (!need_z) z[j] = scalar_zero;
+            if constexpr (!FULL) {
+                if (!need_s) s[j] = 1.f;
+                if (!need_z) z[j] = scalar_zero;
+            }
             const float a = s[j] * QSCALE;
             const float b = bz * z[j] * (b_times_s ? s[j] : 1.f);
             float v = acc[0][j];
@@ -185,7 +190,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
     if constexpr (!GROUPED) {
 #pragma unroll 1
         for (int ch = 0; ch < nchunks; ++ch) {
-            compute(cur);
+            compute(cur, std::false_type{});
             if (ch + 1 < nchunks) {
                 cur = nxt;
                 if (ch + 2 < nchunks) load_chunk(nxt, ch + 2);
@@ -222,129 +227,122 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         }
         stamp(3);
     } else {
-        // One block streams the layers y, y + Y, ... of its 16-column tile.  A wave's work is the flattened sequence of (layer, chunk)
-        // items; it keeps DECODE3_RING chunk buffers and asks for item i + DECODE3_RING when it is done with item i, so block start is
-        // paid once per group and the first-byte latency of the next layers and the reduce + store of this one run under the stream.
-        // The item loop is unrolled by the ring depth.  The loads are hipcc's own.  What it makes of this: the
-        // waits in front of an item's arithmetic are counted and leave the newer items out; the request is hoisted to the START of the
-        // arithmetic into one more set of registers, and each trip of the unrolled loop ends in copies that rotate the sets behind one
-        // vmcnt(0).  (Requests from inline asm with counted waits met the same rotation, with copies of registers hipcc does not count.)
-        constexpr int D = DECODE3_RING;
+        // One block holds the layers y, y + Y, ... of its 16-column tile — LB of them, ALL in flight at once: decode3_wave_split()
+        // (gl_common.h) gives every layer 16 / LB waves, and a wave takes the place of a contiguous run of the single-layer kernel's waves
+        // ("virtual waves": virtual wave v is the chunks v, v + 16, ... below nch_total, each with the rows and x bytes the single-layer
+        // wave v reads).  Nothing orders the waves of a block before the one barrier at the end, so a CU's waves wait for memory and do
+        // arithmetic at different times.  A wave's items — its virtual waves in ascending order, each one's chunks in ascending order — are
+        // a flat list of known length: gvw::ring2_run (gl_async.h) with five counted asm requests per item (w, w, x, s, z).  Every base is
+        // a uniform SGPR pair moved by scalar arithmetic, every per-lane offset is set up once: the loop holds no vector address
+        // arithmetic and no select.  Bit-exact: `tot` accumulates a virtual wave's chunks in ascending order; at its end the two row_ror
+        // sums, the partial row v * 4 + (lane >> 4) of the LAYER'S OWN 4 KB of LDS, `tot` back to zero (a virtual wave without a chunk
+        // writes zeros: K < 4096); after the barrier waves 0 .. LB - 1 each run the single-layer epilogue on one layer's region.
         const int members = (int)((modes >> 16) & 255u), Y = (int)(modes >> 24), y = (int)blockIdx.y;
-        // layer L: the preloaded scalars (L = 0) or the by-value table, scalar loads either way
-        auto fetch_in = [&](int L, const char*& w_, const char*& x_, const char*& s_, const char*& z_) {
-            if (L > 0) {
-                const Decode3Member& m = counters.m[L - 1];
-                w_ = m.w; x_ = m.x; s_ = m.s; z_ = m.z;
-            } else {
-                w_ = wb; x_ = xb; s_ = sp; z_ = zp;
-            }
+        const int LB = (members - y + Y - 1) / Y;
+        const Decode3WaveSplit split = decode3_wave_split(LB, wave);
+        const int li = split.layer < 0 ? 0 : split.layer, v0 = split.v0, v1 = split.v1;
+        // this wave's layer: the preloaded scalars (layer 0) or the by-value table, scalar loads either way, once per wave
+        const int L = y + li * Y;
+        const char *w_ = wb, *x_ = xb, *s_ = sp, *z_ = zp;
+        if (L > 0) {
+            const Decode3Member& m = counters.m[L - 1];
+            w_ = m.w; x_ = m.x; s_ = m.s; z_ = m.z;
+        }
+        // (a scalar load, read ahead of the first request: a load hipcc tracks inside the counted ring would bring the full drain back)
+        if (modes & M_ZSCALAR) scalar_zero = (float)((const int32_t*)z_)[0];
+        // per-lane byte offsets, fixed for the whole launch.  Metadata row of chunk gc, lane g: ((gc * 32 + 2 g) * 8) >> gs_shift
+        // = (gc << 8 >> gs_shift) + (16 g >> gs_shift) for groups up to 256, gc >> (gs_shift - 8) for larger ones (16 g < 256)
+        const uint32_t vw0 = (uint32_t)(g * R) * sw4 + n0 * 4u, vw1 = vw0 + sw4, vx = (uint32_t)lane * 8u;
+        const uint32_t vm = (gs_shift < 8 ? (uint32_t)(g * R * 8) >> gs_shift : 0u) * mstride2 + n0 * 2u;
+        // (absent metadata is still requested — the first bytes of the weight buffer — so every item is five requests)
+        const uint32_t vs = need_s ? vm : 0u, vz = need_z ? vm : 0u, ms_s = need_s ? mstride2 : 0u, ms_z = need_z ? mstride2 : 0u;
+        const char *sb = need_s ? s_ : w_, *zb = need_z ? z_ : w_;
+        const int shl = gs_shift < 8 ? 8 - gs_shift : 0, shr = gs_shift > 8 ? gs_shift - 8 : 0;
+        const uint32_t chunk_w = (uint32_t)CHUNK * sw4;
+        const int nv = v1 - v0, rem = (nch_total & (NW - 1)) - v0;
+        const int n = (nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem));  // items of this wave (0: an idle wave, or K too short)
+        float* rd = red + li * RED;
+
+        constexpr int NLC = 5;
+        int rv = v0, rgc = v0;  // request cursor: virtual wave, chunk
+        auto request = [&](Chunk& ck, int) __attribute__((always_inline)) {
+            const char* wq = w_ + (uint32_t)rgc * chunk_w;
+            gvw::gld128<NT>(ck.w[0], wq, vw0);
+            gvw::gld128<NT>(ck.w[1], wq, vw1);
+            gvw::gld64(ck.xq, x_ + (uint32_t)rgc * (uint32_t)(CHUNK * 16), vx);
+            const uint32_t grp = ((uint32_t)rgc << shl) >> shr;
+            gvw::gld64(ck.s, sb + grp * ms_s, vs);
+            gvw::gld64(ck.z, zb + grp * ms_z, vz);
+            rgc += NW;
+            if (rgc >= nch_total) rgc = ++rv;
         };
-        // (a scalar zero point rides in the ring as well, in the `z` slot no mode with a scalar zero uses: the aligned 8 bytes that hold it
-        // — same page, cannot fault — and `zhi` says which half it is.  Waiting for a scalar load of it would stall every layer.)
-        auto fetch_out = [&](int L, uint16_t*& o_, const uint16_t*& b_, bool& zhi) {
-            const char* z_ = zp;
-            o_ = out;
-            if (L > 0) {
-                const Decode3Member& m = counters.m[L - 1];
-                o_ = m.out; z_ = m.z;
-            }
-            if constexpr (BIASED) b_ = counters.bias[L];
-            zhi = ((uintptr_t)z_ & 4u) != 0;
+        auto tie_chunk = [&](Chunk& ck) __attribute__((always_inline)) {
+            gvw::tie(ck.w[0]);
+            gvw::tie(ck.w[1]);
+            gvw::tie(ck.xq);
+            gvw::tie(ck.s);
+            gvw::tie(ck.z);
         };
-        // `live` = false: the sequence has ended; the request still goes out, to the first bytes of the last layer's buffers (one cached
-        // line each), so every item carries exactly one request
-        auto request = [&](Chunk& ck, const char* w_, const char* x_, const char* s_, const char* z_, int chunk, bool live) {
-            const uint32_t wo = wo0 + (uint32_t)(chunk * CSTRIDE) * sw4;
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const u32x4* src = (const u32x4*)(w_ + (live ? wo + (uint32_t)i * sw4 : 0u));
-                ck.w[i] = NT ? __builtin_nontemporal_load(src) : *src;
-            }
-            ck.xq = *(const u32x2*)(x_ + (live ? xo0 + (uint32_t)(chunk * CSTRIDE) * 16u : 0u));
-            const uint32_t row = row0 + (uint32_t)(chunk * CSTRIDE);
-            const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
-            const char* zs_ = (modes & M_ZSCALAR) ? z_ - ((uintptr_t)z_ & 7u) : w_;  // (pointer arithmetic: the address space stays global)
-            ck.s = *(const u32x2*)((need_s ? s_ : w_) + ((need_s && live) ? mo : 0u));
-            ck.z = *(const u32x2*)((need_z ? z_ : zs_) + ((need_z && live) ? mo : 0u));
-        };
-        // a layer's end, the single-layer code on LDS half `rd`: DPP row sums, partials to LDS, one barrier, wave 0 sums and stores
-        auto reduce_store = [&](float* rd, uint16_t* dst, const uint16_t* bsrc) {
-            uint16_t braw = 0;
-            if constexpr (BIASED) {
-                if (wave == 0 && lane < 16) braw = bsrc[tile * TC + lane];
-            }
+        // a virtual wave's end, the single-layer code: DPP row sums, the partial row to the layer's LDS region
+        auto flush = [&](int v) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float v = tot[j];
-                v += dpp_movf<0x124>(v);  // row_ror:4
-                v += dpp_movf<0x128>(v);  // row_ror:8
-                tot[j] = v;
+                float t = tot[j];
+                t += dpp_movf<0x124>(t);  // row_ror:4
+                t += dpp_movf<0x128>(t);  // row_ror:8
+                tot[j] = t;
             }
-            if ((lane & 12) == 0) *(f32x4*)(rd + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
-            __syncthreads();
-            if (wave == 0) {
-                constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
-                const int o = lane & 15, part = lane >> 4;
-                float v = 0.f;
+            if ((lane & 12) == 0) *(f32x4*)(rd + ((v * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
 #pragma unroll
-                for (int r = 0; r < PER; ++r) v += rd[(part * PER + r) * TC + o];
-                v += __shfl_xor(v, 16);
-                v += __shfl_xor(v, 32);
-                uint16_t h = TR::from_float(v);
-                if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));  // (as in the single-layer form)
-                if (lane < 16) dst[tile * TC + o] = h;
-            }
+            for (int j = 0; j < 4; ++j) tot[j] = 0.f;
         };
-
-        uint16_t* lout;
-        const uint16_t* lbias = nullptr;
-        bool zhi;
-        int par = 0;  // LDS half of the layer being summed: one barrier per layer is enough (a wave that writes half p again has passed
-                      // the barrier of the layer between, which wave 0 enters only after it has read half p)
-        if (nchunks == 0) {  // a wave without rows (K < 8192): zeros to the sum, and the barrier of every layer
-#pragma unroll 1
-            for (int L = y; L < members; L += Y, par ^= 1) {
-                fetch_out(L, lout, lbias, zhi);
-                reduce_store(red + par * RED, lout, lbias);
-            }
-            return;
-        }
-        // request cursor: runs D items ahead of the compute cursor
-        int rL = y, rch = 0;
-        const char *rw, *rx, *rs, *rz;
-        fetch_in(rL, rw, rx, rs, rz);
-        Chunk ring[D];
-        auto request_next = [&](Chunk& ck) {
-            request(ck, rw, rx, rs, rz, rch, rL < members);
-            if (++rch == nchunks) {  // the next layer's pointers: asked for one item before they are used
-                rch = 0;
-                rL += Y;
-                if (rL < members) fetch_in(rL, rw, rx, rs, rz);
-            }
-        };
-#pragma unroll
-        for (int b = 0; b < D; ++b) request_next(ring[b]);
-        int cL = y, cch = 0;
-        fetch_out(cL, lout, lbias, zhi);
-#pragma unroll 1
-        for (;;) {
-#pragma unroll
-            for (int b = 0; b < D; ++b) {
-                if (modes & M_ZSCALAR) scalar_zero = (float)(int32_t)(zhi ? ring[b].z[1] : ring[b].z[0]);
-                compute(ring[b]);
-                request_next(ring[b]);
-                if (++cch == nchunks) {
-                    reduce_store(red + par * RED, lout, lbias);
-                    cch = 0;
-                    par ^= 1;
-                    cL += Y;
-                    if (cL >= members) return;
-                    fetch_out(cL, lout, lbias, zhi);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) tot[j] = 0.f;
+        int cv = v0, cgc = v0;  // compute cursor
+        // (the first two requests belong to the variant that consumes them: requested ahead of the branch, their registers — still in
+        // flight — were COPIED into each variant's own set in front of its loop)
+        auto run = [&](auto full) {
+            Chunk A, B;
+            if (n > 0) request(A, 0);
+            if (n > 1) request(B, 1);
+            gvw::ring2_run<NLC>(n, A, B, request, tie_chunk, [&](const Chunk& ck, int) __attribute__((always_inline)) {
+                compute(ck, full);
+                cgc += NW;
+                if (cgc >= nch_total) {
+                    flush(cv);
+                    cgc = ++cv;
                 }
+            });
+        };
+        // (scales and zeros both present — every A16W4 layer quantised with a zero tensor: the selects are compiled out)
+        if (need_s && need_z) run(std::true_type{}); else run(std::false_type{});
+        if (split.layer >= 0) {
+#pragma unroll 1
+            for (int v = cv; v < v1; ++v) flush(v);  // virtual waves without a chunk
+        }
+
+        // waves 0 .. LB - 1 finish one layer each; they ask for its bias element in front of the barrier
+        const bool fin = wave < LB;
+        uint16_t* o_ = out;
+        uint16_t braw = 0;
+        if (fin) {
+            const int Lf = y + wave * Y;
+            if (Lf > 0) o_ = counters.m[Lf - 1].out;
+            if constexpr (BIASED) {
+                if (lane < 16) braw = counters.bias[Lf][tile * TC + lane];
             }
+        }
+        __syncthreads();
+        if (fin) {
+            const float* rf = red + wave * RED;
+            constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
+            const int o = lane & 15, part = lane >> 4;
+            float v = 0.f;
+#pragma unroll
+            for (int r = 0; r < PER; ++r) v += rf[(part * PER + r) * TC + o];
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            uint16_t h = TR::from_float(v);
+            if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));  // (as in the single-layer form)
+            if (lane < 16) o_[tile * TC + o] = h;
         }
     }
 }
@@ -357,10 +355,12 @@ const void* gemv_w4_decode3_fn(int tag, bool nt) {
     return (const void*)k;
 }
 
-const void* gemv_w4_decode3_group_fn(int tag, bool nt) {
+// The grouped forms exist with default-policy weight loads only (NT = false), whatever the members' own launches use: the two 16-column
+// tiles of a 128-byte line run on one XCD, and with a block's waves out of step the partner asks for its half some time later — a
+// non-temporal line has left the L2 by then (11.6 MB fetched per layer against 9.5; profiles/r13/decode_group_waves.log §2).
+const void* gemv_w4_decode3_group_fn(int tag) {
     typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3GroupTable);
-    kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true, Decode3GroupTable> : gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTable>)
-                     : (nt ? gemv_w4_decode3_kernel<bf16_tag, true, Decode3GroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTable>);
+    kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTable>;
     return (const void*)k;
 }
 
@@ -371,10 +371,9 @@ const void* gemv_w4_decode3_bias_fn(int tag, bool nt) {
     return (const void*)k;
 }
 
-const void* gemv_w4_decode3_bias_group_fn(int tag, bool nt) {
+const void* gemv_w4_decode3_bias_group_fn(int tag) {
     typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3BiasGroupTable);
-    kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true, Decode3BiasGroupTable> : gemv_w4_decode3_kernel<half_tag, false, Decode3BiasGroupTable>)
-                     : (nt ? gemv_w4_decode3_kernel<bf16_tag, true, Decode3BiasGroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3BiasGroupTable>);
+    kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3BiasGroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3BiasGroupTable>;
     return (const void*)k;
 }
 

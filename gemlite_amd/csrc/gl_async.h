@@ -112,6 +112,64 @@ __device__ __forceinline__ uint32_t lds_addr_of(const unsigned char* p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)p;
 }
 
-
 }  // namespace async
+
+// Round 6 ("GEMV family onto counted asm loads"): the chunk requests of gemv_wn_kernel (and, round 13, of the grouped gemv_w4_decode3_kernel) are inline-asm global loads
+// retired with hand-counted s_waitcnt (the head of this file has the reasoning; scripts/isa_asmloads.py replays the generated code).  With the loads
+// left to hipcc, every instantiation carried a full `s_waitcnt vmcnt(0)` at the head of its two-chunk loop: the chunk requested a moment
+// before was waited for in full before the arithmetic on the OLDER chunk could start — one memory latency per loop iteration with nothing
+// overlapped.  Uniform base + 32-bit byte offset per lane, as before.
+namespace gvw {
+template <bool NT>
+__device__ __forceinline__ void gld128(u32x4& d, const char* base, uint32_t voff) {
+    if constexpr (NT) asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(d) : "v"(voff), "s"(base) : "memory");
+    else asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(d) : "v"(voff), "s"(base) : "memory");
+}
+__device__ __forceinline__ void gld64(u32x2& d, const char* base, uint32_t voff) {
+    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(d) : "v"(voff), "s"(base) : "memory");
+}
+__device__ __forceinline__ void gld32(uint32_t& d, const char* base, uint32_t voff) {
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(d) : "v"(voff), "s"(base) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <typename T>
+__device__ __forceinline__ void tie(T& v) { asm volatile("" : "+v"(v)); }
+
+// Two chunk buffers A / B, one chunk in flight while the other is computed on.  NLC = requests per chunk.  On entry A holds chunk 0 and B
+// chunk 1 (requested by the caller, those that exist).  Steady state: unconditional requests, ONE wait value ("everything but the newest
+// chunk has landed": loads return in order); the last one to three chunks are peeled, their waits picked by uniform branches.
+template <int NLC, typename Buf, typename Issue, typename Tie, typename Compute>
+__device__ __forceinline__ void ring2_run(int n, Buf& A, Buf& B, Issue&& issue, Tie&& tie_buf, Compute&& compute) {
+    int i = 0;
+#pragma unroll 1
+    for (; i + 4 <= n; i += 2) {
+        wait_vm<NLC>();
+        tie_buf(A);
+        compute(A, i);
+        issue(A, i + 2);
+        wait_vm<NLC>();
+        tie_buf(B);
+        compute(B, i + 1);
+        issue(B, i + 3);
+    }
+    const int rem = n - i;  // 0 (no chunk at all), 1, 2 or 3
+    if (rem >= 1) {
+        if (rem >= 2) wait_vm<NLC>(); else wait_vm<0>();
+        tie_buf(A);
+        compute(A, i);
+        if (rem >= 2) {
+            if (rem == 3) { issue(A, i + 2); wait_vm<NLC>(); } else wait_vm<0>();
+            tie_buf(B);
+            compute(B, i + 1);
+            if (rem == 3) {
+                wait_vm<0>();
+                tie_buf(A);
+                compute(A, i + 2);
+            }
+        }
+    }
+}
+}  // namespace gvw
+
 }  // namespace gl

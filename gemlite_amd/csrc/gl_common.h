@@ -609,22 +609,29 @@ struct Decode3BiasGroupTable {
 inline uint32_t decode3_group_modes(uint32_t modes, int members, int grid_y) {
     return (modes & 0xFFFFu) | ((uint32_t)members << 16) | ((uint32_t)grid_y << 24);
 }
-// grid.y of a grouped launch of `members` layers of `tiles` 16-column tiles each: block (tile, y) streams the layers y, y + grid.y, ...
-// one after the other.  One block per CU is resident, so a wide layer (tiles >= resident) gets one block per tile that walks every
-// member; a narrow one spreads its members over the CUs its tiles leave idle.
+// grid.y of a grouped launch of `members` layers of `tiles` 16-column tiles each: block (tile, y) holds the layers y, y + grid.y, ...
+// One block per CU is resident, so a wide layer (tiles >= resident) gets one block per tile that holds every member; a narrow one
+// spreads its members over the CUs its tiles leave idle.
 inline int decode3_group_grid_y(int64_t tiles, int members, int64_t resident) {
     const int64_t y = tiles > 0 ? resident / tiles : 1;
     return (int)(y < 1 ? 1 : (y > members ? (members > 1 ? members : 1) : y));
+}
+// How the 16 waves of a grouped block share its `lb` layers (1 .. DECODE3_GMAX), all in flight at once: P = 16 / lb waves per layer,
+// wave w works on block-local layer w / P (the waves past lb * P have no work) and, inside it, takes the place of the single-layer kernel's
+// waves [v0, v1) — "virtual waves", a contiguous share of 16: virtual wave v is the chunks v, v + 16, ... of the layer.
+struct Decode3WaveSplit {
+    int layer;   // block-local layer, -1: the wave has no items
+    int v0, v1;  // its virtual waves [v0, v1)
+};
+GL_HD Decode3WaveSplit decode3_wave_split(int lb, int wave) {
+    const int P = 16 / lb, li = wave / P, wl = wave - li * P;
+    if (li >= lb) return Decode3WaveSplit{-1, 0, 0};
+    return Decode3WaveSplit{li, wl * 16 / P, (wl + 1) * 16 / P};
 }
 // Waves per SIMD the compiler must keep resident for the grouped kernel (the second __launch_bounds__ argument of HIP).  One 1024-thread
 // block is 4 waves per SIMD = 128 VGPRs per lane (two blocks per CU, 64 VGPRs, spill: profiles/r07/capture_groups.log)
 #ifndef DECODE3_GROUP_WAVES_PER_SIMD
 #define DECODE3_GROUP_WAVES_PER_SIMD 4
-#endif
-// Chunk buffers per wave of the grouped kernel in the source: item i + DECODE3_RING is asked for when item i is done (hipcc adds one
-// more register set by hoisting that request).  2 and 3 were measured, 2 is the faster (profiles/r08/decode_group_stream.log §2).
-#ifndef DECODE3_RING
-#define DECODE3_RING 2
 #endif
 
 // scalar kernel arguments of gemm_w4_rows_kernel (gemm_wn_rows.hip): the same 14 preloaded dwords, then M and the row strides

@@ -176,7 +176,8 @@ typedef struct gemlite_hip_forward_args {
      *   packed GEMV (M = 1)        [0] 2/3/4 = 16-/32-/64-column tiles   [1] K slices   [2] 4/8/16 waves per block
      *                              (82 = 8 waves, 2 rows per lane; 48 = 4 waves, 8 rows per lane)   [3] & 3: 1 = x through LDS,
      *                              2 = x direct; & 16 = the round-2 kernel instead of the 16-column decode kernel,
-     *                              & 32 = default-policy (not non-temporal) weight loads in the decode kernel,
+     *                              & 32 = default-policy (not non-temporal) weight loads in the decode kernel (single-layer launches; a grouped launch under
+     *                              capture always uses the default policy),
      *                              & 4096 = the round-3 decode kernel (struct arguments) instead of gemv_w4_decode3_kernel
      *   MFMA GEMV (M = 1..4, 4- and 2-bit words under 16-bit activations; default where it measured faster)
      *                              [0] 21/22/24 = 16-/32-/64-column tiles   [2] 4/8/16 waves per block
@@ -332,11 +333,16 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
  *   _stats       process-wide counts: decode launches seen under capture, and how many of them joined a node instead of adding one
  *   _compatible  host only, nothing is dereferenced: 1 if launch `b` captured directly behind launch `a` would join it, else 0
  *   _grid_y      host only: the grid.y rule for a grouped launch of `members` layers of `tiles` 16-column tiles (N / 16), answered for
- *                a full 256-CU part: clamp(256 / tiles, 1, members) (a launch uses its own device's CU count in place of 256); block (tile, y) streams the layers y, y + grid.y, ...  0 for a non-positive argument */
+ *                a full 256-CU part: clamp(256 / tiles, 1, members) (a launch uses its own device's CU count in place of 256); block (tile, y) holds the layers y, y + grid.y, ...  0 for a non-positive argument
+ *   _wave_split  host only: how the 16 waves of a grouped block share its `layers_in_block` layers (1 .. 16), which are all in flight at
+ *                once: out = {block-local layer of `wave` (-1: the wave has no work), v0, v1} — the wave does what the single-layer
+ *                kernel's waves v0 .. v1 - 1 do for that layer (wave v there: the 32-row chunks v, v + 16, ... of K / 8 packed rows).
+ *                16 / layers_in_block waves per layer.  {-1, 0, 0} for an argument out of range */
 int gemlite_hip_capture_group_max(void);
 void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
 int gemlite_hip_capture_group_grid_y(int32_t tiles, int32_t members);
+void gemlite_hip_capture_group_wave_split(int32_t layers_in_block, int32_t wave, int32_t out[3]);
 
 /* Bias in the launch (optional extension; gemlite_hip_forward_args and every entry point above are unchanged).  The M = 1 decode kernel
  * (gemv_w4_decode3_kernel, single and grouped) and the few-row kernels (gemm_w4_rows_kernel / gemm_w2_rows_kernel) have forms that add a

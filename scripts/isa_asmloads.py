@@ -18,12 +18,17 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_loops as L
 
-FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel")
+FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", "Decode3GroupTable", "Decode3BiasGroupTable")
 # gemv_wn_kernel (round 6: gvw::ring2_run): the prologue requests up to two chunks behind uniform branches and the last one to three chunks run in
 # straight-line code BEHIND the loop — replayed in address order (no branch is followed), prologue and tail included, every conditional request
 # issued and every run of alternative waits taken at its weakest member
-LINEAR_WITH_TAIL = ("gemv_wn_kernel",)
-ALTERNATIVE_WAITS = ("gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel")
+# Decode3GroupTable / Decode3BiasGroupTable (round 13): the grouped forms of gemv_w4_decode3_kernel, named by their table argument — the single-layer
+# forms keep hipcc's own loads.  The kernel holds gvw::ring2_run TWICE (metadata selects compiled in / out), each copy with its own first requests, loop and
+# peeled tail, each ending drained.  What the replay covers: the copy whose loop is picked (most v_dot2; the first on a tie) is replayed with its
+# wrap-around trips; the OTHER copy is replayed in address order only — first requests, ONE trip of its loop, its tail — so a touch that only a second
+# trip of that copy's loop would show is not seen.  (Both copies are the same source with one `if constexpr` apart.)
+LINEAR_WITH_TAIL = ("gemv_wn_kernel", "Decode3GroupTable", "Decode3BiasGroupTable")
+ALTERNATIVE_WAITS = ("gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", "Decode3GroupTable", "Decode3BiasGroupTable")
 VREG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 
 
