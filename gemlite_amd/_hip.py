@@ -101,6 +101,20 @@ class QuantizeArgs(C.Structure):
     ]
 
 
+class QuantizeHqqArgs(C.Structure):
+    """struct gemlite_hip_quantize_hqq_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("iters", C.c_int32),
+        ("q", QuantizeArgs),
+        ("lp_norm", C.c_float),
+        ("beta", C.c_float),
+        ("kappa", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
 class QuantizeMxArgs(C.Structure):
     """struct gemlite_hip_quantize_mx_args (field order/types must match the header)."""
 
@@ -231,6 +245,8 @@ def load():
             C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
         lib.gemlite_hip_quantize_groups.restype = C.c_int
         lib.gemlite_hip_quantize_groups.argtypes = [C.POINTER(QuantizeArgs), C.c_void_p]
+        lib.gemlite_hip_quantize_groups_hqq.restype = C.c_int
+        lib.gemlite_hip_quantize_groups_hqq.argtypes = [C.POINTER(QuantizeHqqArgs), C.c_void_p]
         lib.gemlite_hip_quantize_mx.restype = C.c_int
         lib.gemlite_hip_quantize_mx.argtypes = [C.POINTER(QuantizeMxArgs), C.c_void_p]
         lib.gemlite_hip_dequantize.restype = C.c_int
@@ -251,7 +267,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_capture_group_max", "gemlite_hip_capture_group_stats", "gemlite_hip_capture_group_compatible",
     "gemlite_hip_capture_group_grid_y", "gemlite_hip_capture_group_wave_split",
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
-    "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize",
+    "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize", "gemlite_hip_quantize_groups_hqq",
 )
 
 

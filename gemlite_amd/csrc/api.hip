@@ -57,6 +57,7 @@ const void* pack_kernel_fn();
 const void* pack32_kernel_fn();
 const void* unpack_kernel_fn();
 const void* quantize_groups_kernel_fn(bool onepass);
+const void* quantize_hqq_kernel_fn(bool onepass);
 const void* quantize_mx_kernel_fn(int format);
 const void* dequantize_words_kernel_fn(int nbits);
 const void* dequantize_rows_kernel_fn(int fmt);
@@ -945,7 +946,7 @@ int gemlite_hip_abi_version(void) { return GEMLITE_HIP_ABI_VERSION; }
 
 const char* gemlite_hip_build_info(void) {
     return "libgemlite_hip gfx950 (CDNA4) abi=1 kernels: gemv_wn, gemv_decode, gemv_mfma, gemv_a8wn, gemm_wn_rows, gemm_wn_direct, gemm_wn_stream, gemm_wn_mma, gemm_wn_tiled, gemm_a8w8, "
-           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups, quantize_mx, dequantize"
+           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups, quantize_mx, dequantize, quantize_hqq"
 #ifdef GL_AB_KERNELS
            " +ab_kernels"
 #endif
@@ -1249,8 +1250,8 @@ int gemlite_hip_unpack_over_cols(const void* packed, uint8_t* out, int64_t N, in
     return launch(unpack_kernel_fn(), dim3((unsigned)((total + 255) / 256), 1, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
 }
 
-// everything is checked before the launch (host only: testable without a device)
-int gemlite_hip_quantize_groups(const gemlite_hip_quantize_args* a, void* stream) {
+// everything is checked before the launch (host only: testable without a device).  h: the optimiser's constants (quantize_hqq_kernel), or null
+static int quantize_groups_launch(const gemlite_hip_quantize_args* a, const QuantHqqParams* h, void* stream) {
     if (!a || a->struct_size != sizeof(gemlite_hip_quantize_args)) return GEMLITE_ERR_BAD_ARGUMENT;
     if (!a->w || !a->q_out || !a->scales || !a->zeros) return GEMLITE_ERR_BAD_ARGUMENT;
     if (a->N <= 0 || a->K <= 0 || a->group_size <= 0 || a->ld_w < a->K) return GEMLITE_ERR_BAD_ARGUMENT;
@@ -1274,8 +1275,23 @@ int gemlite_hip_quantize_groups(const gemlite_hip_quantize_args* a, void* stream
     p.pack32 = a->pack_bits == 32; p.fold = a->fold_zeros != 0;
     const int64_t gx = (a->N + 63) / 64, gy = (a->K + p.span - 1) / p.span;
     if (gx > 0x7FFFFFFF || gy > 65535) return GEMLITE_ERR_BAD_SHAPE;
+    if (h) {
+        void* hargs[] = {(void*)&p, (void*)h};
+        return launch(quantize_hqq_kernel_fn(p.span == 256), dim3((unsigned)gx, (unsigned)gy, 1), dim3(256, 1, 1), hargs, 0, (hipStream_t)stream);
+    }
     void* kargs[] = {(void*)&p};
     return launch(quantize_groups_kernel_fn(p.span == 256), dim3((unsigned)gx, (unsigned)gy, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
+}
+
+int gemlite_hip_quantize_groups(const gemlite_hip_quantize_args* a, void* stream) { return quantize_groups_launch(a, nullptr, stream); }
+
+int gemlite_hip_quantize_groups_hqq(const gemlite_hip_quantize_hqq_args* a, void* stream) {
+    if (!a || a->struct_size != sizeof(gemlite_hip_quantize_hqq_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (a->iters < 0 || a->iters > 100) return GEMLITE_ERR_BAD_ARGUMENT;
+    const float inf = __builtin_inff();  // (every comparison below is false for NaN)
+    if (!(a->lp_norm > 0.f && a->lp_norm <= 1.f) || !(a->beta > 0.f && a->beta < inf) || !(a->kappa > 0.f && a->kappa < inf)) return GEMLITE_ERR_BAD_ARGUMENT;
+    const QuantHqqParams h{a->iters, a->lp_norm, a->beta, a->kappa};
+    return quantize_groups_launch(&a->q, &h, stream);
 }
 
 // everything is checked before the launch (host only: testable without a device)

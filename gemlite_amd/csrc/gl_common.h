@@ -550,6 +550,12 @@ struct QuantGroupsParams {
     int w_dt, meta_dt, nbits, group, pack32, fold;
 };
 
+// the optimiser's constants for quantize_hqq_kernel (quantize_groups.hip), beside a QuantGroupsParams
+struct QuantHqqParams {
+    int iters;
+    float lp_norm, beta, kappa;
+};
+
 // parameter block of the weight dequantiser (dequantize.hip)
 enum { DQ_INT = 0, DQ_MXFP8 = 1, DQ_MXFP4 = 2, DQ_NVFP4 = 3 };
 struct DequantParams {

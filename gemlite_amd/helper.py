@@ -7,7 +7,8 @@ A4W4_MXFP_dynamic, A4W4_NVFP_dynamic), ``patch_model``, ``cleanup_linear``.  The
 reads the attributes the reference reads, and the raw-tensor entry points take exactly what
 ``HQQLinear.unpack()`` / ``meta`` hold.
 The ``*_RTN_INT`` subclasses of the ``*_HQQ_INT`` family (not in the reference) quantise an ``nn.Linear`` themselves, on the GPU:
-round to nearest on each group's min / max, HQQ's starting point (``from_linear``, ``quantize_weights``).
+round to nearest on each group's min / max, HQQ's starting point (``from_linear``, ``quantize_weights``); their ``*_HQQOPT_INT``
+subclasses add HQQ's zero-point optimiser to the same launch.
 On gfx950 FP8 means OCP e4m3fn (the reference's HIP default e4m3fnuz, helper.py:13-15, is the MI300X format).
 """
 from typing import Optional
@@ -17,7 +18,7 @@ import torch
 from . import _hip
 from .core import GemLiteLinear, select_modes
 from .dtypes import TORCH_TO_DTYPE, DType
-from .quant_utils import WeightQuantizerINT, WeightQuantizerMXFP, _takes_mx_kernel, check_group_size
+from .quant_utils import WeightQuantizerHQQ, WeightQuantizerINT, WeightQuantizerMXFP, _takes_mx_kernel, check_group_size
 
 default_fp8 = torch.float8_e4m3fn
 default_post_scale = True  # channel-wise scaling applied after the K reduction (reference HIP default)
@@ -200,8 +201,11 @@ class _RTNGroupQuant:
         _hip.require_gpu_tensor(weight, "weight")
         self.device = weight.device
         g = self._group_size_for(weight.shape[1], group_size, f"{name} ({weight.shape[0]} x {weight.shape[1]})")
-        quantizer = WeightQuantizerINT(self.W_nbits, g, dtype=self.dtype, device=weight.device)
-        return self._layer_from_float(weight, bias, quantizer)
+        return self._layer_from_float(weight, bias, self._make_quantizer(g, weight.device))
+
+    def _make_quantizer(self, group_size: int, device) -> WeightQuantizerINT:
+        """The quantiser a subclass quantises with (``quantize`` / ``quantize_packed`` / ``meta_dtype`` / ``group_size``)."""
+        return WeightQuantizerINT(self.W_nbits, group_size, dtype=self.dtype, device=device)
 
     def _layer_from_float(self, weight, bias, quantizer) -> GemLiteLinear:
         W_q, scales, zeros = quantizer.quantize(weight)
@@ -275,6 +279,63 @@ class A8W4_RTN_INT_dynamic(A8Wn_RTN_INT_dynamic):
 
 
 class A8W2_RTN_INT_dynamic(A8Wn_RTN_INT_dynamic):
+    W_nbits = 2
+
+
+class _HQQGroupQuant:
+    """The optimiser's keywords and the quantiser hook of the ``*_HQQOPT_INT`` processors: ``WeightQuantizerHQQ`` in the place of
+    ``WeightQuantizerINT``, everything else (group size handling, the one-launch packed route) is the RTN parent's."""
+
+    def _set_optimizer(self, iters, lp_norm, beta, kappa):
+        self.iters, self.lp_norm, self.beta, self.kappa = iters, lp_norm, beta, kappa
+
+    def _make_quantizer(self, group_size: int, device) -> WeightQuantizerINT:
+        return WeightQuantizerHQQ(self.W_nbits, group_size, dtype=self.dtype, device=device, iters=self.iters, lp_norm=self.lp_norm,
+                                  beta=self.beta, kappa=self.kappa)
+
+
+class A16Wn_HQQOPT_INT(_HQQGroupQuant, A16Wn_RTN_INT):
+    """``A16Wn_RTN_INT`` with HQQ's zero-point optimiser inside the quantising launch: still one launch per layer, the
+    layer is tensor for tensor ``from_weights(*WeightQuantizerHQQ(...).quantize(W), ...)``."""
+
+    def __init__(self, device="cuda:0", dtype=None, packing_bitwidth=None, post_scale=default_post_scale, W_nbits=None,
+                 group_size=None, iters=20, lp_norm=0.7, beta=10.0, kappa=1.01):
+        super().__init__(device=device, dtype=dtype, packing_bitwidth=packing_bitwidth, post_scale=post_scale, W_nbits=W_nbits,
+                         group_size=group_size)
+        self._set_optimizer(iters, lp_norm, beta, kappa)
+
+
+class A16W8_HQQOPT_INT(A16Wn_HQQOPT_INT):
+    W_nbits = 8
+
+
+class A16W4_HQQOPT_INT(A16Wn_HQQOPT_INT):
+    W_nbits = 4
+
+
+class A16W2_HQQOPT_INT(A16Wn_HQQOPT_INT):
+    W_nbits = 2
+
+
+class A16W1_HQQOPT_INT(A16Wn_HQQOPT_INT):
+    W_nbits = 1
+
+
+class A8Wn_HQQOPT_INT_dynamic(_HQQGroupQuant, A8Wn_RTN_INT_dynamic):
+    """``A8Wn_RTN_INT_dynamic`` with HQQ's zero-point optimiser inside the quantising launch."""
+
+    def __init__(self, device="cuda:0", packing_bitwidth=None, dtype=None, post_scale=default_post_scale, fp8=default_fp8,
+                 fp32_scale=False, W_nbits=None, group_size=None, iters=20, lp_norm=0.7, beta=10.0, kappa=1.01):
+        super().__init__(device=device, packing_bitwidth=packing_bitwidth, dtype=dtype, post_scale=post_scale, fp8=fp8,
+                         fp32_scale=fp32_scale, W_nbits=W_nbits, group_size=group_size)
+        self._set_optimizer(iters, lp_norm, beta, kappa)
+
+
+class A8W4_HQQOPT_INT_dynamic(A8Wn_HQQOPT_INT_dynamic):
+    W_nbits = 4
+
+
+class A8W2_HQQOPT_INT_dynamic(A8Wn_HQQOPT_INT_dynamic):
     W_nbits = 2
 
 
@@ -593,13 +654,15 @@ def patch_model(model: torch.nn.Module, device, processor=None, skip_modules=("l
     """Replace every ``nn.Linear`` whose qualified name contains none of ``skip_modules`` by the processor's layer
     (reference: helper.py:34-85; same argument order).  HQQ processors (``from_hqqlinear``) would first quantise
     with the third-party ``hqq`` package, which this build does not ship: they raise NotImplementedError here — feed
-    ``from_weights`` / ``from_hqqlinear`` with already quantised tensors instead, or take the ``*_RTN_INT`` processors, which
-    quantise the float weights themselves.  ``group_size`` reaches those when they were built without one; a layer whose
+    ``from_weights`` / ``from_hqqlinear`` with already quantised tensors instead, or take the ``*_HQQOPT_INT`` processors (HQQ's
+    zero-point optimiser, on the GPU) or the ``*_RTN_INT`` ones (round to nearest), which quantise the float weights themselves.
+    ``group_size`` reaches those when they were built without one; a layer whose
     ``in_features`` it does not divide raises ValueError with the layer's name."""
     if processor is None or hasattr(device, "from_linear") or hasattr(device, "from_hqqlinear"):
         device, processor = (processor if processor is not None else "cuda:0"), device  # (model, processor[, device]) order
     if not hasattr(processor, "from_linear"):
-        raise NotImplementedError("this processor needs layers quantised by the `hqq` package (not part of this build)")
+        raise NotImplementedError("this processor needs layers quantised by the `hqq` package (not part of this build); the "
+                                  "*_HQQOPT_INT processors (HQQ's zero-point optimiser) and the *_RTN_INT ones quantise float weights here")
 
     def _walk(module, prefix):
         for name, child in list(module.named_children()):

@@ -6,7 +6,8 @@ int8 rounded with floor(v + 0.5) — the rounding the reference's kernel uses on
 Runs as one HIP kernel (`gemlite_hip_scale_activations_per_token`).
 
 ``WeightQuantizerINT``: float weights -> grouped asymmetric INT codes + (scale, zero) per group, one HIP kernel
-(`gemlite_hip_quantize_groups`; the reference leaves this step to the third-party ``hqq`` package), and back (``dequantize``:
+(`gemlite_hip_quantize_groups`; the reference leaves this step to the third-party ``hqq`` package); ``WeightQuantizerHQQ``: the same
+with HQQ's zero-point optimiser inside the launch (`gemlite_hip_quantize_groups_hqq`); and back (``dequantize``:
 `gemlite_hip_dequantize`, DESIGN §2.3, which ``WeightQuantizerMXFP.dequantize`` takes too for GPU tensors).
 
 Block-scaled formats (reference: gemlite/quant_utils.py:21-225 weight quantiser, :502-954 activation quantisers):
@@ -65,9 +66,11 @@ def check_group_size(in_features: int, group_size: int, what: str = "weight"):
         raise ValueError(f"{what}: group_size {group_size} must be a multiple of 32 that divides in_features = {in_features}")
 
 
-def _quantize_groups(W: torch.Tensor, W_nbits: int, group_size: int, meta_dtype: torch.dtype, packed: bool, fold_zeros: bool = False):
+def _quantize_groups(W: torch.Tensor, W_nbits: int, group_size: int, meta_dtype: torch.dtype, packed: bool, fold_zeros: bool = False,
+                     hqq=None):
     """One `gemlite_hip_quantize_groups` launch on W's device and current stream.  packed: (int32 words [K/e, N], scales [K/g, N],
-    zeros [K/g, N], folded if asked) — what a packed layer holds; else (uint8 codes [N, K], scales [N * K/g, 1], zeros [N * K/g, 1])."""
+    zeros [K/g, N], folded if asked) — what a packed layer holds; else (uint8 codes [N, K], scales [N * K/g, 1], zeros [N * K/g, 1]).
+    hqq = (iters, lp_norm, beta, kappa): the same launch with the zero-point optimiser, `gemlite_hip_quantize_groups_hqq`."""
     _hip.require_gpu_tensor(W, "W")
     assert W.dim() == 2, "W should be [out_features, in_features]"
     if W.dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -78,7 +81,13 @@ def _quantize_groups(W: torch.Tensor, W_nbits: int, group_size: int, meta_dtype:
     check_group_size(K, group_size)
     n_groups = K // group_size
     dev = W.device
-    a = _hip.QuantizeArgs()
+    if hqq is None:
+        a = _hip.QuantizeArgs()
+    else:
+        h = _hip.QuantizeHqqArgs()
+        h.struct_size = _hip.C.sizeof(_hip.QuantizeHqqArgs)
+        h.iters, h.lp_norm, h.beta, h.kappa = hqq
+        a = h.q
     if packed:
         q = torch.empty((K // (32 // W_nbits), N), dtype=torch.int32, device=dev)
         scales = torch.empty((n_groups, N), dtype=meta_dtype, device=dev)
@@ -93,16 +102,19 @@ def _quantize_groups(W: torch.Tensor, W_nbits: int, group_size: int, meta_dtype:
     a.W_nbits, a.group_size, a.meta_dtype = W_nbits, group_size, TORCH_TO_DTYPE[meta_dtype].value
     a.q_out, a.scales, a.zeros, a.fold_zeros = q.data_ptr(), scales.data_ptr(), zeros.data_ptr(), int(fold_zeros)
     with _hip.on_device(dev):
-        rc = _hip.load().gemlite_hip_quantize_groups(_hip.C.byref(a), _hip.current_stream_handle(dev))
-    _hip.raise_for_status(rc, "quantize_groups")
+        if hqq is None:
+            rc = _hip.load().gemlite_hip_quantize_groups(_hip.C.byref(a), _hip.current_stream_handle(dev))
+        else:
+            rc = _hip.load().gemlite_hip_quantize_groups_hqq(_hip.C.byref(h), _hip.current_stream_handle(dev))
+    _hip.raise_for_status(rc, "quantize_groups" if hqq is None else "quantize_groups_hqq")
     return q, scales, zeros
 
 
 class WeightQuantizerINT:
     """Float weights -> (W_q uint8 [N, K], scales [N * K/g, 1], zeros [N * K/g, 1]): the tensors ``from_weights`` of the ``*_HQQ_INT``
     processors and HQQ's ``meta`` hold.  Asymmetric round to nearest on each group's min / max (HQQ's starting point, without its
-    optimiser); the codes are taken against the ROUNDED (scale, zero), which is what the layer dequantises with.  ``dtype`` is the
-    metadata type: None = W.dtype if that is fp16 / bf16, else fp16.  GPU tensors only."""
+    optimiser: ``WeightQuantizerHQQ`` below adds it); the codes are taken against the ROUNDED (scale, zero), which is what the layer
+    dequantises with.  ``dtype`` is the metadata type: None = W.dtype if that is fp16 / bf16, else fp16.  GPU tensors only."""
 
     def __init__(self, W_nbits: int, group_size: int, dtype=None, device="cuda:0"):
         assert W_nbits in (8, 4, 2, 1), "W_nbits should be 8, 4, 2 or 1"
@@ -162,6 +174,30 @@ class WeightQuantizerINT:
             rc = _hip.load().gemlite_hip_dequantize(_hip.C.byref(a), _hip.current_stream_handle(dev))
         _hip.raise_for_status(rc, "gemlite_hip_dequantize")
         return out if shape is None else out.view(tuple(shape))
+
+
+class WeightQuantizerHQQ(WeightQuantizerINT):
+    """``WeightQuantizerINT`` with HQQ's proximal optimiser on every group's zero, inside the same single launch
+    (`gemlite_hip_quantize_groups_hqq`): same tensors, shapes and layouts returned; the scale is round to nearest's, the
+    zero is the best of up to ``iters`` candidates, judged per group by the error of what the layer computes — no group ends worse
+    than ``WeightQuantizerINT``'s, and ``iters=0`` is ``WeightQuantizerINT``.  The defaults are HQQ's.  GPU tensors only."""
+
+    def __init__(self, W_nbits: int, group_size: int, dtype=None, device="cuda:0", iters: int = 20, lp_norm: float = 0.7,
+                 beta: float = 10.0, kappa: float = 1.01):
+        super().__init__(W_nbits, group_size, dtype=dtype, device=device)
+        self.iters, self.lp_norm, self.beta, self.kappa = int(iters), float(lp_norm), float(beta), float(kappa)
+        if not (0 <= self.iters <= 100 and 0.0 < self.lp_norm <= 1.0 and 0.0 < self.beta < float("inf") and 0.0 < self.kappa < float("inf")):
+            raise ValueError(f"WeightQuantizerHQQ: need 0 <= iters <= 100, 0 < lp_norm <= 1, beta > 0, kappa > 0; got iters={iters}, "
+                             f"lp_norm={lp_norm}, beta={beta}, kappa={kappa}")
+
+    def _hqq(self):
+        return (self.iters, self.lp_norm, self.beta, self.kappa)
+
+    def quantize(self, W: torch.Tensor):
+        return _quantize_groups(W, self.W_nbits, self.group_size, self.meta_dtype(W), packed=False, hqq=self._hqq())
+
+    def quantize_packed(self, W: torch.Tensor, fold_zeros: bool):
+        return _quantize_groups(W, self.W_nbits, self.group_size, self.meta_dtype(W), packed=True, fold_zeros=fold_zeros, hqq=self._hqq())
 
 
 # ------------------------------------------------------------------------------------------------------

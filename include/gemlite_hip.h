@@ -24,6 +24,7 @@
  *                                     (bit layout spec: pack_weights_over_cols_torch :36-60)
  *   gemlite_hip_unpack_over_cols   <- unpack_over_cols_triton, gemlite/bitpack.py:175-241
  *   gemlite_hip_quantize_groups    <- (no counterpart: the reference leaves float -> grouped INT to the third-party hqq package)
+ *   gemlite_hip_quantize_groups_hqq <- (hqq's optimize_weights_proximal, restated per group: see the declaration)
  *   gemlite_hip_quantize_mx        <- gemlite/quant_utils.py  WeightQuantizerMXFP (torch ops there; one kernel here)
  *   gemlite_hip_dequantize         <- (no counterpart for a packed layer; WeightQuantizerMXFP.dequantize is torch ops on the quantiser's return)
  *
@@ -430,6 +431,29 @@ typedef struct gemlite_hip_quantize_args {
     int32_t reserved;     /* 0 */
 } gemlite_hip_quantize_args;
 int gemlite_hip_quantize_groups(const gemlite_hip_quantize_args* args, void* stream);
+
+/* The same launch with HQQ's proximal optimiser on the ZERO of every group between the metadata and the codes (the scale stays s_r).
+ * `q` is the struct above, read exactly as there (outputs, layouts, fold_zeros, limits).  Per group of g = group_size weights, fp32:
+ *     Q(z) = clamp(rint(w / s_r + z), 0, qmax);   E(z) = mean_k |w - (Q(rT(z)) - rT(z)) * s_r|     (the error of what the layer computes)
+ *     z = z0 = -lo / s_r;  best_z = z0, best_E = E(z0)                     (rT(z0) is z_r above: iteration 0 is round to nearest)
+ *     for i in 0 .. iters-1, while the group is alive:   beta_i = beta * kappa^i
+ *         q = Q(z);  r = w - (q - z) * s_r;  e = sign(r) * max(|r| - |r|^(lp_norm - 1) / beta_i, 0)      (e = 0 where r == 0)
+ *         z = mean_k(q - (w - e) / s_r);   E(z) < best_E ? best_z, best_E = z, E(z) : the group stops
+ *     stored: s_r, z_r = rT(best_z), codes Q(z_r)
+ * Unlike HQQ's optimize_weights_proximal the stop is per group, the best zero seen is kept (not the last), and the error is taken against
+ * the rounded zero: no group ends worse than round to nearest.  The order of the sums inside a group is fixed by the kernel: the same
+ * input gives the same bits on every run, in both output forms, wherever the group sits.  The last bit of the power is not part of the
+ * contract.  0 <= iters <= 100 (0: byte for byte the launch above), 0 < lp_norm <= 1, beta > 0, kappa > 0 (finite): anything else is
+ * GEMLITE_ERR_BAD_ARGUMENT; a bad `q` returns what the launch above returns for it; nothing is launched then.  HQQ's defaults: 20, 0.7,
+ * 10, 1.01.  Non-finite weights: unspecified codes for their group, no fault, the loop ends (a comparison with NaN stops the group). */
+typedef struct gemlite_hip_quantize_hqq_args {
+    uint32_t struct_size; /* = sizeof(gemlite_hip_quantize_hqq_args), ABI guard */
+    int32_t iters;
+    gemlite_hip_quantize_args q; /* q.struct_size = sizeof(gemlite_hip_quantize_args) */
+    float lp_norm, beta, kappa;
+    int32_t reserved;     /* 0 */
+} gemlite_hip_quantize_hqq_args;
+int gemlite_hip_quantize_groups_hqq(const gemlite_hip_quantize_hqq_args* args, void* stream);
 
 /* Quantise float weights W[N, K] (fp32 / fp16 / bf16, unit inner stride, row stride ld_w >= K) to a block-scaled format in one launch
  * on `stream`: no workspace, no atomics, 64-bit indices.  K % 32 == 0.  Every step is ONE fp32 IEEE operation (correctly rounded
