@@ -136,6 +136,33 @@ class QuantizeMxArgs(C.Structure):
     ]
 
 
+class QuantizeRowsArgs(C.Structure):
+    """struct gemlite_hip_quantize_rows_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("w_dtype", C.c_int32),
+        ("w", C.c_void_p),
+        ("N", C.c_int64),
+        ("K", C.c_int64),
+        ("ld_w", C.c_int64),
+        ("format", C.c_int32),
+        ("scale_rule", C.c_int32),
+        ("q_out", C.c_void_p),
+        ("ld_q", C.c_int64),
+        ("scales", C.c_void_p),
+        ("stride_s", C.c_int64),
+        ("scale_dtype", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+# form limits of gemlite_hip_quantize_rows (GEMLITE_QUANT_ROWS_WAVE_MAX_K / _RESIDENT_MAX_K of the header): the longest row, in elements,
+# that one wave takes, and the longest that one block reads once
+QUANT_ROWS_WAVE_MAX_K = 1024
+QUANT_ROWS_RESIDENT_MAX_K = 16384
+
+
 class DequantizeArgs(C.Structure):
     """struct gemlite_hip_dequantize_args (field order/types must match the header)."""
 
@@ -249,6 +276,8 @@ def load():
         lib.gemlite_hip_quantize_groups_hqq.argtypes = [C.POINTER(QuantizeHqqArgs), C.c_void_p]
         lib.gemlite_hip_quantize_mx.restype = C.c_int
         lib.gemlite_hip_quantize_mx.argtypes = [C.POINTER(QuantizeMxArgs), C.c_void_p]
+        lib.gemlite_hip_quantize_rows.restype = C.c_int
+        lib.gemlite_hip_quantize_rows.argtypes = [C.POINTER(QuantizeRowsArgs), C.c_void_p]
         lib.gemlite_hip_dequantize.restype = C.c_int
         lib.gemlite_hip_dequantize.argtypes = [C.POINTER(DequantizeArgs), C.c_void_p]
         if lib.gemlite_hip_abi_version() != ABI_VERSION:
@@ -268,6 +297,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_capture_group_grid_y", "gemlite_hip_capture_group_wave_split",
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
     "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize", "gemlite_hip_quantize_groups_hqq",
+    "gemlite_hip_quantize_rows",
 )
 
 

@@ -59,6 +59,7 @@ const void* unpack_kernel_fn();
 const void* quantize_groups_kernel_fn(bool onepass);
 const void* quantize_hqq_kernel_fn(bool onepass);
 const void* quantize_mx_kernel_fn(int format);
+const void* quantize_rows_kernel_fn(int format, int64_t K);
 const void* dequantize_words_kernel_fn(int nbits);
 const void* dequantize_rows_kernel_fn(int fmt);
 const void* dequantize_any_kernel_fn();
@@ -946,7 +947,7 @@ int gemlite_hip_abi_version(void) { return GEMLITE_HIP_ABI_VERSION; }
 
 const char* gemlite_hip_build_info(void) {
     return "libgemlite_hip gfx950 (CDNA4) abi=1 kernels: gemv_wn, gemv_decode, gemv_mfma, gemv_a8wn, gemm_wn_rows, gemm_wn_direct, gemm_wn_stream, gemm_wn_mma, gemm_wn_tiled, gemm_a8w8, "
-           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups, quantize_mx, dequantize, quantize_hqq"
+           "gemm_mx, mx_rows, nvfp4_f16, kmajor, generic, act_quant_per_token, act_quant_mx, pack/unpack_over_cols, quantize_groups, quantize_mx, dequantize, quantize_hqq, quantize_rows"
 #ifdef GL_AB_KERNELS
            " +ab_kernels"
 #endif
@@ -1313,6 +1314,24 @@ int gemlite_hip_quantize_mx(const gemlite_hip_quantize_mx_args* a, void* stream)
     if (gx > 0x7FFFFFFF || gy > 65535) return GEMLITE_ERR_BAD_SHAPE;
     void* kargs[] = {(void*)&p};
     return launch(quantize_mx_kernel_fn(a->format), dim3((unsigned)gx, (unsigned)gy, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
+}
+
+// everything is checked before the launch (host only: testable without a device)
+int gemlite_hip_quantize_rows(const gemlite_hip_quantize_rows_args* a, void* stream) {
+    if (!a || a->struct_size != sizeof(gemlite_hip_quantize_rows_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (!a->w || !a->q_out || !a->scales) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (a->N <= 0 || a->K <= 0 || a->ld_w < a->K || a->ld_q < a->K || a->stride_s <= 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (a->format < 0 || a->format > 2 || !(a->scale_rule == 0 || a->scale_rule == 1)) return GEMLITE_ERR_UNSUPPORTED;
+    if (!(a->w_dtype == GEMLITE_DT_FP32 || a->w_dtype == GEMLITE_DT_FP16 || a->w_dtype == GEMLITE_DT_BF16)) return GEMLITE_ERR_UNSUPPORTED;
+    if (!(a->scale_dtype == GEMLITE_DT_FP32 || a->scale_dtype == GEMLITE_DT_FP16 || a->scale_dtype == GEMLITE_DT_BF16)) return GEMLITE_ERR_UNSUPPORTED;
+    if (a->N > 0x7FFFFFFF) return GEMLITE_ERR_BAD_SHAPE;
+    QuantRowsParams p;
+    p.w = a->w; p.q_out = (uint8_t*)a->q_out; p.scales = a->scales;
+    p.N = a->N; p.K = a->K; p.ld_w = a->ld_w; p.ld_q = a->ld_q; p.stride_s = a->stride_s;
+    p.w_dt = a->w_dtype; p.scale_dt = a->scale_dtype; p.rule = a->scale_rule;
+    const int64_t gx = a->K <= GEMLITE_QUANT_ROWS_WAVE_MAX_K ? (a->N + 3) / 4 : a->N;  // wave form: four rows per block
+    void* kargs[] = {(void*)&p};
+    return launch(quantize_rows_kernel_fn(a->format, a->K), dim3((unsigned)gx, 1, 1), dim3(256, 1, 1), kargs, 0, (hipStream_t)stream);
 }
 
 // everything is checked before the launch (host only: testable without a device)

@@ -539,6 +539,15 @@ struct QuantMxParams {
     int w_dt, pack;
 };
 
+// parameter block of the channel-wise 8-bit weight quantiser (quantize_rows.hip)
+struct QuantRowsParams {
+    const void* w;    // [N, ld_w] fp32 / fp16 / bf16
+    uint8_t* q_out;   // bytes [N, ld_q]: int8 / e4m3 / e5m2, K per row
+    void* scales;     // row n at n * stride_s (elements of scale_dt)
+    int64_t N, K, ld_w, ld_q, stride_s;
+    int w_dt, scale_dt, rule;
+};
+
 // parameter block of the grouped weight quantiser (quantize_groups.hip)
 struct QuantGroupsParams {
     const void* w;   // [N, ld_w] fp32 / fp16 / bf16

@@ -9,6 +9,8 @@ reads the attributes the reference reads, and the raw-tensor entry points take e
 The ``*_RTN_INT`` subclasses of the ``*_HQQ_INT`` family (not in the reference) quantise an ``nn.Linear`` themselves, on the GPU:
 round to nearest on each group's min / max, HQQ's starting point (``from_linear``, ``quantize_weights``); their ``*_HQQOPT_INT``
 subclasses add HQQ's zero-point optimiser to the same launch.
+``A16W8*`` and ``A8W8*_dynamic`` quantise a float weight that is bound for the GPU in one launch, read once in its own dtype
+(``WeightQuantizerRows``); CPU layers run the reference's torch sequence.
 On gfx950 FP8 means OCP e4m3fn (the reference's HIP default e4m3fnuz, helper.py:13-15, is the MI300X format).
 """
 from typing import Optional
@@ -18,10 +20,20 @@ import torch
 from . import _hip
 from .core import GemLiteLinear, select_modes
 from .dtypes import TORCH_TO_DTYPE, DType
-from .quant_utils import WeightQuantizerHQQ, WeightQuantizerINT, WeightQuantizerMXFP, _takes_mx_kernel, check_group_size
+from .quant_utils import (WeightQuantizerHQQ, WeightQuantizerINT, WeightQuantizerMXFP, WeightQuantizerRows, _quantize_rows_torch, _takes_mx_kernel,
+                          _takes_rows_kernel, check_group_size)
 
 default_fp8 = torch.float8_e4m3fn
 default_post_scale = True  # channel-wise scaling applied after the K reduction (reference HIP default)
+
+
+def _quantize_channelwise(weight: torch.Tensor, w_dtype: torch.dtype, device):
+    """Float weight -> (W_q [N, K] of w_dtype, scales fp32 [N, 1]) on `device`, symmetric with one scale per output channel: one
+    `gemlite_hip_quantize_rows` launch on the weight in its own dtype when the kernel applies (a GPU layer, int8 / e4m3fn / e5m2, a 2-D
+    fp32 / fp16 / bf16 weight with unit inner stride), else the reference's torch sequence."""
+    if _takes_rows_kernel(weight, w_dtype, device):
+        return WeightQuantizerRows(w_dtype, device=device).quantize(weight.to(device))
+    return _quantize_rows_torch(weight, w_dtype, device)
 
 
 def _gemlite_dtype(dtype: torch.dtype) -> DType:
@@ -68,12 +80,8 @@ class A16W8:
         out_features, in_features = weight.shape
         if scales is None:  # quantise: symmetric, one scale per output channel
             w_dtype = self.fp8 if self.fp8 else torch.int8
-            info = torch.finfo(w_dtype) if w_dtype.is_floating_point else torch.iinfo(w_dtype)
             dtype = weight.dtype if self.dtype is None else self.dtype
-            W = weight.to(device=self.device, dtype=torch.float32)
-            scales = (W.abs().amax(dim=1, keepdim=True) / info.max).clamp_(min=1e-6)
-            W_q = (W / scales).clamp_(info.min, info.max)
-            W_q = W_q.to(w_dtype) if w_dtype.is_floating_point else W_q.round_().to(w_dtype)
+            W_q, scales = _quantize_channelwise(weight, w_dtype, self.device)
         else:  # pre-quantised
             assert weight.element_size() == 1, f"Invalid weight.dtype, should be 8-bit (INT8 or FP8), got {weight.dtype}"
             dtype = self.dtype or (scales.dtype if scales.dtype in (torch.float16, torch.bfloat16) else torch.float16)
@@ -387,16 +395,12 @@ class A8W8_dynamic:
         if self.fp8:
             w_dtype = self.fp8 if isinstance(self.fp8, torch.dtype) else default_fp8
             input_dtype = TORCH_TO_DTYPE[w_dtype]
-            info = torch.finfo(w_dtype)
         else:
-            w_dtype, input_dtype, info = torch.int8, DType.INT8, torch.iinfo(torch.int8)
+            w_dtype, input_dtype = torch.int8, DType.INT8
         out_features, in_features = weight.shape
         if scales is None:
             dtype = weight.dtype if self.dtype is None else self.dtype
-            W = weight.to(device=self.device, dtype=torch.float32)
-            scales = (W.abs().amax(dim=1, keepdim=True) / info.max).clamp_(min=1e-6)
-            W_q = (W / scales).clamp_(info.min, info.max)
-            W_q = W_q.to(w_dtype) if w_dtype.is_floating_point else W_q.round_().to(w_dtype)
+            W_q, scales = _quantize_channelwise(weight, w_dtype, self.device)
         else:
             assert weight.element_size() == 1, "Invalid weight.dtype, should be 8-bit."
             dtype = self.dtype or (scales.dtype if scales.dtype in (torch.float16, torch.bfloat16) else torch.float16)
@@ -409,8 +413,10 @@ class A8W8_dynamic:
         layer.W_group_mode, layer.channel_scale_mode = 0, 3  # post-scaling (helper.py:474-475)
         return layer
 
-    def from_linear(self, linear: torch.nn.Linear) -> GemLiteLinear:
-        return self.from_weights(linear.weight.data, None if linear.bias is None else linear.bias.data)
+    def from_linear(self, linear: torch.nn.Linear, del_orig: bool = True) -> GemLiteLinear:
+        out = self.from_weights(linear.weight.data, None if linear.bias is None else linear.bias.data)
+        cleanup_linear(linear, del_orig)
+        return out
 
 
 class A8W8_int8_dynamic(A8W8_dynamic):

@@ -10,6 +10,10 @@ Runs as one HIP kernel (`gemlite_hip_scale_activations_per_token`).
 with HQQ's zero-point optimiser inside the launch (`gemlite_hip_quantize_groups_hqq`); and back (``dequantize``:
 `gemlite_hip_dequantize`, DESIGN §2.3, which ``WeightQuantizerMXFP.dequantize`` takes too for GPU tensors).
 
+``WeightQuantizerRows``: float weights -> channel-wise symmetric INT8 / FP8 codes + one scale per output channel, the tensors of the
+``A16W8*`` / ``A8W8*_dynamic`` processors (GPU weights: one HIP kernel, `gemlite_hip_quantize_rows`; CPU tensors: the
+reference's torch sequence, ``_quantize_rows_torch``).
+
 Block-scaled formats (reference: gemlite/quant_utils.py:21-225 weight quantiser, :502-954 activation quantisers):
 ``WeightQuantizerMXFP`` (GPU float weights: one HIP kernel, `gemlite_hip_quantize_mx`; CPU tensors, the scale-search
 window and ``index=False``: the reference's torch code) and
@@ -198,6 +202,104 @@ class WeightQuantizerHQQ(WeightQuantizerINT):
 
     def quantize_packed(self, W: torch.Tensor, fold_zeros: bool):
         return _quantize_groups(W, self.W_nbits, self.group_size, self.meta_dtype(W), packed=True, fold_zeros=fold_zeros, hqq=self._hqq())
+
+
+# ------------------------------------------------------------------------------------------------------
+# channel-wise symmetric 8-bit weights: one scale per output channel (one HIP launch)
+# ------------------------------------------------------------------------------------------------------
+ROWS_FORMATS = {torch.int8: 0, torch.float8_e4m3fn: 1, torch.float8_e5m2: 2}  # code dtype -> format of gemlite_hip_quantize_rows
+_ROWS_KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+# The scale rule the processors pass: 0 divides amax by the format's maximum, 1 multiplies by the fp32 reciprocal of it.  Rule 1 is
+# what torch's `tensor / python_scalar` computes on a GPU tensor, so the layers equal what the torch sequence built there.
+ROWS_SCALE_RULE = 1
+
+
+def _quantize_rows_torch(weight: torch.Tensor, w_dtype: torch.dtype, device=None):
+    """The reference's sequence (helper.py:110-118, :437-444), torch ops on `device`: (W_q [N, K] of w_dtype, scales fp32 [N, 1])."""
+    info = torch.finfo(w_dtype) if w_dtype.is_floating_point else torch.iinfo(w_dtype)
+    W = weight.to(device=device, dtype=torch.float32)
+    scales = (W.abs().amax(dim=1, keepdim=True) / info.max).clamp_(min=1e-6)
+    W_q = (W / scales).clamp_(info.min, info.max)
+    W_q = W_q.to(w_dtype) if w_dtype.is_floating_point else W_q.round_().to(w_dtype)
+    return W_q, scales
+
+
+def _takes_rows_kernel(weight: torch.Tensor, w_dtype: torch.dtype, device) -> bool:
+    """The inputs `gemlite_hip_quantize_rows` takes for a layer on `device`; everything else stays on the torch sequence above."""
+    return (torch.device(device).type == "cuda" and w_dtype in ROWS_FORMATS and weight.dim() == 2 and weight.dtype in _ROWS_KERNEL_DTYPES
+            and weight.shape[0] > 0 and weight.shape[1] > 0 and weight.stride(1) == 1)
+
+
+def _quantize_rows(W: torch.Tensor, w_dtype: torch.dtype, scale_dtype: torch.dtype, scale_rule: int):
+    """One `gemlite_hip_quantize_rows` launch on W's device and current stream (contract: DESIGN §2.4, include/gemlite_hip.h):
+    (codes [N, K] of w_dtype, scales [N, 1] of scale_dtype).  W is read in its own dtype through its row stride."""
+    _hip.require_gpu_tensor(W, "W")
+    assert W.dim() == 2 and W.stride(1) == 1, "W should be [out_features, in_features] with unit inner stride"
+    N, K = W.shape
+    dev = W.device
+    q = torch.empty((N, K), dtype=w_dtype, device=dev)
+    scales = torch.empty((N, 1), dtype=scale_dtype, device=dev)
+    a = _hip.QuantizeRowsArgs()
+    a.struct_size = _hip.C.sizeof(_hip.QuantizeRowsArgs)
+    a.w, a.w_dtype, a.N, a.K, a.ld_w = W.data_ptr(), TORCH_TO_DTYPE[W.dtype].value, N, K, (W.stride(0) if N > 1 else max(K, W.stride(0)))
+    a.format, a.scale_rule, a.q_out, a.ld_q = ROWS_FORMATS[w_dtype], int(scale_rule), q.data_ptr(), K
+    a.scales, a.stride_s, a.scale_dtype, a.reserved = scales.data_ptr(), 1, TORCH_TO_DTYPE[scale_dtype].value, 0
+    with _hip.on_device(dev):
+        rc = _hip.load().gemlite_hip_quantize_rows(_hip.C.byref(a), _hip.current_stream_handle(dev))
+    _hip.raise_for_status(rc, "quantize_rows")
+    return q, scales
+
+
+class WeightQuantizerRows:
+    """Float weights -> (W_q [N, K] int8 / float8_e4m3fn / float8_e5m2, scales [N, 1]): symmetric, one scale per output channel,
+    ``s = max(amax / qmax, 1e-6)``, ``W_q = clamp(W / s)`` rounded to nearest even — what ``from_weights(W_q, bias, scales)`` of the
+    ``A16W8*`` / ``A8W8*_dynamic`` processors takes.  A 2-D fp32 / fp16 / bf16 GPU weight with unit inner stride is quantised by ONE HIP
+    launch in its own dtype (`gemlite_hip_quantize_rows`); CPU tensors (and ``*fnuz`` fp8, other layouts) run the reference's
+    torch sequence.  ``fp32_scale=False`` returns the scales rounded once to ``dtype`` (None = W.dtype if that is fp16 / bf16, else fp16).
+    ``scale_rule``: 0 = amax / qmax (torch on a CPU tensor), 1 = amax * (1 / qmax) (torch on a GPU tensor), None = ``ROWS_SCALE_RULE``."""
+
+    def __init__(self, w_dtype: torch.dtype, dtype=None, device="cuda:0", fp32_scale: bool = True, scale_rule=None):
+        assert w_dtype.itemsize == 1, f"w_dtype should be an 8-bit type (INT8 or FP8), got {w_dtype}"
+        assert scale_rule in (None, 0, 1), "scale_rule should be 0, 1 or None"
+        self.w_dtype, self.dtype, self.device, self.fp32_scale = w_dtype, dtype, device, fp32_scale
+        self.scale_rule = ROWS_SCALE_RULE if scale_rule is None else scale_rule
+
+    def scale_dtype(self, W: torch.Tensor) -> torch.dtype:
+        if self.fp32_scale:
+            return torch.float32
+        if self.dtype is not None:
+            return self.dtype
+        return W.dtype if W.dtype in (torch.float16, torch.bfloat16) else torch.float16
+
+    def quantize(self, W: torch.Tensor):
+        if W.is_cuda and _takes_rows_kernel(W, self.w_dtype, W.device):
+            return _quantize_rows(W, self.w_dtype, self.scale_dtype(W), self.scale_rule)
+        W_q, scales = _quantize_rows_torch(W, self.w_dtype)
+        return W_q, scales.to(self.scale_dtype(W))
+
+    def dequantize(self, W_q: torch.Tensor, scales: torch.Tensor, dtype=None):
+        """The float weights [N, K] the tensors of ``quantize()`` stand for, ``code * s`` (one fp32 multiplication, then one rounding to
+        ``dtype``: float16 / bfloat16 / float32, default ``self.dtype`` or float16), in one `gemlite_hip_dequantize` launch."""
+        _hip.require_gpu_tensor(W_q, "W_q")
+        assert W_q.dim() == 2 and W_q.element_size() == 1 and scales.numel() == W_q.shape[0], "W_q [N, K] 8-bit codes, one scale per row"
+        if dtype is None:
+            dtype = self.dtype if self.dtype is not None else torch.float16
+        N, K = W_q.shape
+        dev = W_q.device
+        scales = scales.reshape(N, 1)
+        out = torch.empty((N, K), dtype=dtype, device=dev)
+        a = _hip.DequantizeArgs()
+        a.struct_size = _hip.C.sizeof(_hip.DequantizeArgs)
+        a.w_q, a.scales, a.out = W_q.data_ptr(), scales.data_ptr(), out.data_ptr()
+        a.N, a.K, a.ld_out, a.W_nbits, a.group_size = N, K, K, 8, K
+        a.stride_wk, a.stride_wn, a.stride_meta_g, a.stride_meta_n = W_q.stride(1), W_q.stride(0), 0, scales.stride(0)
+        a.elements_per_sample, a.w_pack_bits, a.w_dtype = 1, 0, TORCH_TO_DTYPE[W_q.dtype].value
+        a.out_dtype, a.input_dtype, a.meta_dtype = TORCH_TO_DTYPE[dtype].value, TORCH_TO_DTYPE[dtype].value, TORCH_TO_DTYPE[scales.dtype].value
+        a.W_group_mode, a.channel_scale_mode, a.post_scale = 0, 1, 1.0
+        with _hip.on_device(dev):
+            rc = _hip.load().gemlite_hip_dequantize(_hip.C.byref(a), _hip.current_stream_handle(dev))
+        _hip.raise_for_status(rc, "gemlite_hip_dequantize")
+        return out
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -27,6 +27,7 @@
  *   gemlite_hip_quantize_groups_hqq <- (hqq's optimize_weights_proximal, restated per group: see the declaration)
  *   gemlite_hip_quantize_mx        <- gemlite/quant_utils.py  WeightQuantizerMXFP (torch ops there; one kernel here)
  *   gemlite_hip_dequantize         <- (no counterpart for a packed layer; WeightQuantizerMXFP.dequantize is torch ops on the quantiser's return)
+ *   gemlite_hip_quantize_rows      <- gemlite/helper.py  A16W8.from_weights / A8W8_dynamic.from_weights (torch ops there; one kernel here)
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer is a DEVICE pointer unless stated;
@@ -529,6 +530,42 @@ typedef struct gemlite_hip_dequantize_args {
     int64_t reserved;     /* 0 */
 } gemlite_hip_dequantize_args;
 int gemlite_hip_dequantize(const gemlite_hip_dequantize_args* args, void* stream);
+
+/* Quantise float weights W[N, K] (fp32 / fp16 / bf16, unit inner stride, row stride ld_w >= K elements) to channel-wise symmetric 8-bit
+ * codes and one scale per row — the tensors an A16W8 / A8W8 layer holds — in one launch on `stream`: no workspace, no atomics, 64-bit
+ * addresses, capturable.  Per row n, every step ONE fp32 IEEE operation (correctly rounded divisions, nothing contracts, denormals kept):
+ *     amax = max_k |w[n, k]|                       (exact: widening to fp32 is exact)
+ *     scale_rule 0: s = amax / qmax      scale_rule 1: s = amax * (1.0f / qmax)        qmax = 127.f | 448.f | 57344.f
+ *     s = max(s, 1e-6f)                            (the fp32 nearest to 1e-6)
+ *     q = min(max(w / s, qmin), qmax)              qmin = -128.f | -448.f | -57344.f
+ *     format 0 int8: rint(q), half to even, stored as int8
+ *     format 1 e4m3fn, 2 e5m2: one round-to-nearest-even conversion (subnormal results kept, -0 keeps its sign)
+ *     scales[n * stride_s] = s as fp32, or rounded once (RNE) to fp16 / bf16 (scale_dtype); the codes always use the fp32 s
+ * Rule 0 is a true division by the format's maximum (what torch computes for `amax / max` on a CPU tensor), rule 1 the multiplication
+ * by its fp32 reciprocal; they differ in the last bit of s for some amax.
+ * A row that holds a NaN or an Inf gets a non-finite scale; its codes are unspecified (written, no fault); every other row is unaffected.
+ * q_out: bytes [N][K], row stride ld_q >= K bytes.  Rows of at most GEMLITE_QUANT_ROWS_WAVE_MAX_K elements take one wave each, rows of
+ * at most GEMLITE_QUANT_ROWS_RESIDENT_MAX_K one block that reads the weight once, longer rows one block that reads it twice; any
+ * alignment of w / q_out / ld_w / ld_q and any K are correct (narrower accesses).
+ * Checked on the host before the launch: BAD_ARGUMENT (null pointers, struct_size, N / K <= 0, ld_w < K, ld_q < K, stride_s <= 0),
+ * UNSUPPORTED (dtypes, format, scale_rule), BAD_SHAPE (N beyond the grid limit 2^31 - 1). */
+#define GEMLITE_QUANT_ROWS_WAVE_MAX_K 1024
+#define GEMLITE_QUANT_ROWS_RESIDENT_MAX_K 16384
+typedef struct gemlite_hip_quantize_rows_args {
+    uint32_t struct_size; /* = sizeof(gemlite_hip_quantize_rows_args), ABI guard */
+    int32_t w_dtype;      /* GEMLITE_DT_FP32 / FP16 / BF16 */
+    const void* w;
+    int64_t N, K, ld_w;
+    int32_t format;       /* 0 int8, 1 fp8 e4m3fn, 2 fp8 e5m2 */
+    int32_t scale_rule;   /* 0 divide by qmax, 1 multiply by 1.0f / qmax */
+    void* q_out;
+    int64_t ld_q;
+    void* scales;
+    int64_t stride_s;     /* elements of scale_dtype between the scales of consecutive rows */
+    int32_t scale_dtype;  /* GEMLITE_DT_FP32 / FP16 / BF16 */
+    int32_t reserved;     /* 0 */
+} gemlite_hip_quantize_rows_args;
+int gemlite_hip_quantize_rows(const gemlite_hip_quantize_rows_args* args, void* stream);
 
 #ifdef __cplusplus
 }
