@@ -67,7 +67,10 @@ const void* dequantize_any_kernel_fn();
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
 bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPlan& la, const gemlite_hip_forward_args& b, const LaunchPlan& lb);
-bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident);
+bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident, int dev);
+bool capture_group_shared_x_enabled();
+int capture_group_last_form();
+int ensure_lds(const void* fn, size_t lds, int dev);
 void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st);
 
 }  // namespace gl
@@ -903,7 +906,7 @@ static int check_device(int* dev_out) {
 }
 
 // Raise the dynamic-LDS cap of a kernel above 64 KiB: once per (device, kernel) — the attribute is per device.
-static int ensure_lds(const void* fn, size_t lds, int dev) {
+int gl::ensure_lds(const void* fn, size_t lds, int dev) {
     if (lds <= 65536) return GEMLITE_OK;
     struct Done { const void* fn; int dev; };
     static thread_local Done done[32] = {};
@@ -1012,6 +1015,17 @@ void gemlite_hip_capture_group_wave_split(int32_t layers_in_block, int32_t wave,
     out[0] = s.layer; out[1] = s.v0; out[2] = s.v1;
 }
 
+int gemlite_hip_capture_group_last_form(void) { return capture_group_last_form(); }
+
+int gemlite_hip_capture_group_form(int32_t members, int32_t same_x, int64_t K) {
+    if (members < 1 || members > DECODE3_GMAX || K <= 0 || (K & 255)) return -1;
+    return decode3_group_form(members, same_x != 0, K / 256, capture_group_shared_x_enabled());
+}
+
+int64_t gemlite_hip_capture_group_shared_x_lds_bytes(int64_t K) {
+    return (K > 0 && !(K & 255)) ? decode3_shared_x_lds_bytes(K / 256) : 0;
+}
+
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b) {
     if (validate(a) != GEMLITE_OK || validate(b) != GEMLITE_OK) return 0;
     Resolved ra, rb;
@@ -1101,7 +1115,7 @@ static int launch_resolved(const gemlite_hip_forward_args* args, Resolved& r, in
             // under stream capture an independent neighbour joins the node of the launch before it (capture_group.hip); a launch with
             // profile events or the timeline probe is always its own
             const bool plain = tl_evt_start || tl_evt_stop;
-            if (!plain && capture_group_try_join(*args, r.lp, st, resident)) return GEMLITE_OK;
+            if (!plain && capture_group_try_join(*args, r.lp, st, resident, dev)) return GEMLITE_OK;
             const int rc = launch(r.lp.fn, r.lp.grid, r.lp.block, dargs, 0, st);
             if (!plain && rc == GEMLITE_OK) capture_group_note_launch(*args, r.lp, st);
             return rc;

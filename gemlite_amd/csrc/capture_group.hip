@@ -20,7 +20,12 @@
 // member.  A dependent chain (x_B overlaps out_A) never groups and gets the graph it always got, node for node.  Any HIP error on this path
 // drops the group and the call is launched the plain way: grouping never turns a working capture into a failing one.
 //
-// GEMLITE_HIP_NO_CAPTURE_GROUPS=1 (read once) turns it off; GEMLITE_HIP_CAPTURE_GROUP_MAX=n (development, read once) lowers the member limit.
+// A group whose members all read the SAME x (q / k / v, gate / up, the experts of one token) takes the shared-x form of the grouped kernel
+// (gemv_decode.hip: x is staged in LDS once per block): the form is chosen again at every join (decode3_group_form, gl_common.h), so the
+// first member with another x puts the group back on the per-wave-x form for good.
+//
+// GEMLITE_HIP_NO_CAPTURE_GROUPS=1 (read once) turns it off; GEMLITE_HIP_CAPTURE_GROUP_MAX=n (development, read once) lowers the member limit;
+// GEMLITE_HIP_CAPTURE_GROUP_SHARED_X=0 (read once) keeps every group on the per-wave-x form (A/B runs in separate processes).
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -33,6 +38,8 @@ const void* gemv_w4_decode3_fn(int tag, bool nt);        // gemv_decode.hip
 const void* gemv_w4_decode3_group_fn(int tag);           // gemv_decode.hip: default-policy weight loads whatever the members' launches use
 const void* gemv_w4_decode3_bias_fn(int tag, bool nt);        // the forms that add a bias in the epilogue: a group holds one kind only
 const void* gemv_w4_decode3_bias_group_fn(int tag);            // (the kernel functions differ, so same_launch() keeps them apart)
+const void* gemv_w4_decode3_group_sx_fn(int tag, bool biased);  // gemv_decode.hip: the shared-x grouped forms
+int ensure_lds(const void* fn, size_t lds, int dev);            // api.hip
 
 namespace {
 
@@ -101,6 +108,15 @@ const void* group_fn_of(const void* fn) {
     return nullptr;
 }
 
+const void* group_sx_fn_of(const void* fn) {
+    for (int tag = 0; tag < 2; ++tag)
+        for (int nt = 0; nt < 2; ++nt) {
+            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_sx_fn(tag, false);
+            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_group_sx_fn(tag, true);
+        }
+    return nullptr;
+}
+
 int env_int(const char* name, int absent) {
     const char* v = getenv(name);
     return (v && *v) ? atoi(v) : absent;
@@ -116,12 +132,15 @@ struct Group {
     hipGraphNode_t node = nullptr;
     LaunchPlan lp{};  // member 0: kernel, grid, block, scalars
     const void* fn_group = nullptr;
+    const void* fn_group_sx = nullptr;
+    bool same_x = true;  // every member so far reads member 0's x
     Decode3GroupTable tab{};
     Decode3BiasGroupTable tabb{};  // the table of a biased group (lp.bias set) instead of `tab`
     Footprint fp[DECODE3_GMAX];
     int members = 0;
 };
 thread_local Group tl_group;
+thread_local int tl_last_form = 0;  // of the last group node this thread rewrote: decode3_group_form()
 
 bool capture_state(hipStream_t st, unsigned long long* id, hipGraph_t* graph, hipGraphNode_t* only_dep) {
     hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
@@ -148,6 +167,13 @@ int capture_group_limit() {
     return limit;
 }
 
+bool capture_group_shared_x_enabled() {
+    static const bool on = env_int("GEMLITE_HIP_CAPTURE_GROUP_SHARED_X", 1) != 0;
+    return on;
+}
+
+int capture_group_last_form() { return tl_last_form; }
+
 void capture_group_stats(uint64_t* seen, uint64_t* joined) {
     if (seen) *seen = g_seen.load(std::memory_order_relaxed);
     if (joined) *joined = g_joined.load(std::memory_order_relaxed);
@@ -161,7 +187,7 @@ bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPla
 // Called in front of every decode3 launch that carries no profile events.  true: the call was folded into the open group's node, nothing
 // is left to launch.  false: launch as always, then call capture_group_note_launch().  resident: blocks of a one-block-per-CU kernel
 // the stream's device holds at once (its CU count).
-bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident) {
+bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident, int dev) {
     Group& g = tl_group;
     g.capturing = false;
     if (capture_group_limit() < 2 || (lp.d3.modes & 64u)) return false;
@@ -187,14 +213,20 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     // the node as it is after this join: members and grid.y are recomputed every time and travel in `modes` (no implicit grid arguments)
     const int members = g.members + 1, grid_y = decode3_group_grid_y(g.lp.grid.x, members, resident);
     uint32_t modes = decode3_group_modes(d.modes, members, grid_y);
+    // (the shared-x tables have the layout of the other two: the same objects are passed)
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                      (void*)&d.nch_total, (void*)&modes, biased ? (void*)&g.tabb : (void*)&g.tab};
+    const bool same_x = g.same_x && lp.d3.x == d.x;
+    int form = decode3_group_form(members, same_x, d.nch_total, capture_group_shared_x_enabled() && g.fn_group_sx != nullptr);
+    const size_t lds = form == 2 ? (size_t)decode3_shared_x_lds_bytes(d.nch_total) : 0;
+    // (the cap is raised once per kernel and device, to the form's maximum: the size of a launch depends on its K)
+    if (form == 2 && ensure_lds(g.fn_group_sx, (size_t)DECODE3_SHARED_X_MAX_LDS, dev) != GEMLITE_OK) form = 1;
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
-    np.func = (void*)g.fn_group;
+    np.func = (void*)(form == 2 ? g.fn_group_sx : g.fn_group);
     np.gridDim = dim3(g.lp.grid.x, (unsigned)grid_y, 1);
     np.blockDim = g.lp.block;
-    np.sharedMemBytes = 0;
+    np.sharedMemBytes = form == 2 ? (unsigned)lds : 0;
     np.kernelParams = kargs;
     np.extra = nullptr;
     if (hipGraphKernelNodeSetParams(g.node, &np) != hipSuccess) {  // the node keeps what it had; this call runs on its own
@@ -203,6 +235,8 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
         return false;
     }
     g.fp[g.members++] = fb;
+    g.same_x = same_x;
+    tl_last_form = form;
     g_joined.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
@@ -228,6 +262,9 @@ void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPl
     g.node = dep;
     g.lp = lp;
     g.fn_group = fn_group;
+    g.fn_group_sx = group_sx_fn_of(lp.fn);
+    g.same_x = true;
+    tl_last_form = 0;  // (a group of one: no grouped node yet)
     memset(&g.tab, 0, sizeof(g.tab));
     memset(&g.tabb, 0, sizeof(g.tabb));
     g.tabb.bias[0] = lp.bias;

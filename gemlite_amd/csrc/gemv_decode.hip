@@ -20,6 +20,19 @@
 #include "gl_common.h"
 #include "gl_async.h"  // gvw: counted asm requests, ring2_run (the grouped form)
 
+// Development only (profiles/r15/decode_group_shared_x.log, the two floors): -DGL_DECODE3_ABLATION=1 replaces the arithmetic of a grouped item
+// by an xor of its loaded registers (requests and waits unchanged: the memory-side floor of the request pattern), =2 sends every request
+// behind a wave's first two to the addresses of its first item (cache-hot; arithmetic unchanged: the issue-side floor).  Outputs are wrong
+// by construction.  Not defined in any build the Makefile knows.
+#ifndef GL_DECODE3_ABLATION
+#define GL_DECODE3_ABLATION 0
+#endif
+// Development only (the same log, §4): -DGL_DECODE3_DOT2_ZERO=1 writes the first product of each fp16 accumulator of the grouped forms as
+// the three-operand v_dot2_f32_f16 with a literal 0 (hipcc emits v_mov 0 + v_dot2c from the builtin).
+#ifndef GL_DECODE3_DOT2_ZERO
+#define GL_DECODE3_DOT2_ZERO 0
+#endif
+
 namespace gl {
 
 namespace dec3 {
@@ -50,10 +63,19 @@ constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
 // dependent chains, eager launches and profiled launches run it.
 // Tail = Decode3BiasTail / Decode3BiasGroupTable: the same two forms with the bias add in the epilogue (gl_common.h has the arithmetic).
 // The lanes of wave 0 that store ask for their bias element in front of the layer's barrier, so it arrives under the reduction.
+// Tail = Decode3GroupTableSX / Decode3BiasGroupTableSX: the SHARED-X grouped forms, for a group whose members all read the same x.  What a
+// lane derives from x — the pair dwords (x0,x4)(x1,x5)(x2,x6)(x3,x7) of its two rows and the sum of its 16 activations — depends on x
+// alone, and the other grouped forms derive it again in every quad of every wave of every block: 8 DPP broadcasts, 8 v_perm, 8 dot
+// products and one of five memory requests per item.  Here thread u of a block does it ONCE for the units u, u + 1024, ... < K / 16 (x[16 u .. 16 u + 15], the rows
+// 2 u, 2 u + 1), with the same instructions in the same order, and writes 36 bytes to LDS; an item is then four requests and three LDS
+// reads.  The x loads go out first, the wave's first two items behind them, and the counted wait in front of the one extra barrier
+// covers the x loads only: the weight requests stay in flight across it.
 template <typename Tail>
 struct Decode3TailKind {
-    static constexpr bool grouped = std::is_same<Tail, Decode3GroupTable>::value || std::is_same<Tail, Decode3BiasGroupTable>::value;
-    static constexpr bool biased = std::is_same<Tail, Decode3BiasTail>::value || std::is_same<Tail, Decode3BiasGroupTable>::value;
+    static constexpr bool shared_x = std::is_same<Tail, Decode3GroupTableSX>::value || std::is_same<Tail, Decode3BiasGroupTableSX>::value;
+    static constexpr bool grouped = std::is_same<Tail, Decode3GroupTable>::value || std::is_same<Tail, Decode3BiasGroupTable>::value || shared_x;
+    static constexpr bool biased = std::is_same<Tail, Decode3BiasTail>::value || std::is_same<Tail, Decode3BiasGroupTable>::value ||
+                                   std::is_same<Tail, Decode3BiasGroupTableSX>::value;
 };
 
 template <typename Tag, bool NT, typename Tail = unsigned*>
@@ -62,13 +84,13 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
                             uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
                             const Tail counters) {
     using namespace dec3;
-    constexpr bool GROUPED = Decode3TailKind<Tail>::grouped, BIASED = Decode3TailKind<Tail>::biased;
+    constexpr bool GROUPED = Decode3TailKind<Tail>::grouped, BIASED = Decode3TailKind<Tail>::biased, SX = Decode3TailKind<Tail>::shared_x;
     using TR = F16Traits<Tag>;
     constexpr bool SUBN = TR::DT == GEMLITE_DT_FP16;
     constexpr int WP = SUBN ? 2 : 1;  // 4-bit fields per 16-bit window (Window<Tag, 4>::WP of gemv_wn.hip)
     constexpr int R = 2, NW = 16, CHUNK = 32, TC = 16, CSTRIDE = NW * CHUNK;
     constexpr int RED = NW * 4 * TC;
-    __shared__ __attribute__((aligned(16))) float red[(GROUPED ? DECODE3_GMAX : 1) * RED];  // [NW * 4 DPP rows][16 columns] (grouped: x the layers a block can hold, 64 KiB)
+    __shared__ __attribute__((aligned(16))) float red[(GROUPED && !SX ? DECODE3_GMAX : 1) * RED];  // [NW * 4 DPP rows][16 columns] (grouped: x the layers a block can hold, 64 KiB; shared x: dynamic LDS instead)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -131,6 +153,8 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
 #pragma unroll
     for (int i = 0; i < WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
 
+    // shared x: the lane's unit as staged in LDS — the pair dwords of its two rows and the sum of its 16 activations
+    struct XStage { u32x4 p[R]; float sum; } xs;
     // full = std::true_type: the caller knows need_s && need_z (the grouped loop's common case), the two selects are compiled out
     auto compute = [&](const Chunk& ck, auto full) {
         constexpr bool FULL = decltype(full)::value;
@@ -145,18 +169,26 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             for (int j = 0; j < 4; ++j) acc[wi][j] = 0.f;
         float xsum = 0.f;
         // quad lane j holds dwords (2 (j & 1), 2 (j & 1) + 1) of row j >> 1: row i's dwords d0..d3 = (x0x1)(x2x3)(x4x5)(x6x7)
-        const uint32_t a0 = dpp_mov<0x00>(ck.xq[0]), a1 = dpp_mov<0x00>(ck.xq[1]), a2 = dpp_mov<0x55>(ck.xq[0]), a3 = dpp_mov<0x55>(ck.xq[1]);
-        const uint32_t b0 = dpp_mov<0xAA>(ck.xq[0]), b1 = dpp_mov<0xAA>(ck.xq[1]), b2 = dpp_mov<0xFF>(ck.xq[0]), b3 = dpp_mov<0xFF>(ck.xq[1]);
+        uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+        if constexpr (!SX) {
+            a0 = dpp_mov<0x00>(ck.xq[0]), a1 = dpp_mov<0x00>(ck.xq[1]), a2 = dpp_mov<0x55>(ck.xq[0]), a3 = dpp_mov<0x55>(ck.xq[1]);
+            b0 = dpp_mov<0xAA>(ck.xq[0]), b1 = dpp_mov<0xAA>(ck.xq[1]), b2 = dpp_mov<0xFF>(ck.xq[0]), b3 = dpp_mov<0xFF>(ck.xq[1]);
+        }
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             const uint32_t d0 = i ? b0 : a0, d1 = i ? b1 : a1, d2 = i ? b2 : a2, d3 = i ? b3 : a3;
             uint32_t xr[4];  // pairs (x0,x4)(x1,x5)(x2,x6)(x3,x7)
-            xr[0] = __builtin_amdgcn_perm(d2, d0, 0x05040100u);
-            xr[1] = __builtin_amdgcn_perm(d2, d0, 0x07060302u);
-            xr[2] = __builtin_amdgcn_perm(d3, d1, 0x05040100u);
-            xr[3] = __builtin_amdgcn_perm(d3, d1, 0x07060302u);
+            if constexpr (SX) {
 #pragma unroll
-            for (int dd = 0; dd < 4; ++dd) xsum = TR::dot2(xr[dd], TR::ONES2, xsum);
+                for (int dd = 0; dd < 4; ++dd) xr[dd] = xs.p[i][dd];
+            } else {
+                xr[0] = __builtin_amdgcn_perm(d2, d0, 0x05040100u);
+                xr[1] = __builtin_amdgcn_perm(d2, d0, 0x07060302u);
+                xr[2] = __builtin_amdgcn_perm(d3, d1, 0x05040100u);
+                xr[3] = __builtin_amdgcn_perm(d3, d1, 0x07060302u);
+#pragma unroll
+                for (int dd = 0; dd < 4; ++dd) xsum = TR::dot2(xr[dd], TR::ONES2, xsum);
+            }
 #pragma unroll
             for (int dd = 0; dd < 4; ++dd) {
                 const int win = dd / WP, wi = dd % WP;
@@ -164,10 +196,19 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
                 for (int j = 0; j < 4; ++j) {
                     uint32_t h = (ck.w[i][j] >> (4 * WP * win)) & wmask[wi];
                     if constexpr (!SUBN) h |= TR::MAGIC2;
+#if GL_DECODE3_DOT2_ZERO
+                    if constexpr (SUBN && GROUPED) {
+                        if (i == 0 && win == 0) {  // the first product of the accumulator: three operands, no zero to move
+                            asm("v_dot2_f32_f16 %0, %1, %2, 0" : "=v"(acc[wi][j]) : "v"(h), "v"(xr[dd]));
+                            continue;
+                        }
+                    }
+#endif
                     acc[wi][j] = TR::dot2(h, xr[dd], acc[wi][j]);
                 }
             }
         }
+        if constexpr (SX) xsum = xs.sum;  // (the same chain of eight dot products from 0.f, run once per block)
         const uint32_t s0 = ck.s[0], s1 = ck.s[1], z0 = ck.z[0], z1 = ck.z[1];
         float s[4] = {TR::to_float((uint16_t)(s0 & 0xFFFFu)), TR::to_float((uint16_t)(s0 >> 16)), TR::to_float((uint16_t)(s1 & 0xFFFFu)), TR::to_float((uint16_t)(s1 >> 16))};
         float z[4] = {TR::to_float((uint16_t)(z0 & 0xFFFFu)), TR::to_float((uint16_t)(z0 >> 16)), TR::to_float((uint16_t)(z1 & 0xFFFFu)), TR::to_float((uint16_t)(z1 >> 16))};
@@ -234,7 +275,8 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         // arithmetic at different times.  A wave's items — its virtual waves in ascending order, each one's chunks in ascending order — are
         // a flat list of known length: gvw::ring2_run (gl_async.h) with five counted asm requests per item (w, w, x, s, z).  Every base is
         // a uniform SGPR pair moved by scalar arithmetic, every per-lane offset is set up once: the loop holds no vector address
-        // arithmetic and no select.  Bit-exact: `tot` accumulates a virtual wave's chunks in ascending order; at its end the two row_ror
+        // arithmetic and no select (the shared-x forms: four requests (w, w, s, z) and three LDS reads per item, whose two lane addresses
+        // move by one vector add each).  Bit-exact: `tot` accumulates a virtual wave's chunks in ascending order; at its end the two row_ror
         // sums, the partial row v * 4 + (lane >> 4) of the LAYER'S OWN 4 KB of LDS, `tot` back to zero (a virtual wave without a chunk
         // writes zeros: K < 4096); after the barrier waves 0 .. LB - 1 each run the single-layer epilogue on one layer's region.
         const int members = (int)((modes >> 16) & 255u), Y = (int)(modes >> 24), y = (int)blockIdx.y;
@@ -261,25 +303,45 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         const uint32_t chunk_w = (uint32_t)CHUNK * sw4;
         const int nv = v1 - v0, rem = (nch_total & (NW - 1)) - v0;
         const int n = (nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem));  // items of this wave (0: an idle wave, or K too short)
-        float* rd = red + li * RED;
+        // shared x: [partial rows, 64 KiB][units x 8 pair dwords][units x sum], units = 16 per chunk (gl_common.h: decode3_shared_x_lds_bytes)
+        float* redg;
+        uint32_t* xpairs = nullptr;
+        float* xsums = nullptr;
+        const int units = nch_total * 16;
+        if constexpr (SX) {
+            extern __shared__ __attribute__((aligned(16))) float d3_lds[];
+            redg = d3_lds;
+            xpairs = (uint32_t*)(d3_lds + DECODE3_GMAX * RED);
+            xsums = (float*)(xpairs + units * 8);
+        } else {
+            redg = red;
+        }
+        float* rd = redg + li * RED;
 
-        constexpr int NLC = 5;
+        constexpr int NLC = SX ? 4 : 5;
         int rv = v0, rgc = v0;  // request cursor: virtual wave, chunk
-        auto request = [&](Chunk& ck, int) __attribute__((always_inline)) {
+        auto request = [&](Chunk& ck, int ri) __attribute__((always_inline)) {
+#if GL_DECODE3_ABLATION == 2
+            const int keep = rgc;
+            if (ri >= 2) rgc = v0;
+#endif
             const char* wq = w_ + (uint32_t)rgc * chunk_w;
             gvw::gld128<NT>(ck.w[0], wq, vw0);
             gvw::gld128<NT>(ck.w[1], wq, vw1);
-            gvw::gld64(ck.xq, x_ + (uint32_t)rgc * (uint32_t)(CHUNK * 16), vx);
+            if constexpr (!SX) gvw::gld64(ck.xq, x_ + (uint32_t)rgc * (uint32_t)(CHUNK * 16), vx);
             const uint32_t grp = ((uint32_t)rgc << shl) >> shr;
             gvw::gld64(ck.s, sb + grp * ms_s, vs);
             gvw::gld64(ck.z, zb + grp * ms_z, vz);
+#if GL_DECODE3_ABLATION == 2
+            rgc = keep;
+#endif
             rgc += NW;
             if (rgc >= nch_total) rgc = ++rv;
         };
         auto tie_chunk = [&](Chunk& ck) __attribute__((always_inline)) {
             gvw::tie(ck.w[0]);
             gvw::tie(ck.w[1]);
-            gvw::tie(ck.xq);
+            if constexpr (!SX) gvw::tie(ck.xq);
             gvw::tie(ck.s);
             gvw::tie(ck.z);
         };
@@ -299,12 +361,82 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         int cv = v0, cgc = v0;  // compute cursor
         // (the first two requests belong to the variant that consumes them: requested ahead of the branch, their registers — still in
         // flight — were COPIED into each variant's own set in front of its loop)
+        // shared x, staging: unit u's 32 bytes of x become its eight pair dwords and its sum with the instructions compute() runs on them
+        // (rows 2 u and 2 u + 1: dwords 0..3 and 4..7; the sum chain from 0.f over row 2 u's pairs, then row 2 u + 1's)
+        auto stage_unit = [&](int u, const u32x4& lo, const u32x4& hi) __attribute__((always_inline)) {
+            u32x4 pr[R];
+            float xsum = 0.f;
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const u32x4& d = i ? hi : lo;
+                pr[i][0] = __builtin_amdgcn_perm(d[2], d[0], 0x05040100u);
+                pr[i][1] = __builtin_amdgcn_perm(d[2], d[0], 0x07060302u);
+                pr[i][2] = __builtin_amdgcn_perm(d[3], d[1], 0x05040100u);
+                pr[i][3] = __builtin_amdgcn_perm(d[3], d[1], 0x07060302u);
+#pragma unroll
+                for (int dd = 0; dd < 4; ++dd) xsum = TR::dot2(pr[i][dd], TR::ONES2, xsum);
+            }
+            if (u < units) {
+                *(u32x4*)(xpairs + u * 8) = pr[0];
+                *(u32x4*)(xpairs + u * 8 + 4) = pr[1];
+                xsums[u] = xsum;
+            }
+        };
+        // (a lane past the last unit loads the last unit's bytes and writes nothing: units is a multiple of 16, not of 64)
+        auto stage_off = [&](int u) { return (uint32_t)(u < units ? u : units - 1) * 32u; };
+        constexpr int STRIPS = (int)((DECODE3_SHARED_X_MAX_UNITS + 1023) / 1024);  // staging trips of the 1024 threads: what fits in LDS
+        // the lane's unit of chunk 0; chunk gc is 128 dwords of pairs and 16 sums further: one vector add each per item
+        const uint32_t* xp_lane = xpairs + g * 8;
+        const float* xs_lane = xsums + g;
         auto run = [&](auto full) {
             Chunk A, B;
-            if (n > 0) request(A, 0);
-            if (n > 1) request(B, 1);
-            gvw::ring2_run<NLC>(n, A, B, request, tie_chunk, [&](const Chunk& ck, int) __attribute__((always_inline)) {
+            if constexpr (SX) {
+                // thread u loads the units u, u + 1024, ... (all trips' loads first), then the wave's first two items go out, then ONE wait
+                // for the x loads alone: they are older than every item request
+                u32x4 lo[STRIPS], hi[STRIPS];
+#pragma unroll
+                for (int t = 0; t < STRIPS; ++t) {
+                    if (wave * 64 + t * 1024 < units) {
+                        const uint32_t so = stage_off(tid + t * 1024);
+                        gvw::gld128<false>(lo[t], xb, so);
+                        gvw::gld128<false>(hi[t], xb, so + 16u);
+                    }
+                }
+                if (n > 0) request(A, 0);
+                if (n > 1) request(B, 1);
+                if (wave * 64 < units) {
+                    if (n > 1) gvw::wait_vm<2 * NLC>(); else if (n > 0) gvw::wait_vm<NLC>(); else gvw::wait_vm<0>();
+#pragma unroll
+                    for (int t = 0; t < STRIPS; ++t) {
+                        if (wave * 64 + t * 1024 < units) {
+                            gvw::tie(lo[t]);
+                            gvw::tie(hi[t]);
+                            stage_unit(tid + t * 1024, lo[t], hi[t]);
+                        }
+                    }
+                }
+                __syncthreads();
+            } else {
+                if (n > 0) request(A, 0);
+                if (n > 1) request(B, 1);
+            }
+            gvw::ring2_run_pre<NLC>(n, A, B, request, tie_chunk, [&](int) __attribute__((always_inline)) {
+                if constexpr (SX) {
+                    const uint32_t* xp = xp_lane + cgc * 128;
+                    xs.p[0] = *(const u32x4*)xp;
+                    xs.p[1] = *(const u32x4*)(xp + 4);
+                    xs.sum = xs_lane[cgc * 16];
+                }
+            }, [&](const Chunk& ck, int) __attribute__((always_inline)) {
+#if GL_DECODE3_ABLATION == 1
+                uint32_t acc = ck.s[0] ^ ck.s[1] ^ ck.z[0] ^ ck.z[1];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc ^= ck.w[0][j] ^ ck.w[1][j];
+                if constexpr (SX) acc ^= xs.p[0][0] ^ xs.p[1][3] ^ __builtin_bit_cast(uint32_t, xs.sum); else acc ^= ck.xq[0] ^ ck.xq[1];
+                tot[0] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, tot[0]) ^ acc);
+#else
                 compute(ck, full);
+#endif
                 cgc += NW;
                 if (cgc >= nch_total) {
                     flush(cv);
@@ -332,7 +464,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         }
         __syncthreads();
         if (fin) {
-            const float* rf = red + wave * RED;
+            const float* rf = redg + wave * RED;
             constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
             const int o = lane & 15, part = lane >> 4;
             float v = 0.f;
@@ -361,6 +493,18 @@ const void* gemv_w4_decode3_fn(int tag, bool nt) {
 const void* gemv_w4_decode3_group_fn(int tag) {
     typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3GroupTable);
     kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTable>;
+    return (const void*)k;
+}
+
+// The shared-x grouped forms (dynamic LDS: decode3_shared_x_lds_bytes), unbiased / biased
+const void* gemv_w4_decode3_group_sx_fn(int tag, bool biased) {
+    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3GroupTableSX);
+    typedef void (*kfnb)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3BiasGroupTableSX);
+    if (biased) {
+        kfnb k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3BiasGroupTableSX> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3BiasGroupTableSX>;
+        return (const void*)k;
+    }
+    kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTableSX> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTableSX>;
     return (const void*)k;
 }
 

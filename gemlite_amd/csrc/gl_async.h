@@ -139,15 +139,19 @@ __device__ __forceinline__ void tie(T& v) { asm volatile("" : "+v"(v)); }
 // Two chunk buffers A / B, one chunk in flight while the other is computed on.  NLC = requests per chunk.  On entry A holds chunk 0 and B
 // chunk 1 (requested by the caller, those that exist).  Steady state: unconditional requests, ONE wait value ("everything but the newest
 // chunk has landed": loads return in order); the last one to three chunks are peeled, their waits picked by uniform branches.
-template <int NLC, typename Buf, typename Issue, typename Tie, typename Compute>
-__device__ __forceinline__ void ring2_run(int n, Buf& A, Buf& B, Issue&& issue, Tie&& tie_buf, Compute&& compute) {
+// `pre(i)` runs in front of the wait for chunk i: what chunk i needs from elsewhere (the shared-x grouped decode kernel: its LDS reads of x)
+// is asked for before the wave goes to sleep on the counter.
+template <int NLC, typename Buf, typename Issue, typename Tie, typename Pre, typename Compute>
+__device__ __forceinline__ void ring2_run_pre(int n, Buf& A, Buf& B, Issue&& issue, Tie&& tie_buf, Pre&& pre, Compute&& compute) {
     int i = 0;
 #pragma unroll 1
     for (; i + 4 <= n; i += 2) {
+        pre(i);
         wait_vm<NLC>();
         tie_buf(A);
         compute(A, i);
         issue(A, i + 2);
+        pre(i + 1);
         wait_vm<NLC>();
         tie_buf(B);
         compute(B, i + 1);
@@ -155,20 +159,27 @@ __device__ __forceinline__ void ring2_run(int n, Buf& A, Buf& B, Issue&& issue, 
     }
     const int rem = n - i;  // 0 (no chunk at all), 1, 2 or 3
     if (rem >= 1) {
+        pre(i);
         if (rem >= 2) wait_vm<NLC>(); else wait_vm<0>();
         tie_buf(A);
         compute(A, i);
         if (rem >= 2) {
+            pre(i + 1);
             if (rem == 3) { issue(A, i + 2); wait_vm<NLC>(); } else wait_vm<0>();
             tie_buf(B);
             compute(B, i + 1);
             if (rem == 3) {
+                pre(i + 2);
                 wait_vm<0>();
                 tie_buf(A);
                 compute(A, i + 2);
             }
         }
     }
+}
+template <int NLC, typename Buf, typename Issue, typename Tie, typename Compute>
+__device__ __forceinline__ void ring2_run(int n, Buf& A, Buf& B, Issue&& issue, Tie&& tie_buf, Compute&& compute) {
+    ring2_run_pre<NLC>(n, A, B, issue, tie_buf, [](int) {}, compute);
 }
 }  // namespace gvw
 

@@ -621,6 +621,32 @@ struct Decode3BiasGroupTable {
     Decode3Member m[DECODE3_GMAX - 1];
     const uint16_t* bias[DECODE3_GMAX];
 };
+// The SHARED-X grouped forms: every member reads the same x (q / k / v, gate / up, the experts of one token), so a block stages the pair
+// dwords and the per-unit sums of x in LDS once and its waves read them from there (gemv_decode.hip).  Same tables under their own type
+// names (the kernel functions differ); the members' x pointers are not read.
+struct Decode3GroupTableSX {
+    Decode3Member m[DECODE3_GMAX - 1];
+};
+struct Decode3BiasGroupTableSX {
+    Decode3Member m[DECODE3_GMAX - 1];
+    const uint16_t* bias[DECODE3_GMAX];
+};
+// LDS of a shared-x block: the 64 KiB of partial rows (DECODE3_GMAX layers x 4 KiB), then per 16-element unit of x (K / 16 = 16 per 32-row
+// chunk) 32 bytes of pair dwords, then per unit its 4-byte sum: 64 KiB + 2.25 K bytes, dynamic.  The block's 1024 threads stage the
+// units in trips of 1024.  0: the staging area does not fit beside the partial rows in the 160 KiB of a CU (K > 43520).
+constexpr int64_t DECODE3_RED_BYTES = (int64_t)DECODE3_GMAX * 16 * 4 * 16 * 4, DECODE3_LDS_LIMIT = 160 * 1024;
+constexpr int64_t DECODE3_SHARED_X_MAX_UNITS = ((DECODE3_LDS_LIMIT - DECODE3_RED_BYTES) / 36) & ~(int64_t)15;  // 2720, whole chunks
+constexpr int64_t DECODE3_SHARED_X_MAX_LDS = DECODE3_RED_BYTES + DECODE3_SHARED_X_MAX_UNITS * 36;  // the cap api.hip raises once per kernel
+// (two members: staging and its barrier cost more than they save, 4.11 us per layer against 3.82 — profiles/r15/decode_group_shared_x.log §5)
+constexpr int DECODE3_SHARED_X_MIN_MEMBERS = 3;
+inline int64_t decode3_shared_x_lds_bytes(int64_t nch_total) {
+    return (nch_total > 0 && nch_total * 16 <= DECODE3_SHARED_X_MAX_UNITS) ? DECODE3_RED_BYTES + nch_total * 16 * 36 : 0;
+}
+// The form of a grouped node: 0 no group (one member), 1 per-wave x (every wave loads the x of its own layer), 2 shared x
+inline int decode3_group_form(int members, bool same_x, int64_t nch_total, bool shared_x_enabled) {
+    if (members < 2) return 0;
+    return (shared_x_enabled && same_x && members >= DECODE3_SHARED_X_MIN_MEMBERS && decode3_shared_x_lds_bytes(nch_total) > 0) ? 2 : 1;
+}
 inline uint32_t decode3_group_modes(uint32_t modes, int members, int grid_y) {
     return (modes & 0xFFFFu) | ((uint32_t)members << 16) | ((uint32_t)grid_y << 24);
 }

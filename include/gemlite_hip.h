@@ -339,12 +339,24 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
  *   _wave_split  host only: how the 16 waves of a grouped block share its `layers_in_block` layers (1 .. 16), which are all in flight at
  *                once: out = {block-local layer of `wave` (-1: the wave has no work), v0, v1} — the wave does what the single-layer
  *                kernel's waves v0 .. v1 - 1 do for that layer (wave v there: the 32-row chunks v, v + 16, ... of K / 8 packed rows).
- *                16 / layers_in_block waves per layer.  {-1, 0, 0} for an argument out of range */
+ *                16 / layers_in_block waves per layer.  {-1, 0, 0} for an argument out of range
+ *   _last_form   host only: the form of the grouped node the calling thread rewrote last: 0 none (no join since the thread's last group
+ *                opened), 1 per-wave x (every wave loads the x of its own layer), 2 shared x (three or more members that all read the same x pointer: a
+ *                block stages x in LDS once; GEMLITE_HIP_CAPTURE_GROUP_SHARED_X=0, read once, keeps every group on form 1)
+ *   _form, _shared_x_lds_bytes   DEVELOPMENT / TEST exports (tests/test_decode_group_shared_x_cpu.py restates them in Python); not part of
+ *                what a caller needs, and free to change with the kernel:
+ *   _form        host only: the rule behind it for `members` layers (1 .. 16) of reduction length K (a multiple of 256) whose x pointers
+ *                all agree (same_x != 0) or not: 0 / 1 / 2 as above, -1 for an argument out of range
+ *   _shared_x_lds_bytes  host only: dynamic LDS of a shared-x block, 64 KiB of partial rows + 2.25 K bytes of staged x; 0 when that is
+ *                past the 160 KiB of a CU (K > 43520: such a K keeps form 1) or K is no positive multiple of 256 */
 int gemlite_hip_capture_group_max(void);
 void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
 int gemlite_hip_capture_group_grid_y(int32_t tiles, int32_t members);
 void gemlite_hip_capture_group_wave_split(int32_t layers_in_block, int32_t wave, int32_t out[3]);
+int gemlite_hip_capture_group_last_form(void);
+int gemlite_hip_capture_group_form(int32_t members, int32_t same_x, int64_t K);
+int64_t gemlite_hip_capture_group_shared_x_lds_bytes(int64_t K);
 
 /* Bias in the launch (optional extension; gemlite_hip_forward_args and every entry point above are unchanged).  The M = 1 decode kernel
  * (gemv_w4_decode3_kernel, single and grouped) and the few-row kernels (gemm_w4_rows_kernel / gemm_w2_rows_kernel) have forms that add a
