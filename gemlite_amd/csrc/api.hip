@@ -70,6 +70,7 @@ bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPla
 bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident, int dev);
 bool capture_group_shared_x_enabled();
 int capture_group_last_form();
+Decode3TilesWanted capture_group_tiles_wanted(int tiles, int members, int resident);
 int ensure_lds(const void* fn, size_t lds, int dev);
 void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st);
 
@@ -1016,6 +1017,20 @@ void gemlite_hip_capture_group_wave_split(int32_t layers_in_block, int32_t wave,
 }
 
 int gemlite_hip_capture_group_last_form(void) { return capture_group_last_form(); }
+
+int gemlite_hip_capture_group_geometry(int32_t tiles, int32_t members, int32_t resident, int32_t tb_want, int32_t span_want, int32_t out[4]) {
+    if (!out || tiles < 1 || members < 1 || members > DECODE3_GMAX || resident < 1 || tb_want < 0 || tb_want > 4 || tb_want == 3) return -1;
+    Decode3TilesWanted want{tb_want, span_want != 0};
+    if (tb_want == 0) want = capture_group_tiles_wanted(tiles, members, resident);
+    const Decode3GroupGeometry geo = decode3_group_geometry(tiles, members, resident, want.tb, want.span);
+    out[0] = geo.tb; out[1] = geo.grid_x; out[2] = geo.grid_y; out[3] = geo.span ? 1 : 0;
+    return 0;
+}
+
+int gemlite_hip_capture_group_tile_of(int32_t tiles, int32_t tb, int32_t span, int32_t block) {
+    if (tiles < 1 || (tb != 1 && tb != 2 && tb != 4) || tiles % tb || block < 0 || block >= tiles / tb) return -1;
+    return decode3_group_first_tile(block, tiles / tb, tb, span != 0, (tiles & 15) == 0);
+}
 
 int gemlite_hip_capture_group_form(int32_t members, int32_t same_x, int64_t K) {
     if (members < 1 || members > DECODE3_GMAX || K <= 0 || (K & 255)) return -1;

@@ -26,6 +26,12 @@
 //
 // GEMLITE_HIP_NO_CAPTURE_GROUPS=1 (read once) turns it off; GEMLITE_HIP_CAPTURE_GROUP_MAX=n (development, read once) lowers the member limit;
 // GEMLITE_HIP_CAPTURE_GROUP_SHARED_X=0 (read once) keeps every group on the per-wave-x form (A/B runs in separate processes).
+//
+// TILE GROUPS (gl_common.h: decode3_group_geometry): a grouped block may hold TB = 1, 2 or 4 adjacent tiles x its layers, grid
+// (tiles / TB, Y), and its tile groups are placed on the XCDs interleaved or in contiguous spans.  (TB, placement) is chosen again at every
+// join from members, tiles and resident blocks (decode3_group_tiles_default); GEMLITE_HIP_CAPTURE_GROUP_TILES=<TB>[s|i] (development, read
+// once) forces the TB asked for and the span ("s") or interleaved ("i", the default) placement for A/B runs — a TB that does not fit the
+// shape still falls back to the next smaller one.
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -172,6 +178,17 @@ bool capture_group_shared_x_enabled() {
     return on;
 }
 
+// What try_join() asks decode3_group_geometry() for: the forced pair of GEMLITE_HIP_CAPTURE_GROUP_TILES, or the rule of gl_common.h
+Decode3TilesWanted capture_group_tiles_wanted(int tiles, int members, int resident) {
+    static const Decode3TilesWanted forced = [] {
+        const char* v = getenv("GEMLITE_HIP_CAPTURE_GROUP_TILES");
+        if (!v || !*v) return Decode3TilesWanted{0, false};
+        const int tb = atoi(v);
+        return Decode3TilesWanted{tb >= 4 ? 4 : (tb >= 2 ? 2 : 1), strchr(v, 's') != nullptr};
+    }();
+    return forced.tb ? forced : decode3_group_tiles_default(tiles, members, resident);
+}
+
 int capture_group_last_form() { return tl_last_form; }
 
 void capture_group_stats(uint64_t* seen, uint64_t* joined) {
@@ -211,8 +228,10 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     m.w = lp.d3.w; m.x = lp.d3.x; m.s = lp.d3.s; m.z = lp.d3.z; m.out = lp.d3.out;
     Decode3Args& d = g.lp.d3;
     // the node as it is after this join: members and grid.y are recomputed every time and travel in `modes` (no implicit grid arguments)
-    const int members = g.members + 1, grid_y = decode3_group_grid_y(g.lp.grid.x, members, resident);
-    uint32_t modes = decode3_group_modes(d.modes, members, grid_y);
+    const int members = g.members + 1, tiles = (int)g.lp.grid.x;
+    const Decode3TilesWanted want = capture_group_tiles_wanted(tiles, members, resident);
+    const Decode3GroupGeometry geo = decode3_group_geometry(tiles, members, resident, want.tb, want.span);
+    uint32_t modes = decode3_group_modes(d.modes, members, geo.grid_y, geo.tb, geo.span);
     // (the shared-x tables have the layout of the other two: the same objects are passed)
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                      (void*)&d.nch_total, (void*)&modes, biased ? (void*)&g.tabb : (void*)&g.tab};
@@ -224,7 +243,7 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
     np.func = (void*)(form == 2 ? g.fn_group_sx : g.fn_group);
-    np.gridDim = dim3(g.lp.grid.x, (unsigned)grid_y, 1);
+    np.gridDim = dim3((unsigned)geo.grid_x, (unsigned)geo.grid_y, 1);
     np.blockDim = g.lp.block;
     np.sharedMemBytes = form == 2 ? (unsigned)lds : 0;
     np.kernelParams = kargs;

@@ -47,7 +47,8 @@ __device__ __forceinline__ float dpp_movf(float v) {
 }
 
 // modes: bits 0..3 W_group_mode | 4 zero_is_scalar | 5 pair the half-line tiles on one XCD | 6 timeline probe | 8..15 log2(group)
-//        grouped launches only (capture_group.hip): 16..23 members | 24..31 grid.y
+//        grouped launches only (capture_group.hip; gl_common.h: decode3_group_modes): 16..20 members | 21..22 log2(tiles per block) |
+//        23 span placement of the tile groups | 24..31 grid.y
 constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
 
 }  // namespace dec3
@@ -96,7 +97,20 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 3, g = lane >> 2;
     int tile = blockIdx.x;
-    if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
+    // grouped: the block's tile group and this wave's slot = (block-local layer, tile of the group); gl_common.h has the geometry
+    [[maybe_unused]] int g_members = 0, g_Y = 1, g_slots = 1, g_tbl = 0, g_tile0 = 0;
+    [[maybe_unused]] Decode3WaveSplit g_split{0, 0, 16};
+    if constexpr (GROUPED) {
+        g_members = (int)((modes >> 16) & DECODE3_M_MEMBERS);
+        g_Y = (int)(modes >> 24);
+        g_tbl = (int)((modes >> DECODE3_M_TB_SHIFT) & 3u);
+        g_slots = ((g_members - (int)blockIdx.y + g_Y - 1) / g_Y) << g_tbl;
+        g_split = decode3_wave_split(g_slots, wave);
+        // (the span placement alone needs the grid's width: one scalar load of the dispatch's block count, in front of the first request)
+        const bool span = (modes & DECODE3_M_SPAN) != 0u;
+        g_tile0 = decode3_group_first_tile(tile, span ? (int)gridDim.x : 0, 1 << g_tbl, span, (modes & M_PAIR) != 0u);
+        tile = g_tile0 + ((g_split.layer < 0 ? 0 : g_split.layer) & ((1 << g_tbl) - 1));
+    } else if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
         const int xcd = tile & 7, idx = tile >> 3;
         tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
     }
@@ -279,10 +293,11 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         // move by one vector add each).  Bit-exact: `tot` accumulates a virtual wave's chunks in ascending order; at its end the two row_ror
         // sums, the partial row v * 4 + (lane >> 4) of the LAYER'S OWN 4 KB of LDS, `tot` back to zero (a virtual wave without a chunk
         // writes zeros: K < 4096); after the barrier waves 0 .. LB - 1 each run the single-layer epilogue on one layer's region.
-        const int members = (int)((modes >> 16) & 255u), Y = (int)(modes >> 24), y = (int)blockIdx.y;
-        const int LB = (members - y + Y - 1) / Y;
-        const Decode3WaveSplit split = decode3_wave_split(LB, wave);
-        const int li = split.layer < 0 ? 0 : split.layer, v0 = split.v0, v1 = split.v1;
+        // With tile groups (TB = 1 << g_tbl tiles per block) the block's LB * TB slots stand where the layers stand in this description:
+        // slot s is layer s / TB on tile s % TB of the block's group, with its own waves, virtual waves and 4 KB of LDS.
+        const int Y = g_Y, y = (int)blockIdx.y, slots = g_slots;
+        const Decode3WaveSplit split = g_split;
+        const int slot = split.layer < 0 ? 0 : split.layer, li = slot >> g_tbl, v0 = split.v0, v1 = split.v1;
         // this wave's layer: the preloaded scalars (layer 0) or the by-value table, scalar loads either way, once per wave
         const int L = y + li * Y;
         const char *w_ = wb, *x_ = xb, *s_ = sp, *z_ = zp;
@@ -316,7 +331,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         } else {
             redg = red;
         }
-        float* rd = redg + li * RED;
+        float* rd = redg + slot * RED;
 
         constexpr int NLC = SX ? 4 : 5;
         int rv = v0, rgc = v0;  // request cursor: virtual wave, chunk
@@ -451,15 +466,16 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             for (int v = cv; v < v1; ++v) flush(v);  // virtual waves without a chunk
         }
 
-        // waves 0 .. LB - 1 finish one layer each; they ask for its bias element in front of the barrier
-        const bool fin = wave < LB;
+        // waves 0 .. slots - 1 finish one slot each (layer wave / TB on tile wave % TB); they ask for its bias element in front of the barrier
+        const bool fin = wave < slots;
+        const int ftile = g_tile0 + (wave & ((1 << g_tbl) - 1));
         uint16_t* o_ = out;
         uint16_t braw = 0;
         if (fin) {
-            const int Lf = y + wave * Y;
+            const int Lf = y + (wave >> g_tbl) * Y;
             if (Lf > 0) o_ = counters.m[Lf - 1].out;
             if constexpr (BIASED) {
-                if (lane < 16) braw = counters.bias[Lf][tile * TC + lane];
+                if (lane < 16) braw = counters.bias[Lf][ftile * TC + lane];
             }
         }
         __syncthreads();
@@ -474,7 +490,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             v += __shfl_xor(v, 32);
             uint16_t h = TR::from_float(v);
             if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));  // (as in the single-layer form)
-            if (lane < 16) o_[tile * TC + o] = h;
+            if (lane < 16) o_[ftile * TC + o] = h;
         }
     }
 }
@@ -488,8 +504,10 @@ const void* gemv_w4_decode3_fn(int tag, bool nt) {
 }
 
 // The grouped forms exist with default-policy weight loads only (NT = false), whatever the members' own launches use: the two 16-column
-// tiles of a 128-byte line run on one XCD, and with a block's waves out of step the partner asks for its half some time later — a
-// non-temporal line has left the L2 by then (11.6 MB fetched per layer against 9.5; profiles/r13/decode_group_waves.log §2).
+// tiles of a 128-byte line are read by two different waves — with one tile per block (TB = 1) in two blocks on two CUs of one XCD, which
+// meet in that XCD's L2 only; with tile groups (TB = 2, 4) by neighbouring waves of one block — and nothing keeps the two in step: the
+// partner asks for its half some time later, and a non-temporal line has left the L2 by then (11.6 MB fetched per layer against 9.5;
+// profiles/r13/decode_group_waves.log §2).
 const void* gemv_w4_decode3_group_fn(int tag) {
     typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3GroupTable);
     kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTable>;

@@ -647,13 +647,17 @@ inline int decode3_group_form(int members, bool same_x, int64_t nch_total, bool 
     if (members < 2) return 0;
     return (shared_x_enabled && same_x && members >= DECODE3_SHARED_X_MIN_MEMBERS && decode3_shared_x_lds_bytes(nch_total) > 0) ? 2 : 1;
 }
-inline uint32_t decode3_group_modes(uint32_t modes, int members, int grid_y) {
-    return (modes & 0xFFFFu) | ((uint32_t)members << 16) | ((uint32_t)grid_y << 24);
+// `modes` of a grouped launch: members in bits 16..20, log2 of the tiles per block (TB) in 21..22, the span placement in 23, grid.y in
+// 24..31.  TB = 1 without the span bit is the word the launch carried before tile groups existed.
+constexpr uint32_t DECODE3_M_MEMBERS = 31u, DECODE3_M_TB_SHIFT = 21u, DECODE3_M_SPAN = 1u << 23;
+inline uint32_t decode3_group_modes(uint32_t modes, int members, int grid_y, int tb = 1, bool span = false) {
+    return (modes & 0xFFFFu) | ((uint32_t)members << 16) | ((tb == 4 ? 2u : (tb == 2 ? 1u : 0u)) << DECODE3_M_TB_SHIFT) | (span ? DECODE3_M_SPAN : 0u) |
+           ((uint32_t)grid_y << 24);
 }
 // grid.y of a grouped launch of `members` layers of `tiles` 16-column tiles each: block (tile, y) holds the layers y, y + grid.y, ...
 // One block per CU is resident, so a wide layer (tiles >= resident) gets one block per tile that holds every member; a narrow one
 // spreads its members over the CUs its tiles leave idle.
-inline int decode3_group_grid_y(int64_t tiles, int members, int64_t resident) {
+GL_HD int decode3_group_grid_y(int64_t tiles, int members, int64_t resident) {
     const int64_t y = tiles > 0 ? resident / tiles : 1;
     return (int)(y < 1 ? 1 : (y > members ? (members > 1 ? members : 1) : y));
 }
@@ -669,6 +673,69 @@ GL_HD Decode3WaveSplit decode3_wave_split(int lb, int wave) {
     if (li >= lb) return Decode3WaveSplit{-1, 0, 0};
     return Decode3WaveSplit{li, wl * 16 / P, (wl + 1) * 16 / P};
 }
+// TILE GROUPS.  A grouped block holds TB in {1, 2, 4} ADJACENT 16-column tiles x LB layers: grid (tiles / TB, Y) with
+// Y = decode3_group_grid_y(tiles / TB, members, resident) and LB = ceil((members - y) / Y).  Its LB * TB (layer, tile) SLOTS (at most 16)
+// take the place of the layers in decode3_wave_split(): slot s is block-local layer s / TB and tile s % TB of the block's tile group, so
+// the waves that read the two (TB = 2) or four (TB = 4: two lines) 64-byte halves of a weight row's 128-byte lines are neighbours on one
+// CU and walk the same item list.  Each slot owns one 4 KiB partial-row region, as each layer did.
+// The rule: the largest TB <= tb_want with tiles % TB == 0 and ceil(members / Y) * TB <= 16.
+struct Decode3GroupGeometry {
+    int tb, grid_x, grid_y;
+    bool span;
+};
+GL_HD Decode3GroupGeometry decode3_group_geometry(int tiles, int members, int64_t resident, int tb_want, bool span) {
+    for (int tb = tb_want >= 4 ? 4 : (tb_want >= 2 ? 2 : 1); tb > 1; tb >>= 1) {
+        if (tiles % tb) continue;
+        const int y = decode3_group_grid_y(tiles / tb, members, resident);
+        if ((members + y - 1) / y * tb <= 16) return Decode3GroupGeometry{tb, tiles / tb, y, span};
+    }
+    return Decode3GroupGeometry{1, tiles, decode3_group_grid_y(tiles, members, resident), span};
+}
+// Block x of `groups` = tiles / TB -> the first tile of its tile group (speed only: any permutation is correct).  Blocks are dealt
+// round-robin over the 8 XCDs, so block b runs on "XCD" b % 8.
+//   interleaved (span = false): TB = 1 and `pair` (tiles % 16 == 0): the pair map — XCD x takes the tiles 16 m + 2 x, 16 m + 2 x + 1 (both
+//       halves of the lines 8 m + x of a weight row); otherwise the identity (TB = 2: XCD x takes the lines 8 m + x as before, each
+//       inside one block).
+//   span (span = true): XCD x takes the contiguous tile groups [x groups / 8, (x + 1) groups / 8); the identity when groups % 8 != 0.
+GL_HD int decode3_group_first_tile(int block, int groups, int tb, bool span, bool pair) {
+    const int xcd = block & 7, idx = block >> 3;
+    int grp = block;
+    if (span) {
+        if ((groups & 7) == 0) grp = xcd * (groups >> 3) + idx;
+    } else if (pair && tb == 1) {
+        grp = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
+    }
+    return grp * tb;
+}
+// What capture_group.hip asks decode3_group_geometry() for when nothing is forced: {tb_want, span} from the group's shape.
+// THE RULE (measured: profiles/r16/decode_group_tiles.log §4 - §6): the interleaved placement, and the largest TB whose busiest CU gets
+// at most 5/4 of the work the busiest CU has with one tile per block.  Work of the busiest CU in (layer, tile) slots: rounds of blocks
+// over the resident CUs x layers of the fullest block x TB.  16 members of 256 tiles on 256 CUs: 1 x 16 x 1 = 1 x 8 x 2 = 1 x 4 x 4, so
+// TB = 4 (whole 256-byte runs of every weight row on one CU: 2.41 -> 2.01 us per layer); 4, 8 and 12 members likewise.  A member count
+// that grid.y = 4 does not divide leaves the blocks unequal: 7, 10 and 15 members (8 / 7, 12 / 10, 16 / 15 of the work) were still 12,
+// 10 and 13 % faster on TB = 4, six members (8 / 6) no faster than on TB = 2, five (8 / 5) and three (4 / 3, a quarter of the CUs idle)
+// SLOWER than on TB = 1, two members on TB = 4 leave half the CUs idle.  The 5/4 bound gives every measured member count the TB that
+// was fastest for it: 1 for 3; 2 for 2, 5 and 6; 4 for 4, 7, 8, 10, 12, 15 and 16.
+// The span placement was slower than the interleaved one under every TB and is never chosen.
+struct Decode3TilesWanted {
+    int tb;
+    bool span;
+};
+GL_HD int64_t decode3_group_busiest_cu(int tiles, int members, int64_t resident, int tb) {
+    const Decode3GroupGeometry geo = decode3_group_geometry(tiles, members, resident, tb, false);
+    if (geo.tb != tb) return -1;  // the shape does not admit this TB
+    const int64_t blocks = (int64_t)geo.grid_x * geo.grid_y, cus = resident > 0 ? resident : 1;
+    return (blocks + cus - 1) / cus * ((members + geo.grid_y - 1) / geo.grid_y) * tb;
+}
+inline Decode3TilesWanted decode3_group_tiles_default(int tiles, int members, int64_t resident) {
+    const int64_t one = decode3_group_busiest_cu(tiles, members, resident, 1);
+    for (int tb = 4; tb > 1; tb >>= 1) {
+        const int64_t c = decode3_group_busiest_cu(tiles, members, resident, tb);
+        if (c >= 0 && c * 4 <= one * 5) return Decode3TilesWanted{tb, false};
+    }
+    return Decode3TilesWanted{1, false};
+}
+
 // Waves per SIMD the compiler must keep resident for the grouped kernel (the second __launch_bounds__ argument of HIP).  One 1024-thread
 // block is 4 waves per SIMD = 128 VGPRs per lane (two blocks per CU, 64 VGPRs, spill: profiles/r07/capture_groups.log)
 #ifndef DECODE3_GROUP_WAVES_PER_SIMD

@@ -348,7 +348,16 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
  *   _form        host only: the rule behind it for `members` layers (1 .. 16) of reduction length K (a multiple of 256) whose x pointers
  *                all agree (same_x != 0) or not: 0 / 1 / 2 as above, -1 for an argument out of range
  *   _shared_x_lds_bytes  host only: dynamic LDS of a shared-x block, 64 KiB of partial rows + 2.25 K bytes of staged x; 0 when that is
- *                past the 160 KiB of a CU (K > 43520: such a K keeps form 1) or K is no positive multiple of 256 */
+ *                past the 160 KiB of a CU (K > 43520: such a K keeps form 1) or K is no positive multiple of 256
+ *   _geometry    host only, DEVELOPMENT / TEST: the tile-group geometry of a grouped launch of `members` layers of `tiles` tiles on a
+ *                device with `resident` CUs: out = {TB, grid.x, grid.y, placement}.  A block holds TB (1, 2 or 4) adjacent tiles x
+ *                ceil((members - y) / grid.y) layers, grid.x = tiles / TB, grid.y = the _grid_y rule for tiles / TB tile groups; its
+ *                (layer, tile) slots — slot s = layer s / TB, tile s % TB, at most 16 — are what _wave_split calls layers.  TB is the
+ *                largest one <= tb_want (1, 2, 4) with tiles % TB == 0 and ceil(members / grid.y) * TB <= 16; placement 0 interleaved,
+ *                1 span (span_want).  tb_want = 0: what a capture picks (GEMLITE_HIP_CAPTURE_GROUP_TILES=<TB>[s|i], read once, or the
+ *                default rule).  Returns 0, or -1 for an argument out of range
+ *   _tile_of     host only, DEVELOPMENT / TEST: the first tile of the tile group that block `block` (0 .. tiles / tb - 1) of a grouped
+ *                launch works on, a permutation of the groups under either placement (span = 0 / 1); -1 for an argument out of range */
 int gemlite_hip_capture_group_max(void);
 void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
@@ -357,6 +366,8 @@ void gemlite_hip_capture_group_wave_split(int32_t layers_in_block, int32_t wave,
 int gemlite_hip_capture_group_last_form(void);
 int gemlite_hip_capture_group_form(int32_t members, int32_t same_x, int64_t K);
 int64_t gemlite_hip_capture_group_shared_x_lds_bytes(int64_t K);
+int gemlite_hip_capture_group_geometry(int32_t tiles, int32_t members, int32_t resident, int32_t tb_want, int32_t span_want, int32_t out[4]);
+int gemlite_hip_capture_group_tile_of(int32_t tiles, int32_t tb, int32_t span, int32_t block);
 
 /* Bias in the launch (optional extension; gemlite_hip_forward_args and every entry point above are unchanged).  The M = 1 decode kernel
  * (gemv_w4_decode3_kernel, single and grouped) and the few-row kernels (gemm_w4_rows_kernel / gemm_w2_rows_kernel) have forms that add a
