@@ -63,7 +63,7 @@ const void* quantize_rows_kernel_fn(int format, int64_t K);
 const void* dequantize_words_kernel_fn(int nbits);
 const void* dequantize_rows_kernel_fn(int fmt);
 const void* dequantize_any_kernel_fn();
-// capture_group.hip: independent decode3 launches of one stream capture folded into one grouped launch
+// capture_group.hip: independent decode3 (or rows) launches of one stream capture folded into one grouped launch
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
 bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPlan& la, const gemlite_hip_forward_args& b, const LaunchPlan& lb);
@@ -1139,7 +1139,12 @@ static int launch_resolved(const gemlite_hip_forward_args* args, Resolved& r, in
             Rows5Args& d = r.lp.r5;
             void* dargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                              (void*)&d.nch_total, (void*)&d.modes, (void*)&d.M, (void*)&d.sxm2, (void*)&d.som, (void*)&r.lp.bias};  // (bias: the biased form only)
-            return launch(r.lp.fn, r.lp.grid, r.lp.block, dargs, r.lp.lds_bytes, st);
+            // the second family of capture_group.hip: the same two calls around the launch as above
+            const bool plain = tl_evt_start || tl_evt_stop;
+            if (!plain && capture_group_try_join(*args, r.lp, st, resident, dev)) return GEMLITE_OK;
+            const int rc = launch(r.lp.fn, r.lp.grid, r.lp.block, dargs, r.lp.lds_bytes, st);
+            if (!plain && rc == GEMLITE_OK) capture_group_note_launch(*args, r.lp, st);
+            return rc;
         }
         void* kargs[] = {(void*)&r.wn};
         return launch(r.lp.fn, r.lp.grid, r.lp.block, kargs, r.lp.lds_bytes, st);

@@ -1,4 +1,5 @@
-// capture_group.hip — host only: back-to-back INDEPENDENT M = 1 decode launches of one stream capture become one grouped launch.
+// capture_group.hip — host only: back-to-back INDEPENDENT launches of one stream capture become one grouped launch.  Two kernel families
+// group, each with its own kind: the M = 1 decode kernel (described first) and the few-row rows kernel (ROWS GROUPS, below).
 //
 // At 8.9 MB a gemv_w4_decode3_kernel launch is latency-bound: of ~4.75 us per layer in a replayed graph, ~1.7 us is the dependent-launch
 // boundary and ~1.6 us ramp, first-byte latency and tail, all paid again by the next launch.  Real decode graphs hold runs
@@ -32,6 +33,18 @@
 // join from members, tiles and resident blocks (decode3_group_tiles_default); GEMLITE_HIP_CAPTURE_GROUP_TILES=<TB>[s|i] (development, read
 // once) forces the TB asked for and the span ("s") or interleaved ("i", the default) placement for A/B runs — a TB that does not fit the
 // shape still falls back to the next smaller one.
+//
+// ROWS GROUPS (family 2).  A serving engine captures one graph per batch size; with two or more requests in a step every 4- / 2-bit layer runs
+// gemm_w4_rows_kernel / gemm_w2_rows_kernel (gemm_wn_rows.hip, LaunchPlan::arg_kind == 2), and q / k / v, gate / up and the experts of a step
+// pay the launch boundary each.  They group under the same look-back, independence rule, member limit and counters: a rows launch joins
+// the open rows group when same_launch() holds — the same kernel function (dtype, MT, SPG, NT, bits, biased or not), grid.x, block, LDS
+// bytes and the seven shared scalars sw4 / mstride2 / nch_total / modes / M / sxm2 / som, and ONE row block (grid.y == 1: the grouped
+// kernel has none).  The node becomes gemm_w4_rows[_bias]_group_kernel (gemm_wn_rows_group.hip), grid (tiles, members): block (tile, y)
+// computes member y's tile exactly as its own launch would; blocks go out x-fastest, so narrow layers spread their members over idle CUs
+// and full-width ones run their members in successive rounds without a launch boundary.  The dynamic-LDS cap of the grouped function is
+// raised once per device (ensure_lds) before the node is rewritten.  The families never mix: a launch of one family behind an open group
+// of the other fails same_launch(), is launched the plain way and opens its own group.  gemlite_hip_capture_group_last_form() == 3.
+// GEMLITE_HIP_CAPTURE_GROUP_ROWS=0 (read once) keeps only this family ungrouped (A/B runs in separate processes).
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -98,10 +111,24 @@ bool independent(const Footprint& a, const Footprint& b) {
 }
 
 // What a group shares: the kernel, its grid and the four scalars behind the five pointers.  (The timeline probe never groups.)
+// Rows launches (arg_kind 2): the kernel, grid.x with ONE row block, block, LDS bytes and the seven scalars behind the five pointers.
+// No shape, M or member count is kept out: every measured cell — 2, 4 and 16 members, 64 and 256 tiles, K = 4096 and 11008, M = 8 .. 64 —
+// was faster grouped by more than the run-to-run spread (profiles/r17/rows_groups.log §2: smallest gain 0.76 us per layer, spread 0.18).
 bool same_launch(const LaunchPlan& a, const LaunchPlan& b) {
+    if (a.arg_kind == 2 && b.arg_kind == 2)
+        return a.fn == b.fn && a.grid.x == b.grid.x && a.grid.y == 1 && b.grid.y == 1 && a.grid.z == 1 && b.grid.z == 1 &&
+               a.block.x == b.block.x && a.lds_bytes == b.lds_bytes && a.r5.sw4 == b.r5.sw4 && a.r5.mstride2 == b.r5.mstride2 &&
+               a.r5.nch_total == b.r5.nch_total && a.r5.modes == b.r5.modes && a.r5.M == b.r5.M && a.r5.sxm2 == b.r5.sxm2 &&
+               a.r5.som == b.r5.som;
     return a.arg_kind == 1 && b.arg_kind == 1 && a.fn == b.fn && a.grid.x == b.grid.x && a.grid.y == 1 && b.grid.y == 1 && a.grid.z == 1 &&
            b.grid.z == 1 && a.block.x == b.block.x && a.d3.sw4 == b.d3.sw4 && a.d3.mstride2 == b.d3.mstride2 &&
            a.d3.nch_total == b.d3.nch_total && a.d3.modes == b.d3.modes && !(a.d3.modes & 64u);
+}
+
+// The grouped form of a rows launch (the planner filled both in; `fn` is the biased form exactly when the launch carries a bias)
+const void* rows_group_fn_of(const LaunchPlan& lp) {
+    if (lp.arg_kind != 2) return nullptr;
+    return lp.bias ? (lp.fn == lp.fn_bias ? lp.fn_bias_group : nullptr) : (lp.fn == lp.bias_of ? lp.fn_group : nullptr);
 }
 
 const void* group_fn_of(const void* fn) {
@@ -142,6 +169,8 @@ struct Group {
     bool same_x = true;  // every member so far reads member 0's x
     Decode3GroupTable tab{};
     Decode3BiasGroupTable tabb{};  // the table of a biased group (lp.bias set) instead of `tab`
+    Rows5GroupTable rtab{};        // a rows group (lp.arg_kind == 2): its table,
+    Rows5BiasGroupTable rtabb{};   // and the table of a biased one
     Footprint fp[DECODE3_GMAX];
     int members = 0;
 };
@@ -173,6 +202,11 @@ int capture_group_limit() {
     return limit;
 }
 
+bool capture_group_rows_enabled() {
+    static const bool on = env_int("GEMLITE_HIP_CAPTURE_GROUP_ROWS", 1) != 0;
+    return on;
+}
+
 bool capture_group_shared_x_enabled() {
     static const bool on = env_int("GEMLITE_HIP_CAPTURE_GROUP_SHARED_X", 1) != 0;
     return on;
@@ -198,16 +232,19 @@ void capture_group_stats(uint64_t* seen, uint64_t* joined) {
 
 // The host-only rule: may launch B (args b, plan lb) run in the same grouped launch as A?
 bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPlan& la, const gemlite_hip_forward_args& b, const LaunchPlan& lb) {
-    return same_launch(la, lb) && group_fn_of(la.fn) != nullptr && independent(footprint(a, la), footprint(b, lb));
+    if (!same_launch(la, lb)) return false;
+    if (la.arg_kind == 2 ? rows_group_fn_of(la) == nullptr : group_fn_of(la.fn) == nullptr) return false;
+    return independent(footprint(a, la), footprint(b, lb));
 }
 
-// Called in front of every decode3 launch that carries no profile events.  true: the call was folded into the open group's node, nothing
+// Called in front of every decode3 and every rows launch that carries no profile events.  true: the call was folded into the open group's node, nothing
 // is left to launch.  false: launch as always, then call capture_group_note_launch().  resident: blocks of a one-block-per-CU kernel
 // the stream's device holds at once (its CU count).
 bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident, int dev) {
     Group& g = tl_group;
     g.capturing = false;
-    if (capture_group_limit() < 2 || (lp.d3.modes & 64u)) return false;
+    const bool rows = lp.arg_kind == 2;
+    if (capture_group_limit() < 2 || (rows ? !capture_group_rows_enabled() : (lp.d3.modes & 64u) != 0)) return false;
     unsigned long long id = 0;
     hipGraph_t graph = nullptr;
     hipGraphNode_t dep = nullptr;
@@ -223,6 +260,37 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     for (int i = 0; i < g.members; ++i)
         if (!independent(g.fp[i], fb)) return false;
     const bool biased = g.lp.bias != nullptr;  // (lp.bias too: same_launch() compared the kernel functions)
+    if (rows) {
+        // member g.members of the node: its pointers behind the scalars of member 0, grid.y one more.  The cap on dynamic LDS first (a
+        // rows block takes 146 KiB): once per grouped function and device
+        if (ensure_lds(g.fn_group, g.lp.lds_bytes, dev) != GEMLITE_OK) {
+            g.open = false;
+            return false;
+        }
+        Rows5Member& rm = biased ? g.rtabb.m[g.members - 1] : g.rtab.m[g.members - 1];
+        if (biased) g.rtabb.bias[g.members] = lp.bias;
+        rm.w = lp.r5.w; rm.x = lp.r5.x; rm.s = lp.r5.s; rm.z = lp.r5.z; rm.out = lp.r5.out;
+        Rows5Args& r = g.lp.r5;
+        void* rargs[] = {(void*)&r.w, (void*)&r.x, (void*)&r.s, (void*)&r.z, (void*)&r.out, (void*)&r.sw4, (void*)&r.mstride2, (void*)&r.nch_total,
+                         (void*)&r.modes, (void*)&r.M, (void*)&r.sxm2, (void*)&r.som, biased ? (void*)&g.rtabb : (void*)&g.rtab};
+        hipKernelNodeParams rp;
+        memset(&rp, 0, sizeof(rp));
+        rp.func = (void*)g.fn_group;
+        rp.gridDim = dim3(g.lp.grid.x, (unsigned)(g.members + 1), 1);
+        rp.blockDim = g.lp.block;
+        rp.sharedMemBytes = (unsigned)g.lp.lds_bytes;
+        rp.kernelParams = rargs;
+        rp.extra = nullptr;
+        if (hipGraphKernelNodeSetParams(g.node, &rp) != hipSuccess) {  // the node keeps what it had; this call runs on its own
+            (void)hipGetLastError();
+            g.open = false;
+            return false;
+        }
+        g.fp[g.members++] = fb;
+        tl_last_form = 3;
+        g_joined.fetch_add(1, std::memory_order_relaxed);
+        return true;
+    }
     Decode3Member& m = biased ? g.tabb.m[g.members - 1] : g.tab.m[g.members - 1];
     if (biased) g.tabb.bias[g.members] = lp.bias;
     m.w = lp.d3.w; m.x = lp.d3.x; m.s = lp.d3.s; m.z = lp.d3.z; m.out = lp.d3.out;
@@ -260,15 +328,15 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     return true;
 }
 
-// After a plain decode3 launch that try_join() declined under capture: the node it became is the stream's single dependency now,
+// After a plain decode3 / rows launch that try_join() declined under capture: the node it became is the stream's single dependency now,
 // and opens a new group of one (which keeps the single-layer kernel until somebody joins).
 void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st) {
     Group& g = tl_group;
     if (!g.capturing) return;
     g.capturing = false;
     g.open = false;
-    const void* fn_group = group_fn_of(lp.fn);
-    if (!fn_group || lp.arg_kind != 1 || lp.grid.y != 1 || lp.grid.z != 1) return;
+    const void* fn_group = lp.arg_kind == 2 ? rows_group_fn_of(lp) : group_fn_of(lp.fn);
+    if (!fn_group || (lp.arg_kind != 1 && lp.arg_kind != 2) || lp.grid.y != 1 || lp.grid.z != 1) return;
     unsigned long long id = 0;
     hipGraph_t graph = nullptr;
     hipGraphNode_t dep = nullptr;
@@ -281,12 +349,15 @@ void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPl
     g.node = dep;
     g.lp = lp;
     g.fn_group = fn_group;
-    g.fn_group_sx = group_sx_fn_of(lp.fn);
+    g.fn_group_sx = lp.arg_kind == 1 ? group_sx_fn_of(lp.fn) : nullptr;
     g.same_x = true;
     tl_last_form = 0;  // (a group of one: no grouped node yet)
     memset(&g.tab, 0, sizeof(g.tab));
     memset(&g.tabb, 0, sizeof(g.tabb));
     g.tabb.bias[0] = lp.bias;
+    memset(&g.rtab, 0, sizeof(g.rtab));
+    memset(&g.rtabb, 0, sizeof(g.rtabb));
+    g.rtabb.bias[0] = lp.bias;
     g.fp[0] = footprint(a, lp);
     g.members = 1;
     g.open = true;

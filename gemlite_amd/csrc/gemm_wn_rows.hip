@@ -32,47 +32,9 @@
 //   * the 8 partial tiles meet in LDS (the wave's own buffer again), one barrier, packed 4-byte stores.
 // All memory requests are inline asm retired by hand-counted waits (gl_async.h has the reasoning; scripts/isa_asmloads.py audits the
 // generated code).  Scalar kernel arguments, the first 14 dwords preloaded into SGPRs (-amdgpu-kernarg-preload-count, see gemv_decode.hip).
-#include <type_traits>
-
-#include "gl_common.h"
-#include "gl_async.h"
+#include "gl_rows5.h"
 
 namespace gl {
-
-namespace rows5 {
-
-template <typename Tag>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<half_tag>(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<bf16_tag>(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8_t, a), __builtin_bit_cast(b8_t, b), c, 0, 0, 0);
-}
-
-// modes: bits 0..3 W_group_mode | 4 zero_is_scalar | 5 pair the half-line tiles on one XCD | 7 channel scales (sp) in the epilogue | 8..15 log2(group)
-constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_POST32 = 64u, M_POST = 128u;  // (M_POST32: the epilogue's channel scales are fp32 — BitNet A16W158)
-constexpr int NW = 8;                              // waves per block
-constexpr int WSLOT_I1 = 272;                      // dword offset of the odd packed rows inside a wave's weight slot (16 dwords of padding: see below)
-constexpr int WSLOT_BYTES = 2304;                  // >= (WSLOT_I1 + 256) * 4
-constexpr int XBUF = 8192;                         // one x piece: 16 MT rows x 256 / 128 / 64 k
-constexpr int WAVE_LDS = 2 * XBUF + WSLOT_BYTES;   // per wave: two x buffers + the weight slot
-
-__device__ __forceinline__ void gld128_nt(u32x4& dst, const char* base, uint32_t voff) {
-    asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(dst) : "v"(voff), "s"(base) : "memory");
-}
-__device__ __forceinline__ void gld16(uint32_t& dst, const char* base, uint32_t voff) {
-    asm volatile("global_load_ushort %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void tie4(u32x4& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void tie1(uint32_t& v) { asm volatile("" : "+v"(v)); }
-
-}  // namespace rows5
 
 // MT = row tiles of 16 (M <= 16 MT); SPG = 32-k steps per quantisation group (4: groups of >= 128, 2: 64, 1: 32); NT = 16-column tiles
 // per block (2: layers with 4096 < N <= 8192 — N / 32 blocks stay resident in ONE round, and an x piece read from LDS feeds both tiles)
@@ -95,6 +57,8 @@ __device__ __forceinline__ void tie1(uint32_t& v) { asm volatile("" : "+v"(v)); 
 // ---------------------------------------------------------------------------------------------------------------------
 // host-side planning.  tuning[0] = 9 forces this kernel (any M), GEMLITE_TF_NO_ROWS_KERNEL = never (the round-4 choice, A/B runs)
 // ---------------------------------------------------------------------------------------------------------------------
+const void* gemm_wn_rows_group_fn(int tag, int mt, int spg, int nt, int bits, bool biased);  // gemm_wn_rows_group.hip: the grouped forms
+
 typedef void (*rows5_fn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, int, uint32_t, uint32_t);
 
 template <typename Tag, int MT>
@@ -236,6 +200,8 @@ bool plan_gemm_wn_rows(const gemlite_hip_forward_args& a, WnParams& p, LaunchPla
     lp.fn = (const void*)fn;
     lp.bias_of = lp.fn;
     lp.fn_bias = (const void*)(f16 ? rows5_bias_pick<half_tag>(mt, spg, nt, bits) : rows5_bias_pick<bf16_tag>(mt, spg, nt, bits));
+    lp.fn_group = gemm_wn_rows_group_fn(f16 ? 0 : 1, mt, spg, nt, bits, false);
+    lp.fn_bias_group = gemm_wn_rows_group_fn(f16 ? 0 : 1, mt, spg, nt, bits, true);
     static const char* names[4] = {"gemm_w4_rows_kernel<16x16>", "gemm_w4_rows_kernel<32x16>", "gemm_w4_rows_kernel<48x16>", "gemm_w4_rows_kernel<64x16>"};
     static const char* names2[4] = {"gemm_w4_rows_kernel<16x32>", "gemm_w4_rows_kernel<32x32>", "gemm_w4_rows_kernel<48x32>", "gemm_w4_rows_kernel<64x32>"};
     static const char* names_w2[4] = {"gemm_w2_rows_kernel<16x16>", "gemm_w2_rows_kernel<32x16>", "gemm_w2_rows_kernel<48x16>", "gemm_w2_rows_kernel<64x16>"};

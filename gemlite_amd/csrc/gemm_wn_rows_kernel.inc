@@ -1,7 +1,21 @@
 // gemm_wn_rows_kernel.inc — the body of gemm_w4_rows_kernel (gemm_wn_rows.hip has the description), included once per form:
 //   GL_ROWS5_KERNEL = gemm_w4_rows_kernel,      GL_ROWS5_BIAS = 0: the kernel as it always was, token for token
 //   GL_ROWS5_KERNEL = gemm_w4_rows_bias_kernel, GL_ROWS5_BIAS = 1: one more argument (behind the preloaded dwords) and the bias add in the epilogue
-#if GL_ROWS5_BIAS
+//   GL_ROWS5_GROUP = 1 (gemm_wn_rows_group.hip: gemm_w4_rows_group_kernel / gemm_w4_rows_bias_group_kernel): the GROUPED forms — grid (tiles,
+//       members), block (tile, y) computes member y's tile.  Member 0's pointers are the preloaded dwords, members 1 .. come from the by-value
+//       table behind the scalars (gl_common.h: Rows5GroupTable / Rows5BiasGroupTable), selected by blockIdx.y — uniform, so scalar loads, once
+//       per wave and in front of the first request.  Everything behind the selection is the single-layer body; the row blocks along grid.y
+//       are compiled out (launches with row blocks never group).  GL_ROWS5_GROUP undefined or 0: the two forms above, token for token.
+#if defined(GL_ROWS5_GROUP) && GL_ROWS5_GROUP
+#define GL_ROWS5_GROUPED 1
+#else
+#define GL_ROWS5_GROUPED 0
+#endif
+#if GL_ROWS5_GROUPED && GL_ROWS5_BIAS
+#define GL_ROWS5_BIAS_PARAM , const Rows5BiasGroupTable tab
+#elif GL_ROWS5_GROUPED
+#define GL_ROWS5_BIAS_PARAM , const Rows5GroupTable tab
+#elif GL_ROWS5_BIAS
 #define GL_ROWS5_BIAS_PARAM , const uint16_t* bias
 #else
 #define GL_ROWS5_BIAS_PARAM
@@ -38,6 +52,17 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
         const int xcd = tile & 7, idx = tile >> 3;
         tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
     }
+#if GL_ROWS5_GROUPED
+    // this block's member: the preloaded scalars (member 0) or the by-value table — blockIdx.y is uniform, so these are scalar loads
+    const int member = (int)blockIdx.y;
+    if (member > 0) {
+        const Rows5Member& mb = tab.m[member - 1];
+        wb = mb.w; xb = mb.x; sp = mb.s; zp = mb.z; out = mb.out;
+    }
+#if GL_ROWS5_BIAS
+    const uint16_t* bias = tab.bias[member];
+#endif
+#else
     // more than 16 MT rows (shapes no tile kernel takes — groups of 32, N % 64 != 0 — at prefill sizes): blocks along grid.y, 16 MT rows each
     if (gridDim.y > 1) {
         const uint32_t m0 = blockIdx.y * (uint32_t)(16 * MT);
@@ -45,6 +70,7 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
         out += (size_t)m0 * som;
         M -= (int)m0;
     }
+#endif
     if (M > 16 * MT) M = 16 * MT;
     const int c = lane & 3, g = lane >> 2;    // role in the weight request
     const int j = lane & 15, kb = lane >> 4;  // role in the MFMA: column j / row j of a tile, 8-k block kb of the 32-k step
@@ -273,3 +299,4 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
 }
 
 #undef GL_ROWS5_BIAS_PARAM
+#undef GL_ROWS5_GROUPED

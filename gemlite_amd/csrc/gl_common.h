@@ -753,6 +753,22 @@ struct Rows5Args {
     uint32_t sxm2, som;
 };
 
+// gemm_w4_rows_group_kernel / gemm_w4_rows_bias_group_kernel (gemm_wn_rows_group.hip): the pointers of members 1 .. ROWS5_GMAX - 1 of a
+// grouped launch, by value behind the scalars above (member 0's, shared by the group but for the five pointers); grid.y = members.  A
+// biased group holds one bias pointer per member, member 0's included (the layout of Decode3GroupTable / Decode3BiasGroupTable).
+constexpr int ROWS5_GMAX = DECODE3_GMAX;
+struct Rows5Member {
+    const char *w, *x, *s, *z;
+    uint16_t* out;
+};
+struct Rows5GroupTable {
+    Rows5Member m[ROWS5_GMAX - 1];
+};
+struct Rows5BiasGroupTable {
+    Rows5Member m[ROWS5_GMAX - 1];
+    const uint16_t* bias[ROWS5_GMAX];
+};
+
 struct LaunchPlan {
     const void* fn;
     const char* name;
@@ -768,6 +784,9 @@ struct LaunchPlan {
     const void* fn_bias = nullptr;
     const void* bias_of = nullptr;
     const uint16_t* bias = nullptr;
+    // the grouped forms of `bias_of` and of `fn_bias` (rows kernels only: capture_group.hip rewrites a capture's node to one of them)
+    const void* fn_group = nullptr;
+    const void* fn_bias_group = nullptr;
 };
 
 }  // namespace gl

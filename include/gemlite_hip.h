@@ -324,15 +324,20 @@ void gemlite_hip_set_profile_events(void* start_event, void* stop_event);
  * to every kernel duration it quotes (on MI355X an empty kernel already reads ~4 us). */
 int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
 
-/* Capture-time grouping of the M = 1 decode kernel.  While `stream` is being captured into a graph, a gemlite_hip_forward call that runs
+/* Capture-time grouping of the M = 1 decode kernel and of the few-row (2 .. 64 rows) 4- / 2-bit rows kernel.  While `stream` is being captured into a graph, a gemlite_hip_forward call that runs
  * gemv_w4_decode3_kernel and is INDEPENDENT of the decode launches captured directly before it (nothing else captured on the stream in
  * between; same kernel, shape, strides and modes; its output overlaps none of their inputs or outputs, their outputs none of its inputs)
  * adds no node: the node before it becomes one grouped launch of up to gemlite_hip_capture_group_max layers.  Every layer's result is
  * bit-identical to its own launch, the graph stays linear, and a dependent chain is captured node for node as before.  Eager launches,
  * launches with profile events and GEMLITE_TF_TIMELINE launches never group.  The environment variable GEMLITE_HIP_NO_CAPTURE_GROUPS=1
  * (read once per process) turns grouping off.
+ * The SECOND family: a call that runs gemm_w4_rows_kernel / gemm_w2_rows_kernel (2 .. 64 rows in one row block) joins the rows launches
+ * captured directly before it under the same rule — same kernel form, tiles, strides, modes and M, the same independence — and the node
+ * becomes gemm_w4_rows_group_kernel, grid (tiles, members): block (tile, y) computes member y's tile as its own launch would, bit for
+ * bit.  The families never mix: a launch of one family behind an open group of the other closes it and opens its own.  Launches with
+ * row blocks (grid.y > 1) never group.  GEMLITE_HIP_CAPTURE_GROUP_ROWS=0 (read once per process) keeps only this family ungrouped.
  *   _max         layers per grouped launch (1 = grouping is off)
- *   _stats       process-wide counts: decode launches seen under capture, and how many of them joined a node instead of adding one
+ *   _stats       process-wide counts: decode and rows launches seen under capture, and how many of them joined a node instead of adding one
  *   _compatible  host only, nothing is dereferenced: 1 if launch `b` captured directly behind launch `a` would join it, else 0
  *   _grid_y      host only: the grid.y rule for a grouped launch of `members` layers of `tiles` 16-column tiles (N / 16), answered for
  *                a full 256-CU part: clamp(256 / tiles, 1, members) (a launch uses its own device's CU count in place of 256); block (tile, y) holds the layers y, y + grid.y, ...  0 for a non-positive argument
@@ -342,7 +347,8 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
  *                16 / layers_in_block waves per layer.  {-1, 0, 0} for an argument out of range
  *   _last_form   host only: the form of the grouped node the calling thread rewrote last: 0 none (no join since the thread's last group
  *                opened), 1 per-wave x (every wave loads the x of its own layer), 2 shared x (three or more members that all read the same x pointer: a
- *                block stages x in LDS once; GEMLITE_HIP_CAPTURE_GROUP_SHARED_X=0, read once, keeps every group on form 1)
+ *                block stages x in LDS once; GEMLITE_HIP_CAPTURE_GROUP_SHARED_X=0, read once, keeps every group on form 1), 3 a group of
+ *                the rows kernel (grid (tiles, members))
  *   _form, _shared_x_lds_bytes   DEVELOPMENT / TEST exports (tests/test_decode_group_shared_x_cpu.py restates them in Python); not part of
  *                what a caller needs, and free to change with the kernel:
  *   _form        host only: the rule behind it for `members` layers (1 .. 16) of reduction length K (a multiple of 256) whose x pointers

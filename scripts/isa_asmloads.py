@@ -18,7 +18,8 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_loops as L
 
-FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", "Decode3GroupTable", "Decode3BiasGroupTable")
+FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", "Decode3GroupTable", "Decode3BiasGroupTable",
+            "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel")
 # gemv_wn_kernel (round 6: gvw::ring2_run): the prologue requests up to two chunks behind uniform branches and the last one to three chunks run in
 # straight-line code BEHIND the loop — replayed in address order (no branch is followed), prologue and tail included, every conditional request
 # issued and every run of alternative waits taken at its weakest member
@@ -28,7 +29,10 @@ FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_r
 # wrap-around trips; the OTHER copy is replayed in address order only — first requests, ONE trip of its loop, its tail — so a touch that only a second
 # trip of that copy's loop would show is not seen.  (Both copies are the same source with one `if constexpr` apart.)
 LINEAR_WITH_TAIL = ("gemv_wn_kernel", "Decode3GroupTable", "Decode3BiasGroupTable")
-ALTERNATIVE_WAITS = ("gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", "Decode3GroupTable", "Decode3BiasGroupTable")
+# gemm_w4_rows_group_kernel / gemm_w4_rows_bias_group_kernel: the grouped forms of gemm_w4_rows_kernel (gemm_wn_rows_group.hip) — the same body
+# behind a scalar selection of the member's pointers, replayed like the single-layer forms
+ALTERNATIVE_WAITS = ("gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", "Decode3GroupTable", "Decode3BiasGroupTable",
+                     "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel")
 VREG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 
 
