@@ -70,6 +70,8 @@ bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPla
 bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st, int resident, int dev);
 bool capture_group_shared_x_enabled();
 int capture_group_last_form();
+int capture_group_last_lines();
+int capture_group_lines_wanted(int tiles, int members, int resident, int tb);
 Decode3TilesWanted capture_group_tiles_wanted(int tiles, int members, int resident);
 int ensure_lds(const void* fn, size_t lds, int dev);
 void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPlan& lp, hipStream_t st);
@@ -1025,6 +1027,15 @@ int gemlite_hip_capture_group_geometry(int32_t tiles, int32_t members, int32_t r
     const Decode3GroupGeometry geo = decode3_group_geometry(tiles, members, resident, want.tb, want.span);
     out[0] = geo.tb; out[1] = geo.grid_x; out[2] = geo.grid_y; out[3] = geo.span ? 1 : 0;
     return 0;
+}
+
+int gemlite_hip_capture_group_last_lines(void) { return capture_group_last_lines(); }
+
+int gemlite_hip_capture_group_lines(int32_t tiles, int32_t members, int32_t resident, int32_t tb, int32_t h_want) {
+    if (tiles < 1 || members < 1 || members > DECODE3_GMAX || resident < 1 || (tb != 1 && tb != 2 && tb != 4) || tiles % tb || h_want < 0 ||
+        h_want > 4 || h_want == 3)
+        return -1;
+    return decode3_group_lines(tb, h_want == 0 ? capture_group_lines_wanted(tiles, members, resident, tb) : h_want);
 }
 
 int gemlite_hip_capture_group_tile_of(int32_t tiles, int32_t tb, int32_t span, int32_t block) {

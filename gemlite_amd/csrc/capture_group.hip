@@ -34,6 +34,11 @@
 // once) forces the TB asked for and the span ("s") or interleaved ("i", the default) placement for A/B runs — a TB that does not fit the
 // shape still falls back to the next smaller one.
 //
+// LINES (gl_common.h: decode3_group_lines): a wave of a grouped block may work on H = 1, 2 or 4 adjacent tiles of its block's tile group at once,
+// in H passes over each virtual wave, so that one request instruction asks for whole 128-byte (H = 2) or 256-byte (H = 4) runs of 8 or 4 weight
+// rows.  H divides TB; it is chosen at every join (decode3_group_lines_default), and every H has kernel functions of its own.
+// GEMLITE_HIP_CAPTURE_GROUP_LINES=1|2|4 (development, read once) forces the H asked for; one that TB does not admit falls back 4 -> 2 -> 1.
+//
 // ROWS GROUPS (family 2).  A serving engine captures one graph per batch size; with two or more requests in a step every 4- / 2-bit layer runs
 // gemm_w4_rows_kernel / gemm_w2_rows_kernel (gemm_wn_rows.hip, LaunchPlan::arg_kind == 2), and q / k / v, gate / up and the experts of a step
 // pay the launch boundary each.  They group under the same look-back, independence rule, member limit and counters: a rows launch joins
@@ -54,10 +59,10 @@
 namespace gl {
 
 const void* gemv_w4_decode3_fn(int tag, bool nt);        // gemv_decode.hip
-const void* gemv_w4_decode3_group_fn(int tag);           // gemv_decode.hip: default-policy weight loads whatever the members' launches use
+const void* gemv_w4_decode3_group_fn(int tag, int h);       // gemv_decode.hip: default-policy weight loads whatever the members' launches use
 const void* gemv_w4_decode3_bias_fn(int tag, bool nt);        // the forms that add a bias in the epilogue: a group holds one kind only
-const void* gemv_w4_decode3_bias_group_fn(int tag);            // (the kernel functions differ, so same_launch() keeps them apart)
-const void* gemv_w4_decode3_group_sx_fn(int tag, bool biased);  // gemv_decode.hip: the shared-x grouped forms
+const void* gemv_w4_decode3_bias_group_fn(int tag, int h);       // (the kernel functions differ, so same_launch() keeps them apart)
+const void* gemv_w4_decode3_group_sx_fn(int tag, bool biased, int h);  // gemv_decode.hip: the shared-x grouped forms (h: tiles per wave)
 int ensure_lds(const void* fn, size_t lds, int dev);            // api.hip
 
 namespace {
@@ -131,21 +136,21 @@ const void* rows_group_fn_of(const LaunchPlan& lp) {
     return lp.bias ? (lp.fn == lp.fn_bias ? lp.fn_bias_group : nullptr) : (lp.fn == lp.bias_of ? lp.fn_group : nullptr);
 }
 
-const void* group_fn_of(const void* fn) {
+const void* group_fn_of(const void* fn, int h = 1) {
     for (int tag = 0; tag < 2; ++tag)
         for (int nt = 0; nt < 2; ++nt)
-            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_fn(tag);
+            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_fn(tag, h);
     for (int tag = 0; tag < 2; ++tag)
         for (int nt = 0; nt < 2; ++nt)
-            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_bias_group_fn(tag);
+            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_bias_group_fn(tag, h);
     return nullptr;
 }
 
-const void* group_sx_fn_of(const void* fn) {
+const void* group_sx_fn_of(const void* fn, int h = 1) {
     for (int tag = 0; tag < 2; ++tag)
         for (int nt = 0; nt < 2; ++nt) {
-            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_sx_fn(tag, false);
-            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_group_sx_fn(tag, true);
+            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_sx_fn(tag, false, h);
+            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_group_sx_fn(tag, true, h);
         }
     return nullptr;
 }
@@ -176,6 +181,7 @@ struct Group {
 };
 thread_local Group tl_group;
 thread_local int tl_last_form = 0;  // of the last group node this thread rewrote: decode3_group_form()
+thread_local int tl_last_lines = 0;  // and its H (0: no grouped decode node yet)
 
 bool capture_state(hipStream_t st, unsigned long long* id, hipGraph_t* graph, hipGraphNode_t* only_dep) {
     hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
@@ -223,7 +229,17 @@ Decode3TilesWanted capture_group_tiles_wanted(int tiles, int members, int reside
     return forced.tb ? forced : decode3_group_tiles_default(tiles, members, resident);
 }
 
+// The H try_join() asks decode3_group_lines() for: the forced one of GEMLITE_HIP_CAPTURE_GROUP_LINES, or the rule of gl_common.h
+int capture_group_lines_wanted(int tiles, int members, int resident, int tb) {
+    static const int forced = [] {
+        const int h = env_int("GEMLITE_HIP_CAPTURE_GROUP_LINES", 0);
+        return h >= 4 ? 4 : (h >= 2 ? 2 : (h == 1 ? 1 : 0));
+    }();
+    return forced ? forced : decode3_group_lines_default(tiles, members, resident, tb);
+}
+
 int capture_group_last_form() { return tl_last_form; }
+int capture_group_last_lines() { return tl_last_lines; }
 
 void capture_group_stats(uint64_t* seen, uint64_t* joined) {
     if (seen) *seen = g_seen.load(std::memory_order_relaxed);
@@ -288,6 +304,7 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
         }
         g.fp[g.members++] = fb;
         tl_last_form = 3;
+        tl_last_lines = 0;
         g_joined.fetch_add(1, std::memory_order_relaxed);
         return true;
     }
@@ -299,7 +316,11 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     const int members = g.members + 1, tiles = (int)g.lp.grid.x;
     const Decode3TilesWanted want = capture_group_tiles_wanted(tiles, members, resident);
     const Decode3GroupGeometry geo = decode3_group_geometry(tiles, members, resident, want.tb, want.span);
+    const int lines = decode3_group_lines(geo.tb, capture_group_lines_wanted(tiles, members, resident, geo.tb));
     uint32_t modes = decode3_group_modes(d.modes, members, geo.grid_y, geo.tb, geo.span);
+    // (every H has kernel functions of its own; g.fn_group / g.fn_group_sx are those of H = 1 and say which forms exist)
+    const void* fn_g = group_fn_of(g.lp.fn, lines);
+    const void* fn_sx = g.fn_group_sx ? group_sx_fn_of(g.lp.fn, lines) : nullptr;
     // (the shared-x tables have the layout of the other two: the same objects are passed)
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                      (void*)&d.nch_total, (void*)&modes, biased ? (void*)&g.tabb : (void*)&g.tab};
@@ -307,10 +328,10 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     int form = decode3_group_form(members, same_x, d.nch_total, capture_group_shared_x_enabled() && g.fn_group_sx != nullptr);
     const size_t lds = form == 2 ? (size_t)decode3_shared_x_lds_bytes(d.nch_total) : 0;
     // (the cap is raised once per kernel and device, to the form's maximum: the size of a launch depends on its K)
-    if (form == 2 && ensure_lds(g.fn_group_sx, (size_t)DECODE3_SHARED_X_MAX_LDS, dev) != GEMLITE_OK) form = 1;
+    if (form == 2 && ensure_lds(fn_sx, (size_t)DECODE3_SHARED_X_MAX_LDS, dev) != GEMLITE_OK) form = 1;
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
-    np.func = (void*)(form == 2 ? g.fn_group_sx : g.fn_group);
+    np.func = (void*)(form == 2 ? fn_sx : fn_g);
     np.gridDim = dim3((unsigned)geo.grid_x, (unsigned)geo.grid_y, 1);
     np.blockDim = g.lp.block;
     np.sharedMemBytes = form == 2 ? (unsigned)lds : 0;
@@ -324,6 +345,7 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     g.fp[g.members++] = fb;
     g.same_x = same_x;
     tl_last_form = form;
+    tl_last_lines = lines;
     g_joined.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
@@ -352,6 +374,7 @@ void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPl
     g.fn_group_sx = lp.arg_kind == 1 ? group_sx_fn_of(lp.fn) : nullptr;
     g.same_x = true;
     tl_last_form = 0;  // (a group of one: no grouped node yet)
+    tl_last_lines = 0;
     memset(&g.tab, 0, sizeof(g.tab));
     memset(&g.tabb, 0, sizeof(g.tabb));
     g.tabb.bias[0] = lp.bias;

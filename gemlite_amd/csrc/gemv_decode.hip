@@ -15,6 +15,11 @@
 //   * grid size / tile pairing come in through the arguments: no implicit-argument loads at all.
 // 16 waves x 64 lanes, lane (g = lane >> 2, c = lane & 3) owns columns 4c .. 4c + 3 of a 16-column tile and packed rows
 // chunk * 512 + wave * 32 + 2 g + {0, 1}.
+// The grouped forms (round 18, LINES): a wave may work on H = 2 or 4 adjacent tiles at once — its lanes are H sub-waves of 64 / H lanes,
+// sub-wave h on tile t0 + h, lane l' of a sub-wave is (c = l' & 3, gl = l' >> 2) — and takes H PASSES over each virtual wave, in pass p the
+// row pair g = p * 16 / H + gl.  One request instruction then asks for 8 rows x 128 contiguous bytes (H = 2) or 4 rows x 256 (H = 4)
+// where it asked for 16 rows x 64: every 128-byte line of the weights is requested once, by one instruction, and nothing depends on two
+// waves staying in step.  The block's slots / H WAVE-SLOTS (a layer x a run of H tiles) are what decode3_wave_split() hands to the waves.
 #include <type_traits>
 
 #include "gl_common.h"
@@ -71,8 +76,17 @@ constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
 // 2 u, 2 u + 1), with the same instructions in the same order, and writes 36 bytes to LDS; an item is then four requests and three LDS
 // reads.  The x loads go out first, the wave's first two items behind them, and the counted wait in front of the one extra barrier
 // covers the x loads only: the weight requests stay in flight across it.
-template <typename Tail>
+// Tail = Decode3Lines<one of the four group tables, HL>: the same grouped form with H = 1 << HL tiles per wave (LINES, gl_common.h) — a
+// compile-time constant, so the H = 1 forms are the code they were and the shifts of the others fold (profiles/r18/decode_group_lines.log §1).
+template <typename T>
+__device__ __forceinline__ const T& decode3_table(const T& t) { return t; }
+template <typename T, int HL>
+__device__ __forceinline__ const T& decode3_table(const Decode3Lines<T, HL>& w) { return w.t; }
+
+template <typename TailArg>
 struct Decode3TailKind {
+    using Tail = typename Decode3LinesOf<TailArg>::table;
+    static constexpr int hl = Decode3LinesOf<TailArg>::hl;
     static constexpr bool shared_x = std::is_same<Tail, Decode3GroupTableSX>::value || std::is_same<Tail, Decode3BiasGroupTableSX>::value;
     static constexpr bool grouped = std::is_same<Tail, Decode3GroupTable>::value || std::is_same<Tail, Decode3BiasGroupTable>::value || shared_x;
     static constexpr bool biased = std::is_same<Tail, Decode3BiasTail>::value || std::is_same<Tail, Decode3BiasGroupTable>::value ||
@@ -99,17 +113,19 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
     int tile = blockIdx.x;
     // grouped: the block's tile group and this wave's slot = (block-local layer, tile of the group); gl_common.h has the geometry
     [[maybe_unused]] int g_members = 0, g_Y = 1, g_slots = 1, g_tbl = 0, g_tile0 = 0;
+    [[maybe_unused]] constexpr int g_hl = Decode3TailKind<Tail>::hl;
     [[maybe_unused]] Decode3WaveSplit g_split{0, 0, 16};
     if constexpr (GROUPED) {
         g_members = (int)((modes >> 16) & DECODE3_M_MEMBERS);
         g_Y = (int)(modes >> 24);
         g_tbl = (int)((modes >> DECODE3_M_TB_SHIFT) & 3u);
         g_slots = ((g_members - (int)blockIdx.y + g_Y - 1) / g_Y) << g_tbl;
-        g_split = decode3_wave_split(g_slots, wave);
+        // lines: H = 1 << g_hl tiles per wave; the block's slots / H wave-slots are what the waves share, sub-wave h of the lanes takes tile run * H + h
+        g_split = decode3_wave_split(g_slots >> g_hl, wave);
         // (the span placement alone needs the grid's width: one scalar load of the dispatch's block count, in front of the first request)
         const bool span = (modes & DECODE3_M_SPAN) != 0u;
         g_tile0 = decode3_group_first_tile(tile, span ? (int)gridDim.x : 0, 1 << g_tbl, span, (modes & M_PAIR) != 0u);
-        tile = g_tile0 + ((g_split.layer < 0 ? 0 : g_split.layer) & ((1 << g_tbl) - 1));
+        tile = g_tile0 + ((((g_split.layer < 0 ? 0 : g_split.layer) << g_hl) & ((1 << g_tbl) - 1)) + (lane >> (6 - g_hl)));
     } else if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
         const int xcd = tile & 7, idx = tile >> 3;
         tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
@@ -295,29 +311,43 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         // writes zeros: K < 4096); after the barrier waves 0 .. LB - 1 each run the single-layer epilogue on one layer's region.
         // With tile groups (TB = 1 << g_tbl tiles per block) the block's LB * TB slots stand where the layers stand in this description:
         // slot s is layer s / TB on tile s % TB of the block's group, with its own waves, virtual waves and 4 KB of LDS.
+        // With lines (H = 1 << hl tiles per wave, a compile-time constant) the waves share the block's slots / H wave-slots instead; a
+        // wave's items are (virtual wave, pass, chunk) ascending, H times as many on a 1 / H share of the waves, and sub-wave h of the
+        // lanes fills slot + h.  Per lane an item is the same compute(); `tot` of a (virtual wave, pass) adds its chunks in ascending
+        // order; the four row pairs 4 r .. 4 r + 3 still meet in one 16-lane DPP row (r = p * 4 / H + the row inside the sub-wave) and
+        // land in partial row v * 4 + r of the slot's region: bit-exact under every H.  What depended on g depends on the pass through
+        // SCALAR adds to the uniform bases (weights, x, metadata row) and one constant inside the shared-x LDS offsets.
         const int Y = g_Y, y = (int)blockIdx.y, slots = g_slots;
         const Decode3WaveSplit split = g_split;
-        const int slot = split.layer < 0 ? 0 : split.layer, li = slot >> g_tbl, v0 = split.v0, v1 = split.v1;
+        // (slot: the wave's first of H = 1 << hl; lq: the lane inside its sub-wave, gl its row pair of a pass)
+        constexpr int hl = g_hl, H = 1 << hl;
+        const int lq = lane & ((64 >> hl) - 1), gl = lq >> 2;
+        const int slot = (split.layer < 0 ? 0 : split.layer) << hl, li = slot >> g_tbl, v0 = split.v0, v1 = split.v1;
         // this wave's layer: the preloaded scalars (layer 0) or the by-value table, scalar loads either way, once per wave
         const int L = y + li * Y;
         const char *w_ = wb, *x_ = xb, *s_ = sp, *z_ = zp;
         if (L > 0) {
-            const Decode3Member& m = counters.m[L - 1];
+            const Decode3Member& m = decode3_table(counters).m[L - 1];
             w_ = m.w; x_ = m.x; s_ = m.s; z_ = m.z;
         }
         // (a scalar load, read ahead of the first request: a load hipcc tracks inside the counted ring would bring the full drain back)
         if (modes & M_ZSCALAR) scalar_zero = (float)((const int32_t*)z_)[0];
-        // per-lane byte offsets, fixed for the whole launch.  Metadata row of chunk gc, lane g: ((gc * 32 + 2 g) * 8) >> gs_shift
-        // = (gc << 8 >> gs_shift) + (16 g >> gs_shift) for groups up to 256, gc >> (gs_shift - 8) for larger ones (16 g < 256)
-        const uint32_t vw0 = (uint32_t)(g * R) * sw4 + n0 * 4u, vw1 = vw0 + sw4, vx = (uint32_t)lane * 8u;
-        const uint32_t vm = (gs_shift < 8 ? (uint32_t)(g * R * 8) >> gs_shift : 0u) * mstride2 + n0 * 2u;
+        // per-lane byte offsets, fixed for the whole launch.  Metadata row of chunk gc, row pair g: ((gc * 32 + 2 g) * 8) >> gs_shift
+        // = (gc << 8 >> gs_shift) + (16 g >> gs_shift) for groups up to 256, gc >> (gs_shift - 8) for larger ones (16 g < 256).
+        // In pass p the lane's row pair is g = p * 16 / H + gl: the lane keeps gl's share, the pass adds whole multiples to the uniform
+        // bases — 32 / H weight rows, 512 / H bytes of x, (256 / H p) >> gs_shift metadata rows (16 g >> gs_shift splits exactly into the
+        // pass's part and the lane's: 256 / H p is a multiple of the group, or the 16 gl < 256 / H behind it stay inside its group)
+        const uint32_t vw0 = (uint32_t)(gl * R) * sw4 + n0 * 4u, vw1 = vw0 + sw4, vx = (uint32_t)lq * 8u;
+        const uint32_t vm = (gs_shift < 8 ? (uint32_t)(gl * R * 8) >> gs_shift : 0u) * mstride2 + n0 * 2u;
+        const uint32_t pass_w = (uint32_t)(CHUNK >> hl) * sw4, pass_x = (uint32_t)(CHUNK * 16) >> hl;
+        const int pass_ms = gs_shift < 8 ? gs_shift : 31;  // (groups of 256 and more: no metadata row inside a chunk)
         // (absent metadata is still requested — the first bytes of the weight buffer — so every item is five requests)
         const uint32_t vs = need_s ? vm : 0u, vz = need_z ? vm : 0u, ms_s = need_s ? mstride2 : 0u, ms_z = need_z ? mstride2 : 0u;
         const char *sb = need_s ? s_ : w_, *zb = need_z ? z_ : w_;
         const int shl = gs_shift < 8 ? 8 - gs_shift : 0, shr = gs_shift > 8 ? gs_shift - 8 : 0;
         const uint32_t chunk_w = (uint32_t)CHUNK * sw4;
         const int nv = v1 - v0, rem = (nch_total & (NW - 1)) - v0;
-        const int n = (nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem));  // items of this wave (0: an idle wave, or K too short)
+        const int n = ((nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem))) << hl;  // items of this wave: H passes per chunk (0: an idle wave, or K too short)
         // shared x: [partial rows, 64 KiB][units x 8 pair dwords][units x sum], units = 16 per chunk (gl_common.h: decode3_shared_x_lds_bytes)
         float* redg;
         uint32_t* xpairs = nullptr;
@@ -331,27 +361,32 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         } else {
             redg = red;
         }
-        float* rd = redg + slot * RED;
+        // the lane's place in a partial row of ITS slot (sub-wave h: slot + h); row v * 4 + r with r = p * 4 / H + (DPP row inside the sub-wave)
+        float* rd = redg + ((slot + (lane >> (6 - hl))) * RED + (lq >> 4) * TC + c * 4);
 
         constexpr int NLC = SX ? 4 : 5;
-        int rv = v0, rgc = v0;  // request cursor: virtual wave, chunk
+        int rv = v0, rp = 0, rgc = v0;  // request cursor: virtual wave, pass, chunk
         auto request = [&](Chunk& ck, int ri) __attribute__((always_inline)) {
 #if GL_DECODE3_ABLATION == 2
-            const int keep = rgc;
-            if (ri >= 2) rgc = v0;
+            const int keep = rgc, keep_p = rp;
+            if (ri >= 2) { rgc = v0; rp = 0; }
 #endif
-            const char* wq = w_ + (uint32_t)rgc * chunk_w;
+            const char* wq = w_ + ((uint32_t)rgc * chunk_w + (uint32_t)rp * pass_w);
             gvw::gld128<NT>(ck.w[0], wq, vw0);
             gvw::gld128<NT>(ck.w[1], wq, vw1);
-            if constexpr (!SX) gvw::gld64(ck.xq, x_ + (uint32_t)rgc * (uint32_t)(CHUNK * 16), vx);
-            const uint32_t grp = ((uint32_t)rgc << shl) >> shr;
+            if constexpr (!SX) gvw::gld64(ck.xq, x_ + ((uint32_t)rgc * (uint32_t)(CHUNK * 16) + (uint32_t)rp * pass_x), vx);
+            const uint32_t grp = (((uint32_t)rgc << shl) >> shr) + (((uint32_t)rp << (8 - hl)) >> pass_ms);
             gvw::gld64(ck.s, sb + grp * ms_s, vs);
             gvw::gld64(ck.z, zb + grp * ms_z, vz);
 #if GL_DECODE3_ABLATION == 2
             rgc = keep;
+            rp = keep_p;
 #endif
             rgc += NW;
-            if (rgc >= nch_total) rgc = ++rv;
+            if (rgc >= nch_total) {  // the next pass over this virtual wave, or the next virtual wave
+                if (++rp == H) { rp = 0; ++rv; }
+                rgc = rv;
+            }
         };
         auto tie_chunk = [&](Chunk& ck) __attribute__((always_inline)) {
             gvw::tie(ck.w[0]);
@@ -361,7 +396,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             gvw::tie(ck.z);
         };
         // a virtual wave's end, the single-layer code: DPP row sums, the partial row to the layer's LDS region
-        auto flush = [&](int v) {
+        auto flush = [&](int v, int p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float t = tot[j];
@@ -369,11 +404,11 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
                 t += dpp_movf<0x128>(t);  // row_ror:8
                 tot[j] = t;
             }
-            if ((lane & 12) == 0) *(f32x4*)(rd + ((v * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
+            if ((lane & 12) == 0) *(f32x4*)(rd + (v * 4 + (p << (2 - hl))) * TC) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
 #pragma unroll
             for (int j = 0; j < 4; ++j) tot[j] = 0.f;
         };
-        int cv = v0, cgc = v0;  // compute cursor
+        int cv = v0, cp = 0, cgc = v0;  // compute cursor
         // (the first two requests belong to the variant that consumes them: requested ahead of the branch, their registers — still in
         // flight — were COPIED into each variant's own set in front of its loop)
         // shared x, staging: unit u's 32 bytes of x become its eight pair dwords and its sum with the instructions compute() runs on them
@@ -400,9 +435,9 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         // (a lane past the last unit loads the last unit's bytes and writes nothing: units is a multiple of 16, not of 64)
         auto stage_off = [&](int u) { return (uint32_t)(u < units ? u : units - 1) * 32u; };
         constexpr int STRIPS = (int)((DECODE3_SHARED_X_MAX_UNITS + 1023) / 1024);  // staging trips of the 1024 threads: what fits in LDS
-        // the lane's unit of chunk 0; chunk gc is 128 dwords of pairs and 16 sums further: one vector add each per item
-        const uint32_t* xp_lane = xpairs + g * 8;
-        const float* xs_lane = xsums + g;
+        // the lane's unit of chunk 0, pass 0; chunk gc is 128 dwords of pairs and 16 sums further, pass p 16 / H units: one vector add each per item
+        const uint32_t* xp_lane = xpairs + gl * 8;
+        const float* xs_lane = xsums + gl;
         auto run = [&](auto full) {
             Chunk A, B;
             if constexpr (SX) {
@@ -437,10 +472,11 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             }
             gvw::ring2_run_pre<NLC>(n, A, B, request, tie_chunk, [&](int) __attribute__((always_inline)) {
                 if constexpr (SX) {
-                    const uint32_t* xp = xp_lane + cgc * 128;
+                    const int unit = cgc * 16 + (cp << (4 - hl));
+                    const uint32_t* xp = xp_lane + unit * 8;
                     xs.p[0] = *(const u32x4*)xp;
                     xs.p[1] = *(const u32x4*)(xp + 4);
-                    xs.sum = xs_lane[cgc * 16];
+                    xs.sum = xs_lane[unit];
                 }
             }, [&](const Chunk& ck, int) __attribute__((always_inline)) {
 #if GL_DECODE3_ABLATION == 1
@@ -454,8 +490,9 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
 #endif
                 cgc += NW;
                 if (cgc >= nch_total) {
-                    flush(cv);
-                    cgc = ++cv;
+                    flush(cv, cp);
+                    if (++cp == H) { cp = 0; ++cv; }
+                    cgc = cv;
                 }
             });
         };
@@ -463,7 +500,8 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         if (need_s && need_z) run(std::true_type{}); else run(std::false_type{});
         if (split.layer >= 0) {
 #pragma unroll 1
-            for (int v = cv; v < v1; ++v) flush(v);  // virtual waves without a chunk
+            for (int v = cv; v < v1; ++v)  // virtual waves without a chunk: every pass writes its rows (cp is 0 here: a virtual wave has all its passes or none)
+                for (int p = 0; p < H; ++p) flush(v, p);
         }
 
         // waves 0 .. slots - 1 finish one slot each (layer wave / TB on tile wave % TB); they ask for its bias element in front of the barrier
@@ -473,9 +511,9 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         uint16_t braw = 0;
         if (fin) {
             const int Lf = y + (wave >> g_tbl) * Y;
-            if (Lf > 0) o_ = counters.m[Lf - 1].out;
+            if (Lf > 0) o_ = decode3_table(counters).m[Lf - 1].out;
             if constexpr (BIASED) {
-                if (lane < 16) braw = counters.bias[Lf][ftile * TC + lane];
+                if (lane < 16) braw = decode3_table(counters).bias[Lf][ftile * TC + lane];
             }
         }
         __syncthreads();
@@ -508,22 +546,24 @@ const void* gemv_w4_decode3_fn(int tag, bool nt) {
 // meet in that XCD's L2 only; with tile groups (TB = 2, 4) by neighbouring waves of one block — and nothing keeps the two in step: the
 // partner asks for its half some time later, and a non-temporal line has left the L2 by then (11.6 MB fetched per layer against 9.5;
 // profiles/r13/decode_group_waves.log §2).
-const void* gemv_w4_decode3_group_fn(int tag) {
-    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3GroupTable);
-    kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTable>;
+// (h: the tiles per wave, 1 / 2 / 4; the forms of H = 1 keep the table itself as their Tail, and with it their names)
+template <typename Table, int HL>
+static const void* decode3_group_fn_of(int tag) {
+    using Tail = typename std::conditional<HL == 0, Table, Decode3Lines<Table, HL>>::type;
+    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Tail);
+    kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Tail> : gemv_w4_decode3_kernel<bf16_tag, false, Tail>;
     return (const void*)k;
 }
+template <typename Table>
+static const void* decode3_group_fn_of(int tag, int h) {
+    return h == 4 ? decode3_group_fn_of<Table, 2>(tag) : (h == 2 ? decode3_group_fn_of<Table, 1>(tag) : decode3_group_fn_of<Table, 0>(tag));
+}
+
+const void* gemv_w4_decode3_group_fn(int tag, int h) { return decode3_group_fn_of<Decode3GroupTable>(tag, h); }
 
 // The shared-x grouped forms (dynamic LDS: decode3_shared_x_lds_bytes), unbiased / biased
-const void* gemv_w4_decode3_group_sx_fn(int tag, bool biased) {
-    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3GroupTableSX);
-    typedef void (*kfnb)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3BiasGroupTableSX);
-    if (biased) {
-        kfnb k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3BiasGroupTableSX> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3BiasGroupTableSX>;
-        return (const void*)k;
-    }
-    kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3GroupTableSX> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3GroupTableSX>;
-    return (const void*)k;
+const void* gemv_w4_decode3_group_sx_fn(int tag, bool biased, int h) {
+    return biased ? decode3_group_fn_of<Decode3BiasGroupTableSX>(tag, h) : decode3_group_fn_of<Decode3GroupTableSX>(tag, h);
 }
 
 const void* gemv_w4_decode3_bias_fn(int tag, bool nt) {
@@ -533,10 +573,6 @@ const void* gemv_w4_decode3_bias_fn(int tag, bool nt) {
     return (const void*)k;
 }
 
-const void* gemv_w4_decode3_bias_group_fn(int tag) {
-    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3BiasGroupTable);
-    kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Decode3BiasGroupTable> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3BiasGroupTable>;
-    return (const void*)k;
-}
+const void* gemv_w4_decode3_bias_group_fn(int tag, int h) { return decode3_group_fn_of<Decode3BiasGroupTable>(tag, h); }
 
 }  // namespace gl

@@ -631,6 +631,22 @@ struct Decode3BiasGroupTableSX {
     Decode3Member m[DECODE3_GMAX - 1];
     const uint16_t* bias[DECODE3_GMAX];
 };
+// LINES (below: decode3_group_lines): the same four tables under a type that carries log2 of the tiles per wave, for the forms with H = 2 and
+// H = 4 (the kernel functions differ; the layout is the table's, so the same objects are passed)
+template <typename Table, int HL>
+struct Decode3Lines {
+    Table t;
+};
+template <typename T>
+struct Decode3LinesOf {
+    using table = T;
+    static constexpr int hl = 0;
+};
+template <typename T, int HL>
+struct Decode3LinesOf<Decode3Lines<T, HL>> {
+    using table = T;
+    static constexpr int hl = HL;
+};
 // LDS of a shared-x block: the 64 KiB of partial rows (DECODE3_GMAX layers x 4 KiB), then per 16-element unit of x (K / 16 = 16 per 32-row
 // chunk) 32 bytes of pair dwords, then per unit its 4-byte sum: 64 KiB + 2.25 K bytes, dynamic.  The block's 1024 threads stage the
 // units in trips of 1024.  0: the staging area does not fit beside the partial rows in the 160 KiB of a CU (K > 43520).
@@ -648,7 +664,8 @@ inline int decode3_group_form(int members, bool same_x, int64_t nch_total, bool 
     return (shared_x_enabled && same_x && members >= DECODE3_SHARED_X_MIN_MEMBERS && decode3_shared_x_lds_bytes(nch_total) > 0) ? 2 : 1;
 }
 // `modes` of a grouped launch: members in bits 16..20, log2 of the tiles per block (TB) in 21..22, the span placement in 23, grid.y in
-// 24..31.  TB = 1 without the span bit is the word the launch carried before tile groups existed.
+// 24..31.  TB = 1 without the span bit is the word the launch carried before tile groups existed.  (The tiles per wave, H, are not in
+// the word: every H has kernel functions of its own.)
 constexpr uint32_t DECODE3_M_MEMBERS = 31u, DECODE3_M_TB_SHIFT = 21u, DECODE3_M_SPAN = 1u << 23;
 inline uint32_t decode3_group_modes(uint32_t modes, int members, int grid_y, int tb = 1, bool span = false) {
     return (modes & 0xFFFFu) | ((uint32_t)members << 16) | ((tb == 4 ? 2u : (tb == 2 ? 1u : 0u)) << DECODE3_M_TB_SHIFT) | (span ? DECODE3_M_SPAN : 0u) |
@@ -677,7 +694,8 @@ GL_HD Decode3WaveSplit decode3_wave_split(int lb, int wave) {
 // Y = decode3_group_grid_y(tiles / TB, members, resident) and LB = ceil((members - y) / Y).  Its LB * TB (layer, tile) SLOTS (at most 16)
 // take the place of the layers in decode3_wave_split(): slot s is block-local layer s / TB and tile s % TB of the block's tile group, so
 // the waves that read the two (TB = 2) or four (TB = 4: two lines) 64-byte halves of a weight row's 128-byte lines are neighbours on one
-// CU and walk the same item list.  Each slot owns one 4 KiB partial-row region, as each layer did.
+// CU and walk the same item list.  Each slot owns one 4 KiB partial-row region, as each layer did.  (With LINES, below, a wave takes
+// H adjacent slots of one layer at once — a WAVE-SLOT — in H passes, and decode3_wave_split() is called on LB * TB / H wave-slots.)
 // The rule: the largest TB <= tb_want with tiles % TB == 0 and ceil(members / Y) * TB <= 16.
 struct Decode3GroupGeometry {
     int tb, grid_x, grid_y;
@@ -706,6 +724,30 @@ GL_HD int decode3_group_first_tile(int block, int groups, int tb, bool span, boo
         grp = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
     }
     return grp * tb;
+}
+// LINES.  A wave of a grouped block works on H in {1, 2, 4} adjacent tiles of the block's tile group at once: its 64 lanes are H sub-waves
+// of 64 / H lanes, sub-wave h on tile run * H + h, lane l' of a sub-wave is (c = l' & 3, gl = l' >> 2) and in pass p = 0 .. H - 1 over a
+// virtual wave takes the row pair g = p * 16 / H + gl.  One request instruction then covers one row of each of its 16 / H row pairs, in H tiles: 8 rows x 128
+// contiguous bytes (H = 2) or 4 rows x 256 (H = 4) instead of 16 rows x 64, and every 128-byte line is asked for by ONE instruction.
+// What the waves share is the block's LB * TB / H WAVE-SLOTS (a layer x a run of H tiles): decode3_wave_split() is called on that count,
+// a wave's items are (virtual wave, pass, chunk) ascending, and sub-wave h of wave-slot ws fills slot ws * H + h — the same 4 KiB region,
+// partial row v * 4 + r with r = p * 4 / H + (16-lane row inside the sub-wave), as the four row pairs 4 r .. 4 r + 3 always wrote.
+// H must divide TB: a wanted H falls back 4 -> 2 -> 1.
+GL_HD int decode3_group_lines(int tb, int h_want) {
+    int h = h_want >= 4 ? 4 : (h_want >= 2 ? 2 : 1);
+    while (h > tb) h >>= 1;
+    return h;
+}
+// The H a launch carries when nothing is forced.  THE RULE (measured: profiles/r18/decode_group_lines.log §4 - §6): whole lines whenever the
+// block holds them — H = 2 for every TB >= 2 — and H = 4 where TB = 4 and the fullest block holds four layers.  At 256 tiles on 256 CUs
+// H = 2 beat H = 1 by 7 - 15 % at every member count measured under TB = 2 (2, 5, 6) and TB = 4 (4, 7, 8, 10, 12, 15, 16); H = 4 was
+// 2 - 10 % SLOWER than H = 2 where the fullest block holds one to three layers (4 - 12 members: one to three wave-slots per block, every
+// wave of the CU on the same 256-byte column strip) and level with it or ahead where it holds four (15, 16 members).
+inline int decode3_group_lines_default(int tiles, int members, int64_t resident, int tb) {
+    if (tb < 2) return 1;
+    const Decode3GroupGeometry geo = decode3_group_geometry(tiles, members, resident, tb, false);
+    const int lb = (members + geo.grid_y - 1) / geo.grid_y;  // layers of the fullest block
+    return (geo.tb == 4 && lb >= 4) ? 4 : 2;
 }
 // What capture_group.hip asks decode3_group_geometry() for when nothing is forced: {tb_want, span} from the group's shape.
 // THE RULE (measured: profiles/r16/decode_group_tiles.log §4 - §6): the interleaved placement, and the largest TB whose busiest CU gets

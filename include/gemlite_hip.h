@@ -363,7 +363,14 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
  *                1 span (span_want).  tb_want = 0: what a capture picks (GEMLITE_HIP_CAPTURE_GROUP_TILES=<TB>[s|i], read once, or the
  *                default rule).  Returns 0, or -1 for an argument out of range
  *   _tile_of     host only, DEVELOPMENT / TEST: the first tile of the tile group that block `block` (0 .. tiles / tb - 1) of a grouped
- *                launch works on, a permutation of the groups under either placement (span = 0 / 1); -1 for an argument out of range */
+ *                launch works on, a permutation of the groups under either placement (span = 0 / 1); -1 for an argument out of range
+ *   _lines       host only, DEVELOPMENT / TEST: the tiles per wave H (1, 2 or 4) that a grouped launch of `members` layers of `tiles`
+ *                tiles with `tb` tiles per block carries: a wave's lanes are H sub-waves on H adjacent tiles and take H passes over each
+ *                virtual wave, so one request instruction asks for whole 128-byte (H = 2) or 256-byte (H = 4) runs of a weight row; the
+ *                block's slots / H wave-slots are what _wave_split calls layers.  H divides TB: h_want = 4 falls back to 2, then 1.
+ *                h_want = 0: what a capture picks (GEMLITE_HIP_CAPTURE_GROUP_LINES=1|2|4, read once, or the default rule).  -1 for an
+ *                argument out of range
+ *   _last_lines  host only: the H of the grouped decode node the calling thread rewrote last (0: none) */
 int gemlite_hip_capture_group_max(void);
 void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
@@ -374,6 +381,8 @@ int gemlite_hip_capture_group_form(int32_t members, int32_t same_x, int64_t K);
 int64_t gemlite_hip_capture_group_shared_x_lds_bytes(int64_t K);
 int gemlite_hip_capture_group_geometry(int32_t tiles, int32_t members, int32_t resident, int32_t tb_want, int32_t span_want, int32_t out[4]);
 int gemlite_hip_capture_group_tile_of(int32_t tiles, int32_t tb, int32_t span, int32_t block);
+int gemlite_hip_capture_group_lines(int32_t tiles, int32_t members, int32_t resident, int32_t tb, int32_t h_want);
+int gemlite_hip_capture_group_last_lines(void);
 
 /* Bias in the launch (optional extension; gemlite_hip_forward_args and every entry point above are unchanged).  The M = 1 decode kernel
  * (gemv_w4_decode3_kernel, single and grouped) and the few-row kernels (gemm_w4_rows_kernel / gemm_w2_rows_kernel) have forms that add a
