@@ -10,7 +10,7 @@
 //   * a decode3 launch under capture that cannot join is launched as always, and the node it became opens a group of one;
 //   * the next decode3 launch joins the open group when NOTHING else was captured on the stream since (the stream's only dependency is the
 //     group's node), kernel / shape / strides / modes agree, and its output overlaps no member's inputs or output and no member's output
-//     overlaps its inputs (a bias the kernel adds itself — gemlite_hip_forward_ext — is one more input).  Joining rewrites the node to gemv_w4_decode3_kernel<.., Decode3GroupTable>, grid (tiles, Y) with
+//     overlaps its inputs (a bias the kernel adds itself — gemlite_hip_forward_ext — is one more input).  Joining rewrites the node to gemv_w4_decode3_group_kernel, grid (tiles, Y) with
 //     Y = clamp(resident blocks / tiles, 1, members): one resident block per tile holds its members ALL AT ONCE — each member gets
 //     16 / (members of the block) of the block's waves and its own 4 KB of LDS, and the block has one barrier (decode3_wave_split,
 //     gl_common.h; gemv_decode.hip) — and narrow layers spread their members over the CUs their tiles leave idle.  No node is added and
@@ -58,11 +58,9 @@
 
 namespace gl {
 
-const void* gemv_w4_decode3_fn(int tag, bool nt);        // gemv_decode.hip
-const void* gemv_w4_decode3_group_fn(int tag, int h);       // gemv_decode.hip: default-policy weight loads whatever the members' launches use
-const void* gemv_w4_decode3_bias_fn(int tag, bool nt);        // the forms that add a bias in the epilogue: a group holds one kind only
-const void* gemv_w4_decode3_bias_group_fn(int tag, int h);       // (the kernel functions differ, so same_launch() keeps them apart)
-const void* gemv_w4_decode3_group_sx_fn(int tag, bool biased, int h);  // gemv_decode.hip: the shared-x grouped forms (h: tiles per wave)
+// gemv_decode.hip: the grouped forms (h: tiles per wave), default-policy weight loads whatever the members' launches use.  A group holds
+// biased launches or unbiased ones, never both: their kernel functions differ, so same_launch() keeps them apart
+const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h);
 int ensure_lds(const void* fn, size_t lds, int dev);            // api.hip
 
 namespace {
@@ -130,29 +128,12 @@ bool same_launch(const LaunchPlan& a, const LaunchPlan& b) {
            a.d3.nch_total == b.d3.nch_total && a.d3.modes == b.d3.modes && !(a.d3.modes & 64u);
 }
 
-// The grouped form of a rows launch (the planner filled both in; `fn` is the biased form exactly when the launch carries a bias)
-const void* rows_group_fn_of(const LaunchPlan& lp) {
-    if (lp.arg_kind != 2) return nullptr;
-    return lp.bias ? (lp.fn == lp.fn_bias ? lp.fn_bias_group : nullptr) : (lp.fn == lp.bias_of ? lp.fn_group : nullptr);
-}
-
-const void* group_fn_of(const void* fn, int h = 1) {
-    for (int tag = 0; tag < 2; ++tag)
-        for (int nt = 0; nt < 2; ++nt)
-            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_fn(tag, h);
-    for (int tag = 0; tag < 2; ++tag)
-        for (int nt = 0; nt < 2; ++nt)
-            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_bias_group_fn(tag, h);
-    return nullptr;
-}
-
-const void* group_sx_fn_of(const void* fn, int h = 1) {
-    for (int tag = 0; tag < 2; ++tag)
-        for (int nt = 0; nt < 2; ++nt) {
-            if (fn == gemv_w4_decode3_fn(tag, nt != 0)) return gemv_w4_decode3_group_sx_fn(tag, false, h);
-            if (fn == gemv_w4_decode3_bias_fn(tag, nt != 0)) return gemv_w4_decode3_group_sx_fn(tag, true, h);
-        }
-    return nullptr;
+// Does the launch have grouped forms?  The planner says so — rows: LaunchPlan::fn_group / fn_bias_group, decode3: d3_group_tag — and `fn`
+// is still the planner's choice (the biased form exactly when the launch carries a bias)
+bool has_group_form(const LaunchPlan& lp) {
+    if (lp.fn != (lp.bias ? lp.fn_bias : lp.bias_of)) return false;
+    if (lp.arg_kind == 2) return (lp.bias ? lp.fn_bias_group : lp.fn_group) != nullptr;
+    return lp.arg_kind == 1 && lp.d3_group_tag >= 0;
 }
 
 int env_int(const char* name, int absent) {
@@ -169,13 +150,8 @@ struct Group {
     hipGraph_t graph = nullptr;
     hipGraphNode_t node = nullptr;
     LaunchPlan lp{};  // member 0: kernel, grid, block, scalars
-    const void* fn_group = nullptr;
-    const void* fn_group_sx = nullptr;
     bool same_x = true;  // every member so far reads member 0's x
-    Decode3GroupTable tab{};
-    Decode3BiasGroupTable tabb{};  // the table of a biased group (lp.bias set) instead of `tab`
-    Rows5GroupTable rtab{};        // a rows group (lp.arg_kind == 2): its table,
-    Rows5BiasGroupTable rtabb{};   // and the table of a biased one
+    GroupTable<true> tab{};  // members 1 .. and every member's bias; an unbiased kernel's argument is its prefix (gl_common.h)
     Footprint fp[DECODE3_GMAX];
     int members = 0;
 };
@@ -249,8 +225,33 @@ void capture_group_stats(uint64_t* seen, uint64_t* joined) {
 // The host-only rule: may launch B (args b, plan lb) run in the same grouped launch as A?
 bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPlan& la, const gemlite_hip_forward_args& b, const LaunchPlan& lb) {
     if (!same_launch(la, lb)) return false;
-    if (la.arg_kind == 2 ? rows_group_fn_of(la) == nullptr : group_fn_of(la.fn) == nullptr) return false;
+    if (!has_group_form(la)) return false;
     return independent(footprint(a, la), footprint(b, lb));
+}
+
+// What a join of either family does once its kernel, grid, LDS bytes and argument list are chosen: member g.members goes into the table
+// (its pointers behind the scalars of member 0), the node becomes `fn`, the bookkeeping.  A failed rewrite leaves the node what it was: the
+// group is dropped and this call runs on its own.
+static bool rewrite_node(Group& g, const GroupMember& mb, const uint16_t* bias, const Footprint& fb, const void* fn, dim3 grid, size_t lds,
+                         void** kargs) {
+    g.tab.m[g.members - 1] = mb;
+    g.tab.bias[g.members] = bias;
+    hipKernelNodeParams np;
+    memset(&np, 0, sizeof(np));
+    np.func = (void*)fn;
+    np.gridDim = grid;
+    np.blockDim = g.lp.block;
+    np.sharedMemBytes = (unsigned)lds;
+    np.kernelParams = kargs;
+    np.extra = nullptr;
+    if (hipGraphKernelNodeSetParams(g.node, &np) != hipSuccess) {
+        (void)hipGetLastError();
+        g.open = false;
+        return false;
+    }
+    g.fp[g.members++] = fb;
+    g_joined.fetch_add(1, std::memory_order_relaxed);
+    return true;
 }
 
 // Called in front of every decode3 and every rows launch that carries no profile events.  true: the call was folded into the open group's node, nothing
@@ -277,40 +278,22 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
         if (!independent(g.fp[i], fb)) return false;
     const bool biased = g.lp.bias != nullptr;  // (lp.bias too: same_launch() compared the kernel functions)
     if (rows) {
-        // member g.members of the node: its pointers behind the scalars of member 0, grid.y one more.  The cap on dynamic LDS first (a
-        // rows block takes 146 KiB): once per grouped function and device
-        if (ensure_lds(g.fn_group, g.lp.lds_bytes, dev) != GEMLITE_OK) {
+        // grid.y one more.  The cap on dynamic LDS first (a rows block takes 146 KiB): once per grouped function and device
+        const void* fn = biased ? g.lp.fn_bias_group : g.lp.fn_group;
+        if (ensure_lds(fn, g.lp.lds_bytes, dev) != GEMLITE_OK) {
             g.open = false;
             return false;
         }
-        Rows5Member& rm = biased ? g.rtabb.m[g.members - 1] : g.rtab.m[g.members - 1];
-        if (biased) g.rtabb.bias[g.members] = lp.bias;
-        rm.w = lp.r5.w; rm.x = lp.r5.x; rm.s = lp.r5.s; rm.z = lp.r5.z; rm.out = lp.r5.out;
         Rows5Args& r = g.lp.r5;
-        void* rargs[] = {(void*)&r.w, (void*)&r.x, (void*)&r.s, (void*)&r.z, (void*)&r.out, (void*)&r.sw4, (void*)&r.mstride2, (void*)&r.nch_total,
-                         (void*)&r.modes, (void*)&r.M, (void*)&r.sxm2, (void*)&r.som, biased ? (void*)&g.rtabb : (void*)&g.rtab};
-        hipKernelNodeParams rp;
-        memset(&rp, 0, sizeof(rp));
-        rp.func = (void*)g.fn_group;
-        rp.gridDim = dim3(g.lp.grid.x, (unsigned)(g.members + 1), 1);
-        rp.blockDim = g.lp.block;
-        rp.sharedMemBytes = (unsigned)g.lp.lds_bytes;
-        rp.kernelParams = rargs;
-        rp.extra = nullptr;
-        if (hipGraphKernelNodeSetParams(g.node, &rp) != hipSuccess) {  // the node keeps what it had; this call runs on its own
-            (void)hipGetLastError();
-            g.open = false;
+        void* kargs[] = {(void*)&r.w, (void*)&r.x, (void*)&r.s, (void*)&r.z, (void*)&r.out, (void*)&r.sw4, (void*)&r.mstride2, (void*)&r.nch_total,
+                         (void*)&r.modes, (void*)&r.M, (void*)&r.sxm2, (void*)&r.som, (void*)&g.tab};
+        if (!rewrite_node(g, GroupMember{lp.r5.w, lp.r5.x, lp.r5.s, lp.r5.z, lp.r5.out}, lp.bias, fb, fn, dim3(g.lp.grid.x, (unsigned)(g.members + 1), 1),
+                          g.lp.lds_bytes, kargs))
             return false;
-        }
-        g.fp[g.members++] = fb;
         tl_last_form = 3;
         tl_last_lines = 0;
-        g_joined.fetch_add(1, std::memory_order_relaxed);
         return true;
     }
-    Decode3Member& m = biased ? g.tabb.m[g.members - 1] : g.tab.m[g.members - 1];
-    if (biased) g.tabb.bias[g.members] = lp.bias;
-    m.w = lp.d3.w; m.x = lp.d3.x; m.s = lp.d3.s; m.z = lp.d3.z; m.out = lp.d3.out;
     Decode3Args& d = g.lp.d3;
     // the node as it is after this join: members and grid.y are recomputed every time and travel in `modes` (no implicit grid arguments)
     const int members = g.members + 1, tiles = (int)g.lp.grid.x;
@@ -318,35 +301,23 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     const Decode3GroupGeometry geo = decode3_group_geometry(tiles, members, resident, want.tb, want.span);
     const int lines = decode3_group_lines(geo.tb, capture_group_lines_wanted(tiles, members, resident, geo.tb));
     uint32_t modes = decode3_group_modes(d.modes, members, geo.grid_y, geo.tb, geo.span);
-    // (every H has kernel functions of its own; g.fn_group / g.fn_group_sx are those of H = 1 and say which forms exist)
-    const void* fn_g = group_fn_of(g.lp.fn, lines);
-    const void* fn_sx = g.fn_group_sx ? group_sx_fn_of(g.lp.fn, lines) : nullptr;
-    // (the shared-x tables have the layout of the other two: the same objects are passed)
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
-                     (void*)&d.nch_total, (void*)&modes, biased ? (void*)&g.tabb : (void*)&g.tab};
+                     (void*)&d.nch_total, (void*)&modes, (void*)&g.tab};
     const bool same_x = g.same_x && lp.d3.x == d.x;
-    int form = decode3_group_form(members, same_x, d.nch_total, capture_group_shared_x_enabled() && g.fn_group_sx != nullptr);
-    const size_t lds = form == 2 ? (size_t)decode3_shared_x_lds_bytes(d.nch_total) : 0;
-    // (the cap is raised once per kernel and device, to the form's maximum: the size of a launch depends on its K)
-    if (form == 2 && ensure_lds(fn_sx, (size_t)DECODE3_SHARED_X_MAX_LDS, dev) != GEMLITE_OK) form = 1;
-    hipKernelNodeParams np;
-    memset(&np, 0, sizeof(np));
-    np.func = (void*)(form == 2 ? fn_sx : fn_g);
-    np.gridDim = dim3((unsigned)geo.grid_x, (unsigned)geo.grid_y, 1);
-    np.blockDim = g.lp.block;
-    np.sharedMemBytes = form == 2 ? (unsigned)lds : 0;
-    np.kernelParams = kargs;
-    np.extra = nullptr;
-    if (hipGraphKernelNodeSetParams(g.node, &np) != hipSuccess) {  // the node keeps what it had; this call runs on its own
-        (void)hipGetLastError();
-        g.open = false;
-        return false;
+    int form = decode3_group_form(members, same_x, d.nch_total, capture_group_shared_x_enabled());
+    // (every H has kernel functions of its own.  The cap is raised once per kernel and device, to the form's maximum: the size of a launch depends on its K)
+    const void* fn = gemv_w4_decode3_group_fn(g.lp.d3_group_tag, biased, form == 2, lines);
+    if (form == 2 && ensure_lds(fn, (size_t)DECODE3_SHARED_X_MAX_LDS, dev) != GEMLITE_OK) {
+        form = 1;
+        fn = gemv_w4_decode3_group_fn(g.lp.d3_group_tag, biased, false, lines);
     }
-    g.fp[g.members++] = fb;
+    const size_t lds = form == 2 ? (size_t)decode3_shared_x_lds_bytes(d.nch_total) : 0;
+    if (!rewrite_node(g, GroupMember{lp.d3.w, lp.d3.x, lp.d3.s, lp.d3.z, lp.d3.out}, lp.bias, fb, fn, dim3((unsigned)geo.grid_x, (unsigned)geo.grid_y, 1), lds,
+                      kargs))
+        return false;
     g.same_x = same_x;
     tl_last_form = form;
     tl_last_lines = lines;
-    g_joined.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 
@@ -357,8 +328,7 @@ void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPl
     if (!g.capturing) return;
     g.capturing = false;
     g.open = false;
-    const void* fn_group = lp.arg_kind == 2 ? rows_group_fn_of(lp) : group_fn_of(lp.fn);
-    if (!fn_group || (lp.arg_kind != 1 && lp.arg_kind != 2) || lp.grid.y != 1 || lp.grid.z != 1) return;
+    if (!has_group_form(lp) || lp.grid.y != 1 || lp.grid.z != 1) return;
     unsigned long long id = 0;
     hipGraph_t graph = nullptr;
     hipGraphNode_t dep = nullptr;
@@ -370,17 +340,11 @@ void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPl
     g.graph = graph;
     g.node = dep;
     g.lp = lp;
-    g.fn_group = fn_group;
-    g.fn_group_sx = lp.arg_kind == 1 ? group_sx_fn_of(lp.fn) : nullptr;
     g.same_x = true;
     tl_last_form = 0;  // (a group of one: no grouped node yet)
     tl_last_lines = 0;
     memset(&g.tab, 0, sizeof(g.tab));
-    memset(&g.tabb, 0, sizeof(g.tabb));
-    g.tabb.bias[0] = lp.bias;
-    memset(&g.rtab, 0, sizeof(g.rtab));
-    memset(&g.rtabb, 0, sizeof(g.rtabb));
-    g.rtabb.bias[0] = lp.bias;
+    g.tab.bias[0] = lp.bias;
     g.fp[0] = footprint(a, lp);
     g.members = 1;
     g.open = true;

@@ -3,7 +3,7 @@
 //   GL_ROWS5_KERNEL = gemm_w4_rows_bias_kernel, GL_ROWS5_BIAS = 1: one more argument (behind the preloaded dwords) and the bias add in the epilogue
 //   GL_ROWS5_GROUP = 1 (gemm_wn_rows_group.hip: gemm_w4_rows_group_kernel / gemm_w4_rows_bias_group_kernel): the GROUPED forms — grid (tiles,
 //       members), block (tile, y) computes member y's tile.  Member 0's pointers are the preloaded dwords, members 1 .. come from the by-value
-//       table behind the scalars (gl_common.h: Rows5GroupTable / Rows5BiasGroupTable), selected by blockIdx.y — uniform, so scalar loads, once
+//       table behind the scalars (gl_common.h: GroupTable<biased>), selected by blockIdx.y — uniform, so scalar loads, once
 //       per wave and in front of the first request.  Everything behind the selection is the single-layer body; the row blocks along grid.y
 //       are compiled out (launches with row blocks never group).  GL_ROWS5_GROUP undefined or 0: the two forms above, token for token.
 #if defined(GL_ROWS5_GROUP) && GL_ROWS5_GROUP
@@ -11,10 +11,8 @@
 #else
 #define GL_ROWS5_GROUPED 0
 #endif
-#if GL_ROWS5_GROUPED && GL_ROWS5_BIAS
-#define GL_ROWS5_BIAS_PARAM , const Rows5BiasGroupTable tab
-#elif GL_ROWS5_GROUPED
-#define GL_ROWS5_BIAS_PARAM , const Rows5GroupTable tab
+#if GL_ROWS5_GROUPED
+#define GL_ROWS5_BIAS_PARAM , const GroupTable<GL_ROWS5_BIAS != 0> tab
 #elif GL_ROWS5_BIAS
 #define GL_ROWS5_BIAS_PARAM , const uint16_t* bias
 #else
@@ -56,7 +54,7 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
     // this block's member: the preloaded scalars (member 0) or the by-value table — blockIdx.y is uniform, so these are scalar loads
     const int member = (int)blockIdx.y;
     if (member > 0) {
-        const Rows5Member& mb = tab.m[member - 1];
+        const GroupMember& mb = tab.m[member - 1];
         wb = mb.w; xb = mb.x; sp = mb.s; zp = mb.z; out = mb.out;
     }
 #if GL_ROWS5_BIAS

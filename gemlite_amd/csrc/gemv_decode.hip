@@ -15,28 +15,39 @@
 //   * grid size / tile pairing come in through the arguments: no implicit-argument loads at all.
 // 16 waves x 64 lanes, lane (g = lane >> 2, c = lane & 3) owns columns 4c .. 4c + 3 of a 16-column tile and packed rows
 // chunk * 512 + wave * 32 + 2 g + {0, 1}.
-// The grouped forms (round 18, LINES): a wave may work on H = 2 or 4 adjacent tiles at once — its lanes are H sub-waves of 64 / H lanes,
-// sub-wave h on tile t0 + h, lane l' of a sub-wave is (c = l' & 3, gl = l' >> 2) — and takes H PASSES over each virtual wave, in pass p the
-// row pair g = p * 16 / H + gl.  One request instruction then asks for 8 rows x 128 contiguous bytes (H = 2) or 4 rows x 256 (H = 4)
-// where it asked for 16 rows x 64: every 128-byte line of the weights is requested once, by one instruction, and nothing depends on two
-// waves staying in step.  The block's slots / H WAVE-SLOTS (a layer x a run of H tiles) are what decode3_wave_split() hands to the waves.
+//
+// Two kernels, the form of each spelled in its template parameters; they share the device helpers of dec3 (an item's arithmetic, the row
+// sums, the final reduction with the bias add and the store), so per layer a group runs the single-layer code in the same order and every
+// layer's output is bit-identical to its own launch:
+//   kernel                                               argument behind the 14 dwords    launched by
+//   gemv_w4_decode3_kernel<Tag, NT, BIASED>              unsigned* counters (timeline) |  the planner: dependent chains, eager and profiled
+//                                                        Decode3BiasTail (BIASED)         launches, a group of one
+//   gemv_w4_decode3_group_kernel<Tag, BIASED, SX, HL>    GroupTable<BIASED> by value      capture_group.hip, by rewriting a capture's node
+//     BIASED  the bias add in the epilogue (gl_common.h has the arithmetic); the lanes that store ask for their bias element in front of
+//             the barrier, so it arrives under the reduction
+//     SX      SHARED X, for a group whose members all read the same x.  What a lane derives from x — the pair dwords (x0,x4)(x1,x5)(x2,x6)
+//             (x3,x7) of its two rows and the sum of its 16 activations — depends on x alone, and the per-wave-x form derives it again in
+//             every quad of every wave of every block: 8 DPP broadcasts, 8 v_perm, 8 dot products and one of five memory requests per
+//             item.  Here thread u of a block does it ONCE for the units u, u + 1024, ... < K / 16 (x[16 u .. 16 u + 15], the rows 2 u,
+//             2 u + 1), with the same instructions in the same order, and writes 36 bytes to LDS (dynamic: decode3_shared_x_lds_bytes);
+//             an item is then four requests and three LDS reads.  The x loads go out first, the wave's first two items behind them, and
+//             the counted wait in front of the one extra barrier covers the x loads only: the weight requests stay in flight across it.
+//             The members' x pointers are not read.
+//     HL      LINES (gl_common.h): H = 1 << HL = 1, 2 or 4 adjacent tiles per wave — its lanes are H sub-waves of 64 / H lanes, sub-wave h
+//             on tile t0 + h, lane l' of a sub-wave is (c = l' & 3, gl = l' >> 2) — in H PASSES over each virtual wave, in pass p the row
+//             pair g = p * 16 / H + gl.  One request instruction then asks for 8 rows x 128 contiguous bytes (H = 2) or 4 rows x 256
+//             (H = 4) where it asked for 16 rows x 64: every 128-byte line of the weights is requested once, by one instruction, and
+//             nothing depends on two waves staying in step.  A compile-time constant, so the H = 1 forms are the code they were and the
+//             shifts of the others fold (profiles/r18/decode_group_lines.log §1).
+// A group: up to DECODE3_GMAX independent layers of identical shape, strides, modes and dtype (capture_group.hip folds back-to-back
+// independent launches of a stream capture into one launch).  Grid (N / 16 / TB, Y): block (tile group, y) holds the layers y, y + Y, ... of
+// its tiles, all at once: each (layer, tile) slot gets its share of the 16 waves and its own 4 KB of LDS, and the block has ONE barrier (the
+// comment at the kernel has the details).  Member count, TB and Y come in `modes`.  Layer 0's pointers are the preloaded scalars; the
+// others come out of the by-value table with scalar loads, once per wave.  No timeline probe in a group.
 #include <type_traits>
 
 #include "gl_common.h"
-#include "gl_async.h"  // gvw: counted asm requests, ring2_run (the grouped form)
-
-// Development only (profiles/r15/decode_group_shared_x.log, the two floors): -DGL_DECODE3_ABLATION=1 replaces the arithmetic of a grouped item
-// by an xor of its loaded registers (requests and waits unchanged: the memory-side floor of the request pattern), =2 sends every request
-// behind a wave's first two to the addresses of its first item (cache-hot; arithmetic unchanged: the issue-side floor).  Outputs are wrong
-// by construction.  Not defined in any build the Makefile knows.
-#ifndef GL_DECODE3_ABLATION
-#define GL_DECODE3_ABLATION 0
-#endif
-// Development only (the same log, §4): -DGL_DECODE3_DOT2_ZERO=1 writes the first product of each fp16 accumulator of the grouped forms as
-// the three-operand v_dot2_f32_f16 with a literal 0 (hipcc emits v_mov 0 + v_dot2c from the builtin).
-#ifndef GL_DECODE3_DOT2_ZERO
-#define GL_DECODE3_DOT2_ZERO 0
-#endif
+#include "gl_async.h"  // gvw: counted asm requests, ring2_run (the grouped kernel)
 
 namespace gl {
 
@@ -55,139 +66,37 @@ __device__ __forceinline__ float dpp_movf(float v) {
 //        grouped launches only (capture_group.hip; gl_common.h: decode3_group_modes): 16..20 members | 21..22 log2(tiles per block) |
 //        23 span placement of the tile groups | 24..31 grid.y
 constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
+constexpr int R = 2, NW = 16, CHUNK = 32, TC = 16, CSTRIDE = NW * CHUNK;
+constexpr int RED = NW * 4 * TC;  // floats of one partial-row region: [NW * 4 DPP rows][16 columns], 4 KiB
 
-}  // namespace dec3
-
-// Tail = unsigned*: the single-layer kernel, `counters` is the timeline buffer.
-// Tail = Decode3GroupTable: the GROUPED form — up to DECODE3_GMAX independent layers of identical shape, strides, modes and dtype
-// (capture_group.hip folds back-to-back independent launches of a stream capture into one such launch).  Grid (N / 16, Y): block
-// (tile, y) holds the layers y, y + Y, ... of its tile, all at once: each layer gets 16 / (layers in the block) waves and its own 4 KB
-// of LDS, and the block has ONE barrier (the comment at the loop has the details).  Member count and Y come in `modes`.  Layer 0's
-// pointers are the preloaded scalars; the others come out of the by-value table behind the 14 dwords with scalar loads, once per
-// wave.  Per layer the arithmetic is the single-layer code in the same order, so
-// every layer's output is bit-identical to its own launch.  No timeline probe in a group.  The single-layer instantiation is untouched:
-// dependent chains, eager launches and profiled launches run it.
-// Tail = Decode3BiasTail / Decode3BiasGroupTable: the same two forms with the bias add in the epilogue (gl_common.h has the arithmetic).
-// The lanes of wave 0 that store ask for their bias element in front of the layer's barrier, so it arrives under the reduction.
-// Tail = Decode3GroupTableSX / Decode3BiasGroupTableSX: the SHARED-X grouped forms, for a group whose members all read the same x.  What a
-// lane derives from x — the pair dwords (x0,x4)(x1,x5)(x2,x6)(x3,x7) of its two rows and the sum of its 16 activations — depends on x
-// alone, and the other grouped forms derive it again in every quad of every wave of every block: 8 DPP broadcasts, 8 v_perm, 8 dot
-// products and one of five memory requests per item.  Here thread u of a block does it ONCE for the units u, u + 1024, ... < K / 16 (x[16 u .. 16 u + 15], the rows
-// 2 u, 2 u + 1), with the same instructions in the same order, and writes 36 bytes to LDS; an item is then four requests and three LDS
-// reads.  The x loads go out first, the wave's first two items behind them, and the counted wait in front of the one extra barrier
-// covers the x loads only: the weight requests stay in flight across it.
-// Tail = Decode3Lines<one of the four group tables, HL>: the same grouped form with H = 1 << HL tiles per wave (LINES, gl_common.h) — a
-// compile-time constant, so the H = 1 forms are the code they were and the shifts of the others fold (profiles/r18/decode_group_lines.log §1).
-template <typename T>
-__device__ __forceinline__ const T& decode3_table(const T& t) { return t; }
-template <typename T, int HL>
-__device__ __forceinline__ const T& decode3_table(const Decode3Lines<T, HL>& w) { return w.t; }
-
-template <typename TailArg>
-struct Decode3TailKind {
-    using Tail = typename Decode3LinesOf<TailArg>::table;
-    static constexpr int hl = Decode3LinesOf<TailArg>::hl;
-    static constexpr bool shared_x = std::is_same<Tail, Decode3GroupTableSX>::value || std::is_same<Tail, Decode3BiasGroupTableSX>::value;
-    static constexpr bool grouped = std::is_same<Tail, Decode3GroupTable>::value || std::is_same<Tail, Decode3BiasGroupTable>::value || shared_x;
-    static constexpr bool biased = std::is_same<Tail, Decode3BiasTail>::value || std::is_same<Tail, Decode3BiasGroupTable>::value ||
-                                   std::is_same<Tail, Decode3BiasGroupTableSX>::value;
+// What a lane holds of one item (a chunk of one virtual wave): its two weight rows, scales, zeros, its 8 bytes of x (per-wave x) ...
+struct Chunk { u32x4 w[R]; u32x2 s, z, xq; };
+// ... or, shared x, its unit as staged in LDS: the pair dwords of its two rows and the sum of its 16 activations
+struct XStage { u32x4 p[R]; float sum; };
+struct NoXStage {  // (what Item holds in its place in the per-wave-x forms)
+    NoXStage() = default;
+    __device__ NoXStage(const XStage&) {}
 };
-
-template <typename Tag, bool NT, typename Tail = unsigned*>
-__global__ __launch_bounds__(1024, (Decode3TailKind<Tail>::grouped ? DECODE3_GROUP_WAVES_PER_SIMD : 1))
-void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
-                            uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
-                            const Tail counters) {
-    using namespace dec3;
-    constexpr bool GROUPED = Decode3TailKind<Tail>::grouped, BIASED = Decode3TailKind<Tail>::biased, SX = Decode3TailKind<Tail>::shared_x;
+// The arithmetic of one item, added to tot[4] (the lane's four columns), and what it reads besides the item: references to the kernel's own
+// variables, as a lambda would capture them.  (A closure, not a function of values: hipcc simplifies a callee before it inlines it, and
+// this shape keeps every kernel's registers, LDS and occupancy what they were — profiles/r19/group_refactor.log.  After a compiler bump
+// rerun scripts/compare_kernel_asm.py --by-body against the previous build: its "resources" line is the check.)
+template <typename Tag, bool SX>
+struct Item {
     using TR = F16Traits<Tag>;
-    constexpr bool SUBN = TR::DT == GEMLITE_DT_FP16;
-    constexpr int WP = SUBN ? 2 : 1;  // 4-bit fields per 16-bit window (Window<Tag, 4>::WP of gemv_wn.hip)
-    constexpr int R = 2, NW = 16, CHUNK = 32, TC = 16, CSTRIDE = NW * CHUNK;
-    constexpr int RED = NW * 4 * TC;
-    __shared__ __attribute__((aligned(16))) float red[(GROUPED && !SX ? DECODE3_GMAX : 1) * RED];  // [NW * 4 DPP rows][16 columns] (grouped: x the layers a block can hold, 64 KiB; shared x: dynamic LDS instead)
+    static constexpr bool SUBN = TR::DT == GEMLITE_DT_FP16;
+    static constexpr int WP = SUBN ? 2 : 1;  // 4-bit fields per 16-bit window (Window<Tag, 4>::WP of gemv_wn.hip)
+    static constexpr float QSCALE = SUBN ? 16777216.0f : 1.0f;
+    std::conditional_t<SX, const XStage&, NoXStage> xs;
+    const uint32_t (&wmask)[WP];   // (15u * 0x00010001u) << (4 * i)
+    const bool &need_s, &need_z;
+    const float &scalar_zero, &bz;  // bz: -1 / 1 / 0 by W_group_mode
+    const bool& b_times_s;
+    float (&tot)[4];
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 3, g = lane >> 2;
-    int tile = blockIdx.x;
-    // grouped: the block's tile group and this wave's slot = (block-local layer, tile of the group); gl_common.h has the geometry
-    [[maybe_unused]] int g_members = 0, g_Y = 1, g_slots = 1, g_tbl = 0, g_tile0 = 0;
-    [[maybe_unused]] constexpr int g_hl = Decode3TailKind<Tail>::hl;
-    [[maybe_unused]] Decode3WaveSplit g_split{0, 0, 16};
-    if constexpr (GROUPED) {
-        g_members = (int)((modes >> 16) & DECODE3_M_MEMBERS);
-        g_Y = (int)(modes >> 24);
-        g_tbl = (int)((modes >> DECODE3_M_TB_SHIFT) & 3u);
-        g_slots = ((g_members - (int)blockIdx.y + g_Y - 1) / g_Y) << g_tbl;
-        // lines: H = 1 << g_hl tiles per wave; the block's slots / H wave-slots are what the waves share, sub-wave h of the lanes takes tile run * H + h
-        g_split = decode3_wave_split(g_slots >> g_hl, wave);
-        // (the span placement alone needs the grid's width: one scalar load of the dispatch's block count, in front of the first request)
-        const bool span = (modes & DECODE3_M_SPAN) != 0u;
-        g_tile0 = decode3_group_first_tile(tile, span ? (int)gridDim.x : 0, 1 << g_tbl, span, (modes & M_PAIR) != 0u);
-        tile = g_tile0 + ((((g_split.layer < 0 ? 0 : g_split.layer) << g_hl) & ((1 << g_tbl) - 1)) + (lane >> (6 - g_hl)));
-    } else if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
-        const int xcd = tile & 7, idx = tile >> 3;
-        tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
-    }
-    const uint32_t n0 = (uint32_t)(tile * TC + c * 4);
-    const int nchunks = (nch_total - wave + NW - 1) / NW;  // chunks wave, wave + NW, ...
-    const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
-    const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
-
-    const uint32_t row0 = (uint32_t)(wave * CHUNK + g * R);  // this lane's first row of chunk 0
-    const uint32_t wo0 = row0 * sw4 + n0 * 4u;
-    const uint32_t xo0 = (uint32_t)(wave * CHUNK) * 16u + (uint32_t)lane * 8u;  // the wave's 512 bytes of x, 8 per lane
-
-    struct Chunk { u32x4 w[R]; u32x2 s, z, xq; };
-    auto load_chunk = [&](Chunk& ck, int chunk) {
-        const uint32_t wo = wo0 + (uint32_t)(chunk * CSTRIDE) * sw4;
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            const u32x4* src = (const u32x4*)(wb + (wo + (uint32_t)i * sw4));
-            ck.w[i] = NT ? __builtin_nontemporal_load(src) : *src;
-        }
-        ck.xq = *(const u32x2*)(xb + (xo0 + (uint32_t)(chunk * CSTRIDE) * 16u));
-        const uint32_t row = row0 + (uint32_t)(chunk * CSTRIDE);
-        const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
-        // (absent metadata is still "loaded" — from the weight buffer, always in bounds — so the loop stays branch-free)
-        ck.s = *(const u32x2*)((need_s ? sp : wb) + (need_s ? mo : 0u));
-        ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
-    };
-
-    // opt-in timeline (GEMLITE_TF_TIMELINE): the mode bit is a preloaded SGPR, so a normal launch never touches `counters` (the one
-    // argument behind the preloaded 14 dwords) and never waits for a kernarg load
-    auto stamp = [&](int i) {
-        if constexpr (!GROUPED && !BIASED) {
-            if (__builtin_expect((modes & M_PROBE) != 0u, 0)) {
-                if (counters && wave == 0 && lane == 0 && blockIdx.x < 1024)
-                    ((unsigned long long*)(counters + MAX_SPLITK_COUNTERS))[blockIdx.x * 4 + i] = __builtin_amdgcn_s_memrealtime();
-            }
-        }
-    };
-    stamp(0);
-    Chunk cur, nxt;
-    if constexpr (!GROUPED) {
-        if (nchunks > 0) load_chunk(cur, 0);
-        if (nchunks > 1) load_chunk(nxt, 1);
-    }
-    stamp(1);
-
-    float tot[4] = {0.f, 0.f, 0.f, 0.f};
-    float scalar_zero = 0.f;  // (grouped: read once per wave, from its own layer)
-    if constexpr (!GROUPED) scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
-    const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
-    const bool b_times_s = w_mode == 3;
-    constexpr float QSCALE = SUBN ? 16777216.0f : 1.0f;
-    uint32_t wmask[WP];
-#pragma unroll
-    for (int i = 0; i < WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
-
-    // shared x: the lane's unit as staged in LDS — the pair dwords of its two rows and the sum of its 16 activations
-    struct XStage { u32x4 p[R]; float sum; } xs;
-    // full = std::true_type: the caller knows need_s && need_z (the grouped loop's common case), the two selects are compiled out
-    auto compute = [&](const Chunk& ck, auto full) {
-        constexpr bool FULL = decltype(full)::value;
+    // FULL: the caller knows need_s && need_z (the grouped loop's common case), the two selects are compiled out
+    template <bool FULL>
+    __device__ void run(const Chunk& ck) const {
         // fp16: the second field of a 16-bit window is read 4 bits up (16 q * 2^-24 as an fp16 subnormal).  Its products go to their
         // own accumulator and the 2^-4 is applied ONCE to the fp32 sum, so nothing is ever rounded: rounds 2-3 (and the first decode3)
         // scaled the matching x pairs by 2^-4 in fp16 instead, which lost mantissa bits for |x| < 2^-10 (1.8e-3 of mean |y|
@@ -226,14 +135,6 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
                 for (int j = 0; j < 4; ++j) {
                     uint32_t h = (ck.w[i][j] >> (4 * WP * win)) & wmask[wi];
                     if constexpr (!SUBN) h |= TR::MAGIC2;
-#if GL_DECODE3_DOT2_ZERO
-                    if constexpr (SUBN && GROUPED) {
-                        if (i == 0 && win == 0) {  // the first product of the accumulator: three operands, no zero to move
-                            asm("v_dot2_f32_f16 %0, %1, %2, 0" : "=v"(acc[wi][j]) : "v"(h), "v"(xr[dd]));
-                            continue;
-                        }
-                    }
-#endif
                     acc[wi][j] = TR::dot2(h, xr[dd], acc[wi][j]);
                 }
             }
@@ -257,322 +158,384 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
             // and a group's outputs must be bit-identical to the single-layer kernel's)
             tot[j] += __builtin_fmaf(b, xsum, a * v);
         }
+    }
+};
+
+// The 4 row sub-groups of every 16-lane DPP row (lane bits 2, 3): two rotations, every lane ends with the row's sum
+__device__ __forceinline__ float row_sum(float v) {
+    v += dpp_movf<0x124>(v);  // row_ror:4
+    v += dpp_movf<0x128>(v);  // row_ror:8
+    return v;
+}
+
+// One wave sums the 64 partial rows of a 4 KiB region and stores the tile's 16 outputs (braw: the bias element of lane < 16)
+// (Red: the region as the kernel names it — the single-layer kernel's own array, a pointer into the group's)
+template <typename Tag, bool BIASED, typename Red>
+__device__ __forceinline__ void finish(const Red& red, uint16_t braw, uint16_t* out, int tile) {
+    using TR = F16Traits<Tag>;
+    const int lane = threadIdx.x & 63;
+    constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
+    const int o = lane & 15, part = lane >> 4;
+    float v = 0.f;
+#pragma unroll
+    for (int r = 0; r < PER; ++r) v += red[(part * PER + r) * TC + o];
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    uint16_t h = TR::from_float(v);
+    // (two roundings, as the matmul launch followed by torch's add has them; a sum of two converted values: nothing to contract)
+    if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));
+    if (lane < 16) out[tile * TC + o] = h;
+}
+
+}  // namespace dec3
+
+template <typename Tag, bool NT, bool BIASED = false>
+__global__ __launch_bounds__(1024, 1)
+void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
+                            uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
+                            const std::conditional_t<BIASED, Decode3BiasTail, unsigned*> counters) {
+    using namespace dec3;
+    __shared__ __attribute__((aligned(16))) float red[RED];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 3, g = lane >> 2;
+    int tile = blockIdx.x;
+    if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
+        const int xcd = tile & 7, idx = tile >> 3;
+        tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
+    }
+    const uint32_t n0 = (uint32_t)(tile * TC + c * 4);
+    const int nchunks = (nch_total - wave + NW - 1) / NW;  // chunks wave, wave + NW, ...
+    const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
+    const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
+
+    const uint32_t row0 = (uint32_t)(wave * CHUNK + g * R);  // this lane's first row of chunk 0
+    const uint32_t wo0 = row0 * sw4 + n0 * 4u;
+    const uint32_t xo0 = (uint32_t)(wave * CHUNK) * 16u + (uint32_t)lane * 8u;  // the wave's 512 bytes of x, 8 per lane
+
+    auto load_chunk = [&](Chunk& ck, int chunk) {
+        const uint32_t wo = wo0 + (uint32_t)(chunk * CSTRIDE) * sw4;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const u32x4* src = (const u32x4*)(wb + (wo + (uint32_t)i * sw4));
+            ck.w[i] = NT ? __builtin_nontemporal_load(src) : *src;
+        }
+        ck.xq = *(const u32x2*)(xb + (xo0 + (uint32_t)(chunk * CSTRIDE) * 16u));
+        const uint32_t row = row0 + (uint32_t)(chunk * CSTRIDE);
+        const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
+        // (absent metadata is still "loaded" — from the weight buffer, always in bounds — so the loop stays branch-free)
+        ck.s = *(const u32x2*)((need_s ? sp : wb) + (need_s ? mo : 0u));
+        ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
     };
-    if constexpr (!GROUPED) {
+
+    // opt-in timeline (GEMLITE_TF_TIMELINE): the mode bit is a preloaded SGPR, so a normal launch never touches `counters` (the one
+    // argument behind the preloaded 14 dwords) and never waits for a kernarg load
+    auto stamp = [&](int i) {
+        if constexpr (!BIASED) {
+            if (__builtin_expect((modes & M_PROBE) != 0u, 0)) {
+                if (counters && wave == 0 && lane == 0 && blockIdx.x < 1024)
+                    ((unsigned long long*)(counters + MAX_SPLITK_COUNTERS))[blockIdx.x * 4 + i] = __builtin_amdgcn_s_memrealtime();
+            }
+        }
+    };
+    stamp(0);
+    Chunk cur, nxt;
+    if (nchunks > 0) load_chunk(cur, 0);
+    if (nchunks > 1) load_chunk(nxt, 1);
+    stamp(1);
+
+    float tot[4] = {0.f, 0.f, 0.f, 0.f};
+    const float scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
+    const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
+    const bool b_times_s = w_mode == 3;
+    uint32_t wmask[Item<Tag, false>::WP];
+#pragma unroll
+    for (int i = 0; i < Item<Tag, false>::WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
+    const Item<Tag, false> item{{}, wmask, need_s, need_z, scalar_zero, bz, b_times_s, tot};
 #pragma unroll 1
-        for (int ch = 0; ch < nchunks; ++ch) {
-            compute(cur, std::false_type{});
-            if (ch + 1 < nchunks) {
-                cur = nxt;
-                if (ch + 2 < nchunks) load_chunk(nxt, ch + 2);
-            }
+    for (int ch = 0; ch < nchunks; ++ch) {
+        item.template run<false>(cur);
+        if (ch + 1 < nchunks) {
+            cur = nxt;
+            if (ch + 2 < nchunks) load_chunk(nxt, ch + 2);
         }
-        stamp(2);
-        uint16_t braw = 0;
-        if constexpr (BIASED) {
-            if (wave == 0 && lane < 16) braw = counters.bias[tile * TC + lane];
-        }
+    }
+    stamp(2);
+    uint16_t braw = 0;
+    if constexpr (BIASED) {
+        if (wave == 0 && lane < 16) braw = counters.bias[tile * TC + lane];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tot[j] = row_sum(tot[j]);
+    if ((lane & 12) == 0) *(f32x4*)(red + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
+    __syncthreads();
+    if (wave == 0) finish<Tag, BIASED>(red, braw, out, tile);
+    stamp(3);
+}
 
-        // ---- the 4 row sub-groups of every 16-lane DPP row (lane bits 2, 3): two rotations, every lane ends with the row's sum --
+// One block holds the layers y, y + Y, ... of its 16-column tile — LB of them, ALL in flight at once: decode3_wave_split()
+// (gl_common.h) gives every layer 16 / LB waves, and a wave takes the place of a contiguous run of the single-layer kernel's waves
+// ("virtual waves": virtual wave v is the chunks v, v + 16, ... below nch_total, each with the rows and x bytes the single-layer
+// wave v reads).  Nothing orders the waves of a block before the one barrier at the end, so a CU's waves wait for memory and do
+// arithmetic at different times.  A wave's items — its virtual waves in ascending order, each one's chunks in ascending order — are
+// a flat list of known length: gvw::ring2_run (gl_async.h) with five counted asm requests per item (w, w, x, s, z).  Every base is
+// a uniform SGPR pair moved by scalar arithmetic, every per-lane offset is set up once: the loop holds no vector address
+// arithmetic and no select (the shared-x forms: four requests (w, w, s, z) and three LDS reads per item, whose two lane addresses
+// move by one vector add each).  Bit-exact: `tot` accumulates a virtual wave's chunks in ascending order; at its end the two row_ror
+// sums, the partial row v * 4 + (lane >> 4) of the LAYER'S OWN 4 KB of LDS, `tot` back to zero (a virtual wave without a chunk
+// writes zeros: K < 4096); after the barrier waves 0 .. LB - 1 each run the single-layer epilogue on one layer's region.
+// With tile groups (TB = 1 << tbl tiles per block) the block's LB * TB slots stand where the layers stand in this description:
+// slot s is layer s / TB on tile s % TB of the block's group, with its own waves, virtual waves and 4 KB of LDS.
+// With lines (H = 1 << HL tiles per wave) the waves share the block's slots / H wave-slots instead; a
+// wave's items are (virtual wave, pass, chunk) ascending, H times as many on a 1 / H share of the waves, and sub-wave h of the
+// lanes fills slot + h.  Per lane an item is the same item(); `tot` of a (virtual wave, pass) adds its chunks in ascending
+// order; the four row pairs 4 r .. 4 r + 3 still meet in one 16-lane DPP row (r = p * 4 / H + the row inside the sub-wave) and
+// land in partial row v * 4 + r of the slot's region: bit-exact under every H.  What depended on g depends on the pass through
+// SCALAR adds to the uniform bases (weights, x, metadata row) and one constant inside the shared-x LDS offsets.
+// Default-policy weight loads only, whatever the members' own launches use: the two 16-column tiles of a 128-byte line are read by two
+// different waves — with one tile per block (TB = 1) in two blocks on two CUs of one XCD, which meet in that XCD's L2 only; with tile
+// groups (TB = 2, 4) by neighbouring waves of one block — and nothing keeps the two in step: the partner asks for its half some time
+// later, and a non-temporal line has left the L2 by then (11.6 MB fetched per layer against 9.5; profiles/r13/decode_group_waves.log §2).
+template <typename Tag, bool BIASED, bool SX, int HL>
+__global__ __launch_bounds__(1024, DECODE3_GROUP_WAVES_PER_SIMD)
+void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
+                                  uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
+                                  const GroupTable<BIASED> tab) {
+    using namespace dec3;
+    using TR = F16Traits<Tag>;
+    constexpr int hl = HL, H = 1 << hl;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 3;
+    // the block's tile group and this wave's slot = (block-local layer, tile of the group); gl_common.h has the geometry
+    const int members = (int)((modes >> 16) & DECODE3_M_MEMBERS), Y = (int)(modes >> 24), y = (int)blockIdx.y;
+    const int tbl = (int)((modes >> DECODE3_M_TB_SHIFT) & 3u);
+    const int slots = ((members - y + Y - 1) / Y) << tbl;
+    // lines: the block's slots / H wave-slots are what the waves share, sub-wave h of the lanes takes tile run * H + h
+    const Decode3WaveSplit split = decode3_wave_split(slots >> hl, wave);
+    // (the span placement alone needs the grid's width: one scalar load of the dispatch's block count, in front of the first request)
+    const bool span = (modes & DECODE3_M_SPAN) != 0u;
+    const int tile0 = decode3_group_first_tile((int)blockIdx.x, span ? (int)gridDim.x : 0, 1 << tbl, span, (modes & M_PAIR) != 0u);
+    const int tile = tile0 + ((((split.layer < 0 ? 0 : split.layer) << hl) & ((1 << tbl) - 1)) + (lane >> (6 - hl)));
+    const uint32_t n0 = (uint32_t)(tile * TC + c * 4);
+    const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
+    const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
+    float tot[4] = {0.f, 0.f, 0.f, 0.f};
+    float scalar_zero = 0.f;  // (read once per wave, from its own layer)
+    const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
+    const bool b_times_s = w_mode == 3;
+    uint32_t wmask[Item<Tag, SX>::WP];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float v = tot[j];
-            v += dpp_movf<0x124>(v);  // row_ror:4
-            v += dpp_movf<0x128>(v);  // row_ror:8
-            tot[j] = v;
-        }
-        if ((lane & 12) == 0) *(f32x4*)(red + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
-        __syncthreads();
-        if (wave == 0) {
-            constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
-            const int o = lane & 15, part = lane >> 4;
-            float v = 0.f;
-#pragma unroll
-            for (int r = 0; r < PER; ++r) v += red[(part * PER + r) * TC + o];
-            v += __shfl_xor(v, 16);
-            v += __shfl_xor(v, 32);
-            uint16_t h = TR::from_float(v);
-            // (two roundings, as the matmul launch followed by torch's add has them; a sum of two converted values: nothing to contract)
-            if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));
-            if (lane < 16) out[tile * TC + o] = h;
-        }
-        stamp(3);
+    for (int i = 0; i < Item<Tag, SX>::WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
+    XStage xs;
+    const Item<Tag, SX> item{xs, wmask, need_s, need_z, scalar_zero, bz, b_times_s, tot};
+
+    // (slot: the wave's first of H; lq: the lane inside its sub-wave, gl its row pair of a pass)
+    const int lq = lane & ((64 >> hl) - 1), gl = lq >> 2;
+    const int slot = (split.layer < 0 ? 0 : split.layer) << hl, li = slot >> tbl, v0 = split.v0, v1 = split.v1;
+    // this wave's layer: the preloaded scalars (layer 0) or the by-value table, scalar loads either way, once per wave
+    const int L = y + li * Y;
+    const char *w_ = wb, *x_ = xb, *s_ = sp, *z_ = zp;
+    if (L > 0) {
+        const GroupMember& m = tab.m[L - 1];
+        w_ = m.w; x_ = m.x; s_ = m.s; z_ = m.z;
+    }
+    // (a scalar load, read ahead of the first request: a load hipcc tracks inside the counted ring would bring the full drain back)
+    if (modes & M_ZSCALAR) scalar_zero = (float)((const int32_t*)z_)[0];
+    // per-lane byte offsets, fixed for the whole launch.  Metadata row of chunk gc, row pair g: ((gc * 32 + 2 g) * 8) >> gs_shift
+    // = (gc << 8 >> gs_shift) + (16 g >> gs_shift) for groups up to 256, gc >> (gs_shift - 8) for larger ones (16 g < 256).
+    // In pass p the lane's row pair is g = p * 16 / H + gl: the lane keeps gl's share, the pass adds whole multiples to the uniform
+    // bases — 32 / H weight rows, 512 / H bytes of x, (256 / H p) >> gs_shift metadata rows (16 g >> gs_shift splits exactly into the
+    // pass's part and the lane's: 256 / H p is a multiple of the group, or the 16 gl < 256 / H behind it stay inside its group)
+    const uint32_t vw0 = (uint32_t)(gl * R) * sw4 + n0 * 4u, vw1 = vw0 + sw4, vx = (uint32_t)lq * 8u;
+    const uint32_t vm = (gs_shift < 8 ? (uint32_t)(gl * R * 8) >> gs_shift : 0u) * mstride2 + n0 * 2u;
+    const uint32_t pass_w = (uint32_t)(CHUNK >> hl) * sw4, pass_x = (uint32_t)(CHUNK * 16) >> hl;
+    const int pass_ms = gs_shift < 8 ? gs_shift : 31;  // (groups of 256 and more: no metadata row inside a chunk)
+    // (absent metadata is still requested — the first bytes of the weight buffer — so every item is five requests)
+    const uint32_t vs = need_s ? vm : 0u, vz = need_z ? vm : 0u, ms_s = need_s ? mstride2 : 0u, ms_z = need_z ? mstride2 : 0u;
+    const char *sb = need_s ? s_ : w_, *zb = need_z ? z_ : w_;
+    const int shl = gs_shift < 8 ? 8 - gs_shift : 0, shr = gs_shift > 8 ? gs_shift - 8 : 0;
+    const uint32_t chunk_w = (uint32_t)CHUNK * sw4;
+    const int nv = v1 - v0, rem = (nch_total & (NW - 1)) - v0;
+    const int n = ((nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem))) << hl;  // items of this wave: H passes per chunk (0: an idle wave, or K too short)
+    // the partial rows: [slots the block can hold][RED], 64 KiB.  Shared x, dynamic LDS: [partial rows][units x 8 pair dwords][units x sum],
+    // units = 16 per chunk (gl_common.h: decode3_shared_x_lds_bytes)
+    float* redg;
+    uint32_t* xpairs = nullptr;
+    float* xsums = nullptr;
+    const int units = nch_total * 16;
+    if constexpr (SX) {
+        extern __shared__ __attribute__((aligned(16))) float d3_lds[];
+        redg = d3_lds;
+        xpairs = (uint32_t*)(d3_lds + DECODE3_GMAX * RED);
+        xsums = (float*)(xpairs + units * 8);
     } else {
-        // One block holds the layers y, y + Y, ... of its 16-column tile — LB of them, ALL in flight at once: decode3_wave_split()
-        // (gl_common.h) gives every layer 16 / LB waves, and a wave takes the place of a contiguous run of the single-layer kernel's waves
-        // ("virtual waves": virtual wave v is the chunks v, v + 16, ... below nch_total, each with the rows and x bytes the single-layer
-        // wave v reads).  Nothing orders the waves of a block before the one barrier at the end, so a CU's waves wait for memory and do
-        // arithmetic at different times.  A wave's items — its virtual waves in ascending order, each one's chunks in ascending order — are
-        // a flat list of known length: gvw::ring2_run (gl_async.h) with five counted asm requests per item (w, w, x, s, z).  Every base is
-        // a uniform SGPR pair moved by scalar arithmetic, every per-lane offset is set up once: the loop holds no vector address
-        // arithmetic and no select (the shared-x forms: four requests (w, w, s, z) and three LDS reads per item, whose two lane addresses
-        // move by one vector add each).  Bit-exact: `tot` accumulates a virtual wave's chunks in ascending order; at its end the two row_ror
-        // sums, the partial row v * 4 + (lane >> 4) of the LAYER'S OWN 4 KB of LDS, `tot` back to zero (a virtual wave without a chunk
-        // writes zeros: K < 4096); after the barrier waves 0 .. LB - 1 each run the single-layer epilogue on one layer's region.
-        // With tile groups (TB = 1 << g_tbl tiles per block) the block's LB * TB slots stand where the layers stand in this description:
-        // slot s is layer s / TB on tile s % TB of the block's group, with its own waves, virtual waves and 4 KB of LDS.
-        // With lines (H = 1 << hl tiles per wave, a compile-time constant) the waves share the block's slots / H wave-slots instead; a
-        // wave's items are (virtual wave, pass, chunk) ascending, H times as many on a 1 / H share of the waves, and sub-wave h of the
-        // lanes fills slot + h.  Per lane an item is the same compute(); `tot` of a (virtual wave, pass) adds its chunks in ascending
-        // order; the four row pairs 4 r .. 4 r + 3 still meet in one 16-lane DPP row (r = p * 4 / H + the row inside the sub-wave) and
-        // land in partial row v * 4 + r of the slot's region: bit-exact under every H.  What depended on g depends on the pass through
-        // SCALAR adds to the uniform bases (weights, x, metadata row) and one constant inside the shared-x LDS offsets.
-        const int Y = g_Y, y = (int)blockIdx.y, slots = g_slots;
-        const Decode3WaveSplit split = g_split;
-        // (slot: the wave's first of H = 1 << hl; lq: the lane inside its sub-wave, gl its row pair of a pass)
-        constexpr int hl = g_hl, H = 1 << hl;
-        const int lq = lane & ((64 >> hl) - 1), gl = lq >> 2;
-        const int slot = (split.layer < 0 ? 0 : split.layer) << hl, li = slot >> g_tbl, v0 = split.v0, v1 = split.v1;
-        // this wave's layer: the preloaded scalars (layer 0) or the by-value table, scalar loads either way, once per wave
-        const int L = y + li * Y;
-        const char *w_ = wb, *x_ = xb, *s_ = sp, *z_ = zp;
-        if (L > 0) {
-            const Decode3Member& m = decode3_table(counters).m[L - 1];
-            w_ = m.w; x_ = m.x; s_ = m.s; z_ = m.z;
-        }
-        // (a scalar load, read ahead of the first request: a load hipcc tracks inside the counted ring would bring the full drain back)
-        if (modes & M_ZSCALAR) scalar_zero = (float)((const int32_t*)z_)[0];
-        // per-lane byte offsets, fixed for the whole launch.  Metadata row of chunk gc, row pair g: ((gc * 32 + 2 g) * 8) >> gs_shift
-        // = (gc << 8 >> gs_shift) + (16 g >> gs_shift) for groups up to 256, gc >> (gs_shift - 8) for larger ones (16 g < 256).
-        // In pass p the lane's row pair is g = p * 16 / H + gl: the lane keeps gl's share, the pass adds whole multiples to the uniform
-        // bases — 32 / H weight rows, 512 / H bytes of x, (256 / H p) >> gs_shift metadata rows (16 g >> gs_shift splits exactly into the
-        // pass's part and the lane's: 256 / H p is a multiple of the group, or the 16 gl < 256 / H behind it stay inside its group)
-        const uint32_t vw0 = (uint32_t)(gl * R) * sw4 + n0 * 4u, vw1 = vw0 + sw4, vx = (uint32_t)lq * 8u;
-        const uint32_t vm = (gs_shift < 8 ? (uint32_t)(gl * R * 8) >> gs_shift : 0u) * mstride2 + n0 * 2u;
-        const uint32_t pass_w = (uint32_t)(CHUNK >> hl) * sw4, pass_x = (uint32_t)(CHUNK * 16) >> hl;
-        const int pass_ms = gs_shift < 8 ? gs_shift : 31;  // (groups of 256 and more: no metadata row inside a chunk)
-        // (absent metadata is still requested — the first bytes of the weight buffer — so every item is five requests)
-        const uint32_t vs = need_s ? vm : 0u, vz = need_z ? vm : 0u, ms_s = need_s ? mstride2 : 0u, ms_z = need_z ? mstride2 : 0u;
-        const char *sb = need_s ? s_ : w_, *zb = need_z ? z_ : w_;
-        const int shl = gs_shift < 8 ? 8 - gs_shift : 0, shr = gs_shift > 8 ? gs_shift - 8 : 0;
-        const uint32_t chunk_w = (uint32_t)CHUNK * sw4;
-        const int nv = v1 - v0, rem = (nch_total & (NW - 1)) - v0;
-        const int n = ((nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem))) << hl;  // items of this wave: H passes per chunk (0: an idle wave, or K too short)
-        // shared x: [partial rows, 64 KiB][units x 8 pair dwords][units x sum], units = 16 per chunk (gl_common.h: decode3_shared_x_lds_bytes)
-        float* redg;
-        uint32_t* xpairs = nullptr;
-        float* xsums = nullptr;
-        const int units = nch_total * 16;
-        if constexpr (SX) {
-            extern __shared__ __attribute__((aligned(16))) float d3_lds[];
-            redg = d3_lds;
-            xpairs = (uint32_t*)(d3_lds + DECODE3_GMAX * RED);
-            xsums = (float*)(xpairs + units * 8);
-        } else {
-            redg = red;
-        }
-        // the lane's place in a partial row of ITS slot (sub-wave h: slot + h); row v * 4 + r with r = p * 4 / H + (DPP row inside the sub-wave)
-        float* rd = redg + ((slot + (lane >> (6 - hl))) * RED + (lq >> 4) * TC + c * 4);
+        __shared__ __attribute__((aligned(16))) float red[DECODE3_GMAX * RED];
+        redg = red;
+    }
+    // the lane's place in a partial row of ITS slot (sub-wave h: slot + h); row v * 4 + r with r = p * 4 / H + (DPP row inside the sub-wave)
+    float* rd = redg + ((slot + (lane >> (6 - hl))) * RED + (lq >> 4) * TC + c * 4);
 
-        constexpr int NLC = SX ? 4 : 5;
-        int rv = v0, rp = 0, rgc = v0;  // request cursor: virtual wave, pass, chunk
-        auto request = [&](Chunk& ck, int ri) __attribute__((always_inline)) {
-#if GL_DECODE3_ABLATION == 2
-            const int keep = rgc, keep_p = rp;
-            if (ri >= 2) { rgc = v0; rp = 0; }
-#endif
-            const char* wq = w_ + ((uint32_t)rgc * chunk_w + (uint32_t)rp * pass_w);
-            gvw::gld128<NT>(ck.w[0], wq, vw0);
-            gvw::gld128<NT>(ck.w[1], wq, vw1);
-            if constexpr (!SX) gvw::gld64(ck.xq, x_ + ((uint32_t)rgc * (uint32_t)(CHUNK * 16) + (uint32_t)rp * pass_x), vx);
-            const uint32_t grp = (((uint32_t)rgc << shl) >> shr) + (((uint32_t)rp << (8 - hl)) >> pass_ms);
-            gvw::gld64(ck.s, sb + grp * ms_s, vs);
-            gvw::gld64(ck.z, zb + grp * ms_z, vz);
-#if GL_DECODE3_ABLATION == 2
-            rgc = keep;
-            rp = keep_p;
-#endif
-            rgc += NW;
-            if (rgc >= nch_total) {  // the next pass over this virtual wave, or the next virtual wave
-                if (++rp == H) { rp = 0; ++rv; }
-                rgc = rv;
-            }
-        };
-        auto tie_chunk = [&](Chunk& ck) __attribute__((always_inline)) {
-            gvw::tie(ck.w[0]);
-            gvw::tie(ck.w[1]);
-            if constexpr (!SX) gvw::tie(ck.xq);
-            gvw::tie(ck.s);
-            gvw::tie(ck.z);
-        };
-        // a virtual wave's end, the single-layer code: DPP row sums, the partial row to the layer's LDS region
-        auto flush = [&](int v, int p) {
+    constexpr int NLC = SX ? 4 : 5;
+    int rv = v0, rp = 0, rgc = v0;  // request cursor: virtual wave, pass, chunk
+    auto request = [&](Chunk& ck, int) __attribute__((always_inline)) {
+        const char* wq = w_ + ((uint32_t)rgc * chunk_w + (uint32_t)rp * pass_w);
+        gvw::gld128<false>(ck.w[0], wq, vw0);
+        gvw::gld128<false>(ck.w[1], wq, vw1);
+        if constexpr (!SX) gvw::gld64(ck.xq, x_ + ((uint32_t)rgc * (uint32_t)(CHUNK * 16) + (uint32_t)rp * pass_x), vx);
+        const uint32_t grp = (((uint32_t)rgc << shl) >> shr) + (((uint32_t)rp << (8 - hl)) >> pass_ms);
+        gvw::gld64(ck.s, sb + grp * ms_s, vs);
+        gvw::gld64(ck.z, zb + grp * ms_z, vz);
+        rgc += NW;
+        if (rgc >= nch_total) {  // the next pass over this virtual wave, or the next virtual wave
+            if (++rp == H) { rp = 0; ++rv; }
+            rgc = rv;
+        }
+    };
+    auto tie_chunk = [&](Chunk& ck) __attribute__((always_inline)) {
+        gvw::tie(ck.w[0]);
+        gvw::tie(ck.w[1]);
+        if constexpr (!SX) gvw::tie(ck.xq);
+        gvw::tie(ck.s);
+        gvw::tie(ck.z);
+    };
+    // a virtual wave's end, the single-layer code: DPP row sums, the partial row to the layer's LDS region
+    auto flush = [&](int v, int p) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float t = tot[j];
-                t += dpp_movf<0x124>(t);  // row_ror:4
-                t += dpp_movf<0x128>(t);  // row_ror:8
-                tot[j] = t;
-            }
-            if ((lane & 12) == 0) *(f32x4*)(rd + (v * 4 + (p << (2 - hl))) * TC) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
+        for (int j = 0; j < 4; ++j) tot[j] = row_sum(tot[j]);
+        if ((lane & 12) == 0) *(f32x4*)(rd + (v * 4 + (p << (2 - hl))) * TC) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) tot[j] = 0.f;
-        };
-        int cv = v0, cp = 0, cgc = v0;  // compute cursor
-        // (the first two requests belong to the variant that consumes them: requested ahead of the branch, their registers — still in
-        // flight — were COPIED into each variant's own set in front of its loop)
-        // shared x, staging: unit u's 32 bytes of x become its eight pair dwords and its sum with the instructions compute() runs on them
-        // (rows 2 u and 2 u + 1: dwords 0..3 and 4..7; the sum chain from 0.f over row 2 u's pairs, then row 2 u + 1's)
-        auto stage_unit = [&](int u, const u32x4& lo, const u32x4& hi) __attribute__((always_inline)) {
-            u32x4 pr[R];
-            float xsum = 0.f;
+        for (int j = 0; j < 4; ++j) tot[j] = 0.f;
+    };
+    int cv = v0, cp = 0, cgc = v0;  // compute cursor
+    // (the first two requests belong to the variant that consumes them: requested ahead of the branch, their registers — still in
+    // flight — were COPIED into each variant's own set in front of its loop)
+    // shared x, staging: unit u's 32 bytes of x become its eight pair dwords and its sum with the instructions item() runs on them
+    // (rows 2 u and 2 u + 1: dwords 0..3 and 4..7; the sum chain from 0.f over row 2 u's pairs, then row 2 u + 1's)
+    auto stage_unit = [&](int u, const u32x4& lo, const u32x4& hi) __attribute__((always_inline)) {
+        u32x4 pr[R];
+        float xsum = 0.f;
 #pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const u32x4& d = i ? hi : lo;
-                pr[i][0] = __builtin_amdgcn_perm(d[2], d[0], 0x05040100u);
-                pr[i][1] = __builtin_amdgcn_perm(d[2], d[0], 0x07060302u);
-                pr[i][2] = __builtin_amdgcn_perm(d[3], d[1], 0x05040100u);
-                pr[i][3] = __builtin_amdgcn_perm(d[3], d[1], 0x07060302u);
+        for (int i = 0; i < R; ++i) {
+            const u32x4& d = i ? hi : lo;
+            pr[i][0] = __builtin_amdgcn_perm(d[2], d[0], 0x05040100u);
+            pr[i][1] = __builtin_amdgcn_perm(d[2], d[0], 0x07060302u);
+            pr[i][2] = __builtin_amdgcn_perm(d[3], d[1], 0x05040100u);
+            pr[i][3] = __builtin_amdgcn_perm(d[3], d[1], 0x07060302u);
 #pragma unroll
-                for (int dd = 0; dd < 4; ++dd) xsum = TR::dot2(pr[i][dd], TR::ONES2, xsum);
+            for (int dd = 0; dd < 4; ++dd) xsum = TR::dot2(pr[i][dd], TR::ONES2, xsum);
+        }
+        if (u < units) {
+            *(u32x4*)(xpairs + u * 8) = pr[0];
+            *(u32x4*)(xpairs + u * 8 + 4) = pr[1];
+            xsums[u] = xsum;
+        }
+    };
+    // (a lane past the last unit loads the last unit's bytes and writes nothing: units is a multiple of 16, not of 64)
+    auto stage_off = [&](int u) { return (uint32_t)(u < units ? u : units - 1) * 32u; };
+    constexpr int STRIPS = (int)((DECODE3_SHARED_X_MAX_UNITS + 1023) / 1024);  // staging trips of the 1024 threads: what fits in LDS
+    // the lane's unit of chunk 0, pass 0; chunk gc is 128 dwords of pairs and 16 sums further, pass p 16 / H units: one vector add each per item
+    const uint32_t* xp_lane = xpairs + gl * 8;
+    const float* xs_lane = xsums + gl;
+    auto run = [&](auto full) {
+        Chunk A, B;
+        if constexpr (SX) {
+            // thread u loads the units u, u + 1024, ... (all trips' loads first), then the wave's first two items go out, then ONE wait
+            // for the x loads alone: they are older than every item request
+            u32x4 lo[STRIPS], hi[STRIPS];
+#pragma unroll
+            for (int t = 0; t < STRIPS; ++t) {
+                if (wave * 64 + t * 1024 < units) {
+                    const uint32_t so = stage_off(tid + t * 1024);
+                    gvw::gld128<false>(lo[t], xb, so);
+                    gvw::gld128<false>(hi[t], xb, so + 16u);
+                }
             }
-            if (u < units) {
-                *(u32x4*)(xpairs + u * 8) = pr[0];
-                *(u32x4*)(xpairs + u * 8 + 4) = pr[1];
-                xsums[u] = xsum;
-            }
-        };
-        // (a lane past the last unit loads the last unit's bytes and writes nothing: units is a multiple of 16, not of 64)
-        auto stage_off = [&](int u) { return (uint32_t)(u < units ? u : units - 1) * 32u; };
-        constexpr int STRIPS = (int)((DECODE3_SHARED_X_MAX_UNITS + 1023) / 1024);  // staging trips of the 1024 threads: what fits in LDS
-        // the lane's unit of chunk 0, pass 0; chunk gc is 128 dwords of pairs and 16 sums further, pass p 16 / H units: one vector add each per item
-        const uint32_t* xp_lane = xpairs + gl * 8;
-        const float* xs_lane = xsums + gl;
-        auto run = [&](auto full) {
-            Chunk A, B;
-            if constexpr (SX) {
-                // thread u loads the units u, u + 1024, ... (all trips' loads first), then the wave's first two items go out, then ONE wait
-                // for the x loads alone: they are older than every item request
-                u32x4 lo[STRIPS], hi[STRIPS];
+            if (n > 0) request(A, 0);
+            if (n > 1) request(B, 1);
+            if (wave * 64 < units) {
+                if (n > 1) gvw::wait_vm<2 * NLC>(); else if (n > 0) gvw::wait_vm<NLC>(); else gvw::wait_vm<0>();
 #pragma unroll
                 for (int t = 0; t < STRIPS; ++t) {
                     if (wave * 64 + t * 1024 < units) {
-                        const uint32_t so = stage_off(tid + t * 1024);
-                        gvw::gld128<false>(lo[t], xb, so);
-                        gvw::gld128<false>(hi[t], xb, so + 16u);
+                        gvw::tie(lo[t]);
+                        gvw::tie(hi[t]);
+                        stage_unit(tid + t * 1024, lo[t], hi[t]);
                     }
                 }
-                if (n > 0) request(A, 0);
-                if (n > 1) request(B, 1);
-                if (wave * 64 < units) {
-                    if (n > 1) gvw::wait_vm<2 * NLC>(); else if (n > 0) gvw::wait_vm<NLC>(); else gvw::wait_vm<0>();
-#pragma unroll
-                    for (int t = 0; t < STRIPS; ++t) {
-                        if (wave * 64 + t * 1024 < units) {
-                            gvw::tie(lo[t]);
-                            gvw::tie(hi[t]);
-                            stage_unit(tid + t * 1024, lo[t], hi[t]);
-                        }
-                    }
-                }
-                __syncthreads();
-            } else {
-                if (n > 0) request(A, 0);
-                if (n > 1) request(B, 1);
             }
-            gvw::ring2_run_pre<NLC>(n, A, B, request, tie_chunk, [&](int) __attribute__((always_inline)) {
-                if constexpr (SX) {
-                    const int unit = cgc * 16 + (cp << (4 - hl));
-                    const uint32_t* xp = xp_lane + unit * 8;
-                    xs.p[0] = *(const u32x4*)xp;
-                    xs.p[1] = *(const u32x4*)(xp + 4);
-                    xs.sum = xs_lane[unit];
-                }
-            }, [&](const Chunk& ck, int) __attribute__((always_inline)) {
-#if GL_DECODE3_ABLATION == 1
-                uint32_t acc = ck.s[0] ^ ck.s[1] ^ ck.z[0] ^ ck.z[1];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc ^= ck.w[0][j] ^ ck.w[1][j];
-                if constexpr (SX) acc ^= xs.p[0][0] ^ xs.p[1][3] ^ __builtin_bit_cast(uint32_t, xs.sum); else acc ^= ck.xq[0] ^ ck.xq[1];
-                tot[0] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, tot[0]) ^ acc);
-#else
-                compute(ck, full);
-#endif
-                cgc += NW;
-                if (cgc >= nch_total) {
-                    flush(cv, cp);
-                    if (++cp == H) { cp = 0; ++cv; }
-                    cgc = cv;
-                }
-            });
-        };
-        // (scales and zeros both present — every A16W4 layer quantised with a zero tensor: the selects are compiled out)
-        if (need_s && need_z) run(std::true_type{}); else run(std::false_type{});
-        if (split.layer >= 0) {
+            __syncthreads();
+        } else {
+            if (n > 0) request(A, 0);
+            if (n > 1) request(B, 1);
+        }
+        gvw::ring2_run_pre<NLC>(n, A, B, request, tie_chunk, [&](int) __attribute__((always_inline)) {
+            if constexpr (SX) {
+                const int unit = cgc * 16 + (cp << (4 - hl));
+                const uint32_t* xp = xp_lane + unit * 8;
+                xs.p[0] = *(const u32x4*)xp;
+                xs.p[1] = *(const u32x4*)(xp + 4);
+                xs.sum = xs_lane[unit];
+            }
+        }, [&](const Chunk& ck, int) __attribute__((always_inline)) {
+            item.template run<decltype(full)::value>(ck);
+            cgc += NW;
+            if (cgc >= nch_total) {
+                flush(cv, cp);
+                if (++cp == H) { cp = 0; ++cv; }
+                cgc = cv;
+            }
+        });
+    };
+    // (scales and zeros both present — every A16W4 layer quantised with a zero tensor: the selects are compiled out)
+    if (need_s && need_z) run(std::true_type{}); else run(std::false_type{});
+    if (split.layer >= 0) {
 #pragma unroll 1
-            for (int v = cv; v < v1; ++v)  // virtual waves without a chunk: every pass writes its rows (cp is 0 here: a virtual wave has all its passes or none)
-                for (int p = 0; p < H; ++p) flush(v, p);
-        }
+        for (int v = cv; v < v1; ++v)  // virtual waves without a chunk: every pass writes its rows (cp is 0 here: a virtual wave has all its passes or none)
+            for (int p = 0; p < H; ++p) flush(v, p);
+    }
 
-        // waves 0 .. slots - 1 finish one slot each (layer wave / TB on tile wave % TB); they ask for its bias element in front of the barrier
-        const bool fin = wave < slots;
-        const int ftile = g_tile0 + (wave & ((1 << g_tbl) - 1));
-        uint16_t* o_ = out;
-        uint16_t braw = 0;
-        if (fin) {
-            const int Lf = y + (wave >> g_tbl) * Y;
-            if (Lf > 0) o_ = decode3_table(counters).m[Lf - 1].out;
-            if constexpr (BIASED) {
-                if (lane < 16) braw = decode3_table(counters).bias[Lf][ftile * TC + lane];
-            }
-        }
-        __syncthreads();
-        if (fin) {
-            const float* rf = redg + wave * RED;
-            constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
-            const int o = lane & 15, part = lane >> 4;
-            float v = 0.f;
-#pragma unroll
-            for (int r = 0; r < PER; ++r) v += rf[(part * PER + r) * TC + o];
-            v += __shfl_xor(v, 16);
-            v += __shfl_xor(v, 32);
-            uint16_t h = TR::from_float(v);
-            if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));  // (as in the single-layer form)
-            if (lane < 16) o_[ftile * TC + o] = h;
+    // waves 0 .. slots - 1 finish one slot each (layer wave / TB on tile wave % TB); they ask for its bias element in front of the barrier
+    const bool fin = wave < slots;
+    const int ftile = tile0 + (wave & ((1 << tbl) - 1));
+    uint16_t* o_ = out;
+    uint16_t braw = 0;
+    if (fin) {
+        const int Lf = y + (wave >> tbl) * Y;
+        if (Lf > 0) o_ = tab.m[Lf - 1].out;
+        if constexpr (BIASED) {
+            if (lane < 16) braw = tab.bias[Lf][ftile * TC + lane];
         }
     }
+    __syncthreads();
+    if (fin) finish<Tag, BIASED>(redg + wave * RED, braw, o_, ftile);
 }
 
 // tag: 0 fp16 | 1 bf16
 const void* gemv_w4_decode3_fn(int tag, bool nt) {
-    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, unsigned*);
-    kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true> : gemv_w4_decode3_kernel<half_tag, false>)
-                     : (nt ? gemv_w4_decode3_kernel<bf16_tag, true> : gemv_w4_decode3_kernel<bf16_tag, false>);
-    return (const void*)k;
+    return tag == 0 ? (nt ? (const void*)gemv_w4_decode3_kernel<half_tag, true> : (const void*)gemv_w4_decode3_kernel<half_tag, false>)
+                    : (nt ? (const void*)gemv_w4_decode3_kernel<bf16_tag, true> : (const void*)gemv_w4_decode3_kernel<bf16_tag, false>);
 }
-
-// The grouped forms exist with default-policy weight loads only (NT = false), whatever the members' own launches use: the two 16-column
-// tiles of a 128-byte line are read by two different waves — with one tile per block (TB = 1) in two blocks on two CUs of one XCD, which
-// meet in that XCD's L2 only; with tile groups (TB = 2, 4) by neighbouring waves of one block — and nothing keeps the two in step: the
-// partner asks for its half some time later, and a non-temporal line has left the L2 by then (11.6 MB fetched per layer against 9.5;
-// profiles/r13/decode_group_waves.log §2).
-// (h: the tiles per wave, 1 / 2 / 4; the forms of H = 1 keep the table itself as their Tail, and with it their names)
-template <typename Table, int HL>
-static const void* decode3_group_fn_of(int tag) {
-    using Tail = typename std::conditional<HL == 0, Table, Decode3Lines<Table, HL>>::type;
-    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Tail);
-    kfn k = tag == 0 ? gemv_w4_decode3_kernel<half_tag, false, Tail> : gemv_w4_decode3_kernel<bf16_tag, false, Tail>;
-    return (const void*)k;
-}
-template <typename Table>
-static const void* decode3_group_fn_of(int tag, int h) {
-    return h == 4 ? decode3_group_fn_of<Table, 2>(tag) : (h == 2 ? decode3_group_fn_of<Table, 1>(tag) : decode3_group_fn_of<Table, 0>(tag));
-}
-
-const void* gemv_w4_decode3_group_fn(int tag, int h) { return decode3_group_fn_of<Decode3GroupTable>(tag, h); }
-
-// The shared-x grouped forms (dynamic LDS: decode3_shared_x_lds_bytes), unbiased / biased
-const void* gemv_w4_decode3_group_sx_fn(int tag, bool biased, int h) {
-    return biased ? decode3_group_fn_of<Decode3BiasGroupTableSX>(tag, h) : decode3_group_fn_of<Decode3GroupTableSX>(tag, h);
-}
-
 const void* gemv_w4_decode3_bias_fn(int tag, bool nt) {
-    typedef void (*kfn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, const Decode3BiasTail);
-    kfn k = tag == 0 ? (nt ? gemv_w4_decode3_kernel<half_tag, true, Decode3BiasTail> : gemv_w4_decode3_kernel<half_tag, false, Decode3BiasTail>)
-                     : (nt ? gemv_w4_decode3_kernel<bf16_tag, true, Decode3BiasTail> : gemv_w4_decode3_kernel<bf16_tag, false, Decode3BiasTail>);
-    return (const void*)k;
+    return tag == 0 ? (nt ? (const void*)gemv_w4_decode3_kernel<half_tag, true, true> : (const void*)gemv_w4_decode3_kernel<half_tag, false, true>)
+                    : (nt ? (const void*)gemv_w4_decode3_kernel<bf16_tag, true, true> : (const void*)gemv_w4_decode3_kernel<bf16_tag, false, true>);
 }
 
-const void* gemv_w4_decode3_bias_group_fn(int tag, int h) { return decode3_group_fn_of<Decode3BiasGroupTable>(tag, h); }
+// Every grouped form (h: the tiles per wave, 1 / 2 / 4; anything else: 1)
+template <typename Tag, bool BIASED, bool SX>
+static const void* decode3_group_pick(int h) {
+    return h == 4 ? (const void*)gemv_w4_decode3_group_kernel<Tag, BIASED, SX, 2>
+                  : (h == 2 ? (const void*)gemv_w4_decode3_group_kernel<Tag, BIASED, SX, 1> : (const void*)gemv_w4_decode3_group_kernel<Tag, BIASED, SX, 0>);
+}
+template <typename Tag>
+static const void* decode3_group_pick(bool biased, bool shared_x, int h) {
+    return biased ? (shared_x ? decode3_group_pick<Tag, true, true>(h) : decode3_group_pick<Tag, true, false>(h))
+                  : (shared_x ? decode3_group_pick<Tag, false, true>(h) : decode3_group_pick<Tag, false, false>(h));
+}
+const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h) {
+    return tag == 0 ? decode3_group_pick<half_tag>(biased, shared_x, h) : decode3_group_pick<bf16_tag>(biased, shared_x, h);
+}
 
 }  // namespace gl

@@ -8,6 +8,7 @@
 //   x            : [M, K] row-major,  out : [M, N] row-major
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/gemlite_hip.h"
@@ -600,53 +601,33 @@ struct Decode3Args {
     unsigned* counters;
 };
 
-// gemv_w4_decode3_kernel<.., Decode3GroupTable> (gemv_decode.hip): the pointers of layers 1 .. DECODE3_GMAX - 1 of a grouped launch, passed
-// by value behind the 14 preloaded dwords (layer 0's Decode3Args without `counters`).  sw4 / mstride2 / nch_total / modes are shared by the
-// group; the member count and grid.y ride in bits 16..23 / 24..31 of `modes` (decode3_group_modes), which no single-layer launch sets.
+// The grouped kernels (gemv_w4_decode3_group_kernel, gemv_decode.hip; gemm_w4_rows[_bias]_group_kernel, gemm_wn_rows_group.hip): the
+// pointers of members 1 .. DECODE3_GMAX - 1 of a grouped launch, passed by value behind the scalar arguments (member 0's: Decode3Args
+// without `counters`, Rows5Args).  sw4 / mstride2 / nch_total / modes are shared by the group; a decode group's member count and grid.y
+// ride in bits 16..23 / 24..31 of `modes` (decode3_group_modes), which no single-layer launch sets; a rows group has grid.y = members.
 constexpr int DECODE3_GMAX = 16;
-struct Decode3Member {
+struct GroupMember {
     const char *w, *x, *s, *z;
     uint16_t* out;
 };
-struct Decode3GroupTable {
-    Decode3Member m[DECODE3_GMAX - 1];
-};
 // The BIASED forms (out = from_float(to_float(from_float(acc)) + to_float(bias[n])): both roundings of "matmul, then out += bias" kept).  The
-// bias pointer travels behind the 14 preloaded dwords like `counters` (a biased launch never carries the timeline probe); a biased group
-// holds one bias pointer per member, layer 0's included.  A group is all-biased or all-unbiased: the kernel functions differ.
+// bias pointer of a single-layer decode launch travels behind the 14 preloaded dwords like `counters` (a biased launch never carries the
+// timeline probe); a biased group holds one bias pointer per member, member 0's included.  A group is all-biased or all-unbiased.
 struct Decode3BiasTail {
     const uint16_t* bias;
 };
-struct Decode3BiasGroupTable {
-    Decode3Member m[DECODE3_GMAX - 1];
+template <bool BIASED>
+struct GroupTable {
+    GroupMember m[DECODE3_GMAX - 1];
     const uint16_t* bias[DECODE3_GMAX];
 };
-// The SHARED-X grouped forms: every member reads the same x (q / k / v, gate / up, the experts of one token), so a block stages the pair
-// dwords and the per-unit sums of x in LDS once and its waves read them from there (gemv_decode.hip).  Same tables under their own type
-// names (the kernel functions differ); the members' x pointers are not read.
-struct Decode3GroupTableSX {
-    Decode3Member m[DECODE3_GMAX - 1];
+template <>
+struct GroupTable<false> {
+    GroupMember m[DECODE3_GMAX - 1];
 };
-struct Decode3BiasGroupTableSX {
-    Decode3Member m[DECODE3_GMAX - 1];
-    const uint16_t* bias[DECODE3_GMAX];
-};
-// LINES (below: decode3_group_lines): the same four tables under a type that carries log2 of the tiles per wave, for the forms with H = 2 and
-// H = 4 (the kernel functions differ; the layout is the table's, so the same objects are passed)
-template <typename Table, int HL>
-struct Decode3Lines {
-    Table t;
-};
-template <typename T>
-struct Decode3LinesOf {
-    using table = T;
-    static constexpr int hl = 0;
-};
-template <typename T, int HL>
-struct Decode3LinesOf<Decode3Lines<T, HL>> {
-    using table = T;
-    static constexpr int hl = HL;
-};
+// (capture_group.hip keeps ONE biased table per group and hands it to either kind of kernel: an unbiased kernel's argument is its prefix)
+static_assert(offsetof(GroupTable<true>, m) == 0 && sizeof(GroupTable<false>) == offsetof(GroupTable<true>, bias), "the unbiased table is a prefix of the biased one");
+static_assert(sizeof(GroupTable<false>) == 600 && sizeof(GroupTable<true>) == 728, "kernel-argument layout of the grouped kernels");
 // LDS of a shared-x block: the 64 KiB of partial rows (DECODE3_GMAX layers x 4 KiB), then per 16-element unit of x (K / 16 = 16 per 32-row
 // chunk) 32 bytes of pair dwords, then per unit its 4-byte sum: 64 KiB + 2.25 K bytes, dynamic.  The block's 1024 threads stage the
 // units in trips of 1024.  0: the staging area does not fit beside the partial rows in the 160 KiB of a CU (K > 43520).
@@ -795,21 +776,7 @@ struct Rows5Args {
     uint32_t sxm2, som;
 };
 
-// gemm_w4_rows_group_kernel / gemm_w4_rows_bias_group_kernel (gemm_wn_rows_group.hip): the pointers of members 1 .. ROWS5_GMAX - 1 of a
-// grouped launch, by value behind the scalars above (member 0's, shared by the group but for the five pointers); grid.y = members.  A
-// biased group holds one bias pointer per member, member 0's included (the layout of Decode3GroupTable / Decode3BiasGroupTable).
-constexpr int ROWS5_GMAX = DECODE3_GMAX;
-struct Rows5Member {
-    const char *w, *x, *s, *z;
-    uint16_t* out;
-};
-struct Rows5GroupTable {
-    Rows5Member m[ROWS5_GMAX - 1];
-};
-struct Rows5BiasGroupTable {
-    Rows5Member m[ROWS5_GMAX - 1];
-    const uint16_t* bias[ROWS5_GMAX];
-};
+constexpr int ROWS5_GMAX = DECODE3_GMAX;  // members of a grouped rows launch (GroupTable, above)
 
 struct LaunchPlan {
     const void* fn;
@@ -829,6 +796,8 @@ struct LaunchPlan {
     // the grouped forms of `bias_of` and of `fn_bias` (rows kernels only: capture_group.hip rewrites a capture's node to one of them)
     const void* fn_group = nullptr;
     const void* fn_bias_group = nullptr;
+    // decode3 launches: the dtype tag capture_group.hip asks gemv_w4_decode3_group_fn() with, at every join (H, shared x: the join's choice)
+    int d3_group_tag = -1;  // 0 fp16 | 1 bf16 | -1: the launch has no grouped forms
 };
 
 }  // namespace gl

@@ -18,21 +18,25 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_loops as L
 
-FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", "Decode3GroupTable", "Decode3BiasGroupTable",
+DECODE3_GROUPED = "gemv_w4_decode3_group_kernel"
+FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", DECODE3_GROUPED,
             "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel")
 # gemv_wn_kernel (round 6: gvw::ring2_run): the prologue requests up to two chunks behind uniform branches and the last one to three chunks run in
 # straight-line code BEHIND the loop — replayed in address order (no branch is followed), prologue and tail included, every conditional request
 # issued and every run of alternative waits taken at its weakest member
-# Decode3GroupTable / Decode3BiasGroupTable (round 13): the grouped forms of gemv_w4_decode3_kernel, named by their table argument — the single-layer
-# forms keep hipcc's own loads.  The kernel holds gvw::ring2_run TWICE (metadata selects compiled in / out), each copy with its own first requests, loop and
+# DECODE3_GROUPED (round 13): gemv_w4_decode3_group_kernel (gemv_decode.hip) — the single-layer gemv_w4_decode3_kernel keeps hipcc's own loads.
+# All 24 forms must be found: fewer is a failure, not "nothing could be checked".  The kernel holds gvw::ring2_run TWICE (metadata selects
+# compiled in / out), each copy with its own first requests, loop and
 # peeled tail, each ending drained.  What the replay covers: the copy whose loop is picked (most v_dot2; the first on a tie) is replayed with its
 # wrap-around trips; the OTHER copy is replayed in address order only — first requests, ONE trip of its loop, its tail — so a touch that only a second
 # trip of that copy's loop would show is not seen.  (Both copies are the same source with one `if constexpr` apart.)
-LINEAR_WITH_TAIL = ("gemv_wn_kernel", "Decode3GroupTable", "Decode3BiasGroupTable")
+LINEAR_WITH_TAIL = ("gemv_wn_kernel", DECODE3_GROUPED)
 # gemm_w4_rows_group_kernel / gemm_w4_rows_bias_group_kernel: the grouped forms of gemm_w4_rows_kernel (gemm_wn_rows_group.hip) — the same body
 # behind a scalar selection of the member's pointers, replayed like the single-layer forms
-ALTERNATIVE_WAITS = ("gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", "Decode3GroupTable", "Decode3BiasGroupTable",
+ALTERNATIVE_WAITS = ("gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", DECODE3_GROUPED,
                      "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel")
+DECODE3_GROUPED_FORMS = 24  # 2 dtypes x biased x shared x x H
+
 VREG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 
 
@@ -123,7 +127,7 @@ def replay(lines, seq, weakest_of_alternatives=False):
 
 
 def check():
-    seen, reports = 0, []
+    seen, grouped, reports = 0, 0, []
     for co in L.code_objects(L.LIB):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(co)
@@ -132,7 +136,7 @@ def check():
         fn, lines = None, []
 
         def flush():
-            nonlocal seen
+            nonlocal seen, grouped
             if not fn or not any(h in fn for h in FAMILIES) or not lines:
                 return
             seen += 1
@@ -159,6 +163,7 @@ def check():
             if best is None:
                 return
             lo, hi, _ = best
+            grouped += DECODE3_GROUPED in fn
             # first pass: straight-line from the top, following UNCONDITIONAL forward branches (hipcc rotates some loops: the preheader ends in an
             # s_branch into the middle of the body — the ring form of the rows kernel with four pieces per chunk); then full iterations
             linear_tail = any(k in fn for k in LINEAR_WITH_TAIL)
@@ -212,20 +217,24 @@ def check():
             if m and fn:
                 lines.append((int(m.group(2), 16), m.group(1).strip()))
         flush()
-    return seen, reports
+    return seen, grouped, reports
 
 
 if __name__ == "__main__":
     if not L.OBJDUMP or not os.path.exists(L.LIB):
         print("isa_asmloads: cannot check (no llvm-objdump or no library)")
         sys.exit(2)
-    seen, reports = check()
+    seen, grouped, reports = check()
     if seen == 0:
         print("isa_asmloads: no gemm_wn_mma_kernel found — nothing was checked")
         sys.exit(2)
     names = sorted(set(r[0] for r in reports))
     dem = dict(zip(names, subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.strip().split("\n"))) if names else {}
-    print(f"isa_asmloads: {seen} MFMA tile kernels replayed; destination of an outstanding load touched early in {len(names)} kernels")
+    print(f"isa_asmloads: {seen} MFMA tile kernels replayed, {grouped} of them forms of gemv_w4_decode3_group_kernel; "
+          f"destination of an outstanding load touched early in {len(names)} kernels")
+    if grouped != DECODE3_GROUPED_FORMS:
+        print(f"  MISSING: {DECODE3_GROUPED_FORMS} forms of {DECODE3_GROUPED} expected")
+        sys.exit(1)
     for (fn, a, t, r) in reports[:40]:
         print(f"  EARLY {dem.get(fn, fn)[:120]} @{a}: {t[:80]}  (v{r})")
     sys.exit(1 if reports else 0)

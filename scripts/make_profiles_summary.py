@@ -13,7 +13,8 @@ if os.path.exists(os.path.join(root, off, "bench_full.json")):
     full = json.load(open(os.path.join(root, off, "bench_full.json"))).get("blocks", {})
 avg = calls = mn = None
 for row in csv.DictReader(open(os.path.join(root, off, "rocprof_bench_kernel_stats.csv"))):
-    if "gemv_w4_decode3_kernel<gl::half_tag, true>" in row["Name"] or "gemv_w4_decode3_kernel<gl::half_tag, true, unsigned int*>" in row["Name"]:
+    # (the single-layer fp16 form with non-temporal weight loads, as its name was spelled in rounds 4, 6 and 19: <Tag, NT, BIASED>)
+    if any(f"gemv_w4_decode3_kernel<gl::half_tag, true{t}>" in row["Name"] for t in ("", ", unsigned int*", ", false")):
         avg, calls, mn = float(row["AverageNs"]) / 1000, int(row["Calls"]), float(row["MinNs"]) / 1000
 cb = d["cpu_baseline"]
 

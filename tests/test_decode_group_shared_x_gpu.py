@@ -1,4 +1,4 @@
-"""The SHARED-X form of the grouped M = 1 decode kernel (gemv_decode.hip, Tail = Decode3GroupTableSX / Decode3BiasGroupTableSX): a group
+"""The SHARED-X form of the grouped M = 1 decode kernel (gemv_decode.hip, gemv_w4_decode3_group_kernel with SX = true): a group
 whose members all read the same x stages the pair dwords and the per-unit sums of x in LDS once per block, and an item is four
 requests and three LDS reads.  ONE x tensor is passed to every member here.  Every comparison is BIT-EXACT (torch.equal) against the eager
 output of the same layer on the same x; outputs are pre-filled with NaN before the replay; every case asserts through

@@ -1,5 +1,5 @@
 """The grouped M = 1 decode kernel streams the layers of a capture group through one resident block per tile (gemv_decode.hip,
-Tail = Decode3GroupTable): a layer loop with a ring of chunk buffers, grid (N / 16, Y).  Every comparison is BIT-EXACT (torch.equal)
+gemv_w4_decode3_group_kernel): a layer loop with a ring of chunk buffers, grid (N / 16, Y).  Every comparison is BIT-EXACT (torch.equal)
 against the eager output of the same layer; outputs are pre-filled with NaN before the replay, so a skipped layer shows."""
 import ctypes as C
 

@@ -1,5 +1,5 @@
-"""The grouped M = 1 decode kernel gives every layer of a block its own waves (gemv_decode.hip, Tail = Decode3GroupTable /
-Decode3BiasGroupTable): block (tile, y) holds LB layers at once, 16 / LB waves each, a wave walks a contiguous run of the single-layer
+"""The grouped M = 1 decode kernel gives every layer of a block its own waves (gemv_decode.hip, gemv_w4_decode3_group_kernel, unbiased /
+biased): block (tile, y) holds LB layers at once, 16 / LB waves each, a wave walks a contiguous run of the single-layer
 kernel's waves ("virtual waves") through a two-buffer ring of counted requests, and the block has one barrier.  Every comparison is
 BIT-EXACT (torch.equal) against the eager output of the same layer; outputs are pre-filled with NaN before the replay, so a layer that
 was skipped shows; every case names the kernel the planner gives its layers."""
