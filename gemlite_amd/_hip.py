@@ -196,6 +196,27 @@ class DequantizeArgs(C.Structure):
     ]
 
 
+class ExpertsArgs(C.Structure):
+    """struct gemlite_hip_experts_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("ids_dtype", C.c_int32),
+        ("layer", ForwardArgs),
+        ("ids", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("n_slots", C.c_int64),
+        ("n_experts", C.c_int64),
+        ("slots_per_x_row", C.c_int64),
+        ("stride_expert_w", C.c_int64),
+        ("stride_expert_meta", C.c_int64),
+        ("stride_expert_bias", C.c_int64),
+        ("stride_x_row", C.c_int64),
+        ("stride_out_slot", C.c_int64),
+        ("reserved", C.c_int64 * 2),
+    ]
+
+
 BIAS_NOT_ADDED = 1  # gemlite_hip_forward_ex: launched without the bias, the caller adds it
 
 _lib = None
@@ -294,6 +315,10 @@ def load():
         lib.gemlite_hip_quantize_rows.argtypes = [C.POINTER(QuantizeRowsArgs), C.c_void_p]
         lib.gemlite_hip_dequantize.restype = C.c_int
         lib.gemlite_hip_dequantize.argtypes = [C.POINTER(DequantizeArgs), C.c_void_p]
+        lib.gemlite_hip_forward_experts.restype = C.c_int
+        lib.gemlite_hip_forward_experts.argtypes = [C.POINTER(ExpertsArgs), C.c_void_p]
+        lib.gemlite_hip_experts_query.restype = C.c_int
+        lib.gemlite_hip_experts_query.argtypes = [C.POINTER(ExpertsArgs)]
         if lib.gemlite_hip_abi_version() != ABI_VERSION:
             raise GemliteHipError("libgemlite_hip.so ABI version mismatch; rebuild it")
         _lib = lib
@@ -315,6 +340,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
     "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize", "gemlite_hip_quantize_groups_hqq",
     "gemlite_hip_quantize_rows",
+    "gemlite_hip_forward_experts", "gemlite_hip_experts_query",
 )
 
 

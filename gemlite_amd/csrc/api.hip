@@ -63,6 +63,7 @@ const void* quantize_rows_kernel_fn(int format, int64_t K);
 const void* dequantize_words_kernel_fn(int nbits);
 const void* dequantize_rows_kernel_fn(int fmt);
 const void* dequantize_any_kernel_fn();
+const void* gemv_w4_decode3_experts_fn(int tag, bool biased, bool ids64);  // gemv_decode.hip
 // capture_group.hip: independent decode3 (or rows) launches of one stream capture folded into one grouped launch
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
@@ -1215,6 +1216,94 @@ static int launch_resolved(const gemlite_hip_forward_args* args, Resolved& r, in
         if (e != GEMLITE_OK) return e;
     }
     return launch(r.lp.fn, r.lp.grid, r.lp.block, kargs, r.lp.lds_bytes, st);
+}
+
+// ---- experts: n_slots M = 1 GEMVs in one launch, the expert of each read on the GPU (gemv_decode.hip: gemv_w4_decode3_experts_kernel) ----
+// Not a planned launch: resolve(), the planners and capture_group.hip never see it.  The 14 scalars are derived here exactly as
+// plan_gemv_wn derives them for the single-layer kernel (Decode3Args), from expert 0's layer; the domain is checked in full first.
+struct ExpertsLaunch {
+    Decode3Args d3;
+    ExpertsTail tail;
+    const void* fn;
+    dim3 grid;
+};
+
+static int experts_plan(const gemlite_hip_experts_args* e, ExpertsLaunch& L) {
+    if (!e || e->struct_size != sizeof(gemlite_hip_experts_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    const gemlite_hip_forward_args& a = e->layer;
+    const int v = validate(&a);
+    if (v != GEMLITE_OK) return v;
+    if (!e->ids || e->n_slots <= 0 || e->n_experts <= 0 || e->slots_per_x_row <= 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (e->ids_dtype != GEMLITE_DT_INT32 && e->ids_dtype != GEMLITE_DT_INT64) return GEMLITE_ERR_UNSUPPORTED;
+    const bool f16 = a.input_dtype == GEMLITE_DT_FP16;
+    if ((!f16 && a.input_dtype != GEMLITE_DT_BF16) || a.output_dtype != a.input_dtype) return GEMLITE_ERR_UNSUPPORTED;
+    if (a.W_nbits != 4 || a.elements_per_sample != 8 || a.w_pack_bits != 32) return GEMLITE_ERR_UNSUPPORTED;
+    if (a.channel_scale_mode != 0 || a.W_group_mode < 1) return GEMLITE_ERR_UNSUPPORTED;
+    const bool need_s = a.W_group_mode >= 2, has_z = a.W_group_mode == 1 || a.W_group_mode >= 3;
+    const bool z_scalar = has_z && a.zero_is_scalar != 0, need_z = has_z && !z_scalar;
+    if ((need_s && a.meta_dtype != a.input_dtype) || (need_z && a.zeros_dtype != a.input_dtype) || (z_scalar && a.zeros_dtype != GEMLITE_DT_INT32))
+        return GEMLITE_ERR_UNSUPPORTED;
+    if (a.stride_xk != 1 || a.stride_wn != 1 || a.stride_on != 1 || ((need_s || need_z) && a.stride_meta_n != 1)) return GEMLITE_ERR_UNSUPPORTED;
+    const int64_t gs = a.group_size;
+    if (a.M != 1 || a.N % 16 != 0 || a.K % 256 != 0 || gs < 32 || (gs & (gs - 1)) != 0 || a.K % gs != 0) return GEMLITE_ERR_BAD_SHAPE;
+    if (e->n_slots > 65535 || e->n_experts > 0x7FFFFFFF) return GEMLITE_ERR_BAD_SHAPE;
+    // every base a slot can produce keeps the alignment of the kernel's loads: 16-byte weights and x rows, 8-byte metadata, 2-byte bias
+    const bool per_group = (need_s || need_z) && gs < a.K;  // (one K-long group: the row stride is never used)
+    if (e->stride_expert_w < 0 || e->stride_expert_meta < 0 || e->stride_expert_bias < 0 || e->stride_x_row < 0 || e->stride_out_slot < 0 ||
+        a.stride_wk <= 0 || (per_group && a.stride_meta_g <= 0))
+        return GEMLITE_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)a.w_q % 16) != 0 || (a.stride_wk % 4) != 0 || (e->stride_expert_w % 16) != 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)a.x % 16) != 0 || (e->stride_x_row % 8) != 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if ((need_s && ((uintptr_t)a.scales % 8) != 0) || (need_z && ((uintptr_t)a.zeros % 8) != 0) || (z_scalar && ((uintptr_t)a.zeros % 4) != 0) ||
+        (per_group && (a.stride_meta_g % 4) != 0) || ((need_s || need_z) && (e->stride_expert_meta % 8) != 0))
+        return GEMLITE_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)a.out % 2) != 0 || (e->bias && (((uintptr_t)e->bias % 2) != 0 || (e->stride_expert_bias % 2) != 0))) return GEMLITE_ERR_BAD_ARGUMENT;
+    // 32-bit byte offsets inside one expert, as the single-layer kernel has them
+    const int64_t rows = a.K / 8, meta_g = per_group ? a.stride_meta_g : 0;
+    if (rows * a.stride_wk * 4 >= (1ll << 32) || (a.K / gs) * meta_g * 2 + a.N * 2 >= (1ll << 32) || rows * 16 >= (1ll << 31)) return GEMLITE_ERR_BAD_SHAPE;
+
+    const int64_t tiles = a.N / 16;
+    const uint32_t gs_shift = per_group ? (uint32_t)__builtin_ctzll((unsigned long long)gs) : 31u;
+    L.d3.w = (const char*)a.w_q;
+    L.d3.x = (const char*)a.x;
+    L.d3.s = need_s ? (const char*)a.scales : (const char*)a.w_q;
+    L.d3.z = has_z ? (const char*)a.zeros : (const char*)a.w_q;
+    L.d3.out = (uint16_t*)a.out;
+    L.d3.sw4 = (uint32_t)a.stride_wk * 4u;
+    L.d3.mstride2 = (uint32_t)meta_g * 2u;
+    L.d3.nch_total = (int)(rows / 32);
+    L.d3.modes = (uint32_t)a.W_group_mode | (z_scalar ? 16u : 0u) | (((tiles & 15) == 0) ? 32u : 0u) | (gs_shift << 8);
+    L.d3.counters = nullptr;
+    L.tail.ids = e->ids;
+    L.tail.bias = (const uint16_t*)e->bias;
+    L.tail.stride_w = e->stride_expert_w;
+    L.tail.stride_meta = e->stride_expert_meta;
+    L.tail.stride_bias = e->stride_expert_bias;
+    L.tail.stride_x = e->stride_x_row * 2;
+    L.tail.stride_out = e->stride_out_slot;
+    L.tail.n_experts = (uint32_t)e->n_experts;
+    L.tail.slots_per_x_row = (uint32_t)(e->slots_per_x_row > 65536 ? 65536 : e->slots_per_x_row);  // (slot < 65535: row 0 either way)
+    L.fn = gemv_w4_decode3_experts_fn(f16 ? 0 : 1, e->bias != nullptr, e->ids_dtype == GEMLITE_DT_INT64);
+    L.grid = dim3((unsigned)tiles, (unsigned)e->n_slots, 1);
+    return GEMLITE_OK;
+}
+
+int gemlite_hip_experts_query(const gemlite_hip_experts_args* args) {
+    ExpertsLaunch L;
+    return experts_plan(args, L);
+}
+
+int gemlite_hip_forward_experts(const gemlite_hip_experts_args* args, void* stream) {
+    ExpertsLaunch L;
+    const int v = experts_plan(args, L);
+    if (v != GEMLITE_OK) return v;
+    int dev = 0;
+    const int dv = check_device(&dev);
+    if (dv != GEMLITE_OK) return dv;
+    Decode3Args& d = L.d3;
+    void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
+                     (void*)&d.nch_total, (void*)&d.modes, (void*)&L.tail};
+    return launch(L.fn, L.grid, dim3(1024, 1, 1), kargs, 0, (hipStream_t)stream);
 }
 
 int gemlite_hip_scale_activations_per_token(const void* x, void* y, float* scales, int64_t M, int64_t K,

@@ -16,13 +16,15 @@
 // 16 waves x 64 lanes, lane (g = lane >> 2, c = lane & 3) owns columns 4c .. 4c + 3 of a 16-column tile and packed rows
 // chunk * 512 + wave * 32 + 2 g + {0, 1}.
 //
-// Two kernels, the form of each spelled in its template parameters; they share the device helpers of dec3 (an item's arithmetic, the row
+// Three kernels, the form of each spelled in its template parameters; they share the device helpers of dec3 (an item's arithmetic, the row
 // sums, the final reduction with the bias add and the store), so per layer a group runs the single-layer code in the same order and every
 // layer's output is bit-identical to its own launch:
 //   kernel                                               argument behind the 14 dwords    launched by
 //   gemv_w4_decode3_kernel<Tag, NT, BIASED>              unsigned* counters (timeline) |  the planner: dependent chains, eager and profiled
 //                                                        Decode3BiasTail (BIASED)         launches, a group of one
 //   gemv_w4_decode3_group_kernel<Tag, BIASED, SX, HL>    GroupTable<BIASED> by value      capture_group.hip, by rewriting a capture's node
+//   gemv_w4_decode3_experts_kernel<Tag, BIASED, IDS64>   ExpertsTail by value             gemlite_hip_forward_experts (api.hip): the single-layer
+//                                                                                         block per (tile, slot), the expert id read on the GPU
 //     BIASED  the bias add in the epilogue (gl_common.h has the arithmetic); the lanes that store ask for their bias element in front of
 //             the barrier, so it arrives under the reduction
 //     SX      SHARED X, for a group whose members all read the same x.  What a lane derives from x — the pair dwords (x0,x4)(x1,x5)(x2,x6)
@@ -513,7 +515,109 @@ void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp
     if (fin) finish<Tag, BIASED>(redg + wave * RED, braw, o_, ftile);
 }
 
+// The experts of a mixture-of-experts layer (gemlite_hip_forward_experts): grid (N / 16, slots), block (tile, s) is the single-layer block
+// of expert ids[s] on x row s / slots_per_x_row — the body of gemv_w4_decode3_kernel<Tag, true, BIASED> line for line (the same waves and
+// chunks in the same order, Item::run<false>, row_sum, the block's own 4 KiB of partial rows, finish), so every slot is bit-identical
+// to that expert's own launch.  What differs lies in front of the first request: the id is a SCALAR load the block does itself (uniform
+// per block; int32 or int64 as the router wrote it), the expert's bases are base + id * stride in 64-bit scalar arithmetic (a stacked
+// tensor is far beyond 4 GiB; the offsets inside an expert stay 32-bit), and the x row / output slot come from blockIdx.y.  The first 14
+// dwords are the decode3 set (preloaded), the tail is read with scalar loads and the id load follows it: two dependent scalar round trips
+// in front of the weight requests, where the single-layer kernel has none (no user SGPR is left to preload the ids pointer into).
+// An id outside [0, n_experts) is never turned into an address: the block writes its 16 zeros and leaves (a uniform branch).
+template <typename Tag, bool BIASED, bool IDS64>
+__global__ __launch_bounds__(1024, 1)
+void gemv_w4_decode3_experts_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
+                                    uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes, const ExpertsTail tail) {
+    using namespace dec3;
+    __shared__ __attribute__((aligned(16))) float red[RED];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 3, g = lane >> 2;
+    int tile = blockIdx.x;
+    if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
+        const int xcd = tile & 7, idx = tile >> 3;
+        tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
+    }
+    const uint32_t slot = blockIdx.y;
+    // (int32: a negative id is >= 2^31 as unsigned and n_experts is below 2^31; int64: the high dword takes part in the comparison)
+    uint64_t e;
+    if constexpr (IDS64) {
+        e = (uint64_t)((const int64_t*)tail.ids)[slot];
+    } else {
+        e = (uint64_t)(uint32_t)((const int32_t*)tail.ids)[slot];
+    }
+    out += (uint64_t)slot * (uint64_t)tail.stride_out;
+    if (e >= (uint64_t)tail.n_experts) {
+        if (tid < TC) out[tile * TC + tid] = 0;
+        return;
+    }
+    wb += e * (uint64_t)tail.stride_w;
+    sp += e * (uint64_t)tail.stride_meta;
+    if (!(modes & M_ZSCALAR)) zp += e * (uint64_t)tail.stride_meta;  // (one scalar zero is shared by all experts)
+    xb += (uint64_t)(slot / tail.slots_per_x_row) * (uint64_t)tail.stride_x;
+
+    const uint32_t n0 = (uint32_t)(tile * TC + c * 4);
+    const int nchunks = (nch_total - wave + NW - 1) / NW;  // chunks wave, wave + NW, ...
+    const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
+    const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
+
+    const uint32_t row0 = (uint32_t)(wave * CHUNK + g * R);  // this lane's first row of chunk 0
+    const uint32_t wo0 = row0 * sw4 + n0 * 4u;
+    const uint32_t xo0 = (uint32_t)(wave * CHUNK) * 16u + (uint32_t)lane * 8u;  // the wave's 512 bytes of x, 8 per lane
+
+    auto load_chunk = [&](Chunk& ck, int chunk) {
+        const uint32_t wo = wo0 + (uint32_t)(chunk * CSTRIDE) * sw4;
+#pragma unroll
+        for (int i = 0; i < R; ++i) ck.w[i] = __builtin_nontemporal_load((const u32x4*)(wb + (wo + (uint32_t)i * sw4)));
+        ck.xq = *(const u32x2*)(xb + (xo0 + (uint32_t)(chunk * CSTRIDE) * 16u));
+        const uint32_t row = row0 + (uint32_t)(chunk * CSTRIDE);
+        const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
+        // (absent metadata is still "loaded" — from the expert's weights, always in bounds — so the loop stays branch-free)
+        ck.s = *(const u32x2*)((need_s ? sp : wb) + (need_s ? mo : 0u));
+        ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
+    };
+    Chunk cur, nxt;
+    if (nchunks > 0) load_chunk(cur, 0);
+    if (nchunks > 1) load_chunk(nxt, 1);
+
+    float tot[4] = {0.f, 0.f, 0.f, 0.f};
+    const float scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
+    const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
+    const bool b_times_s = w_mode == 3;
+    uint32_t wmask[Item<Tag, false>::WP];
+#pragma unroll
+    for (int i = 0; i < Item<Tag, false>::WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
+    const Item<Tag, false> item{{}, wmask, need_s, need_z, scalar_zero, bz, b_times_s, tot};
+#pragma unroll 1
+    for (int ch = 0; ch < nchunks; ++ch) {
+        item.template run<false>(cur);
+        if (ch + 1 < nchunks) {
+            cur = nxt;
+            if (ch + 2 < nchunks) load_chunk(nxt, ch + 2);
+        }
+    }
+    uint16_t braw = 0;
+    if constexpr (BIASED) {
+        if (wave == 0 && lane < 16) braw = ((const uint16_t*)((const char*)tail.bias + e * (uint64_t)tail.stride_bias))[tile * TC + lane];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tot[j] = row_sum(tot[j]);
+    if ((lane & 12) == 0) *(f32x4*)(red + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
+    __syncthreads();
+    if (wave == 0) finish<Tag, BIASED>(red, braw, out, tile);
+}
+
 // tag: 0 fp16 | 1 bf16
+template <typename Tag>
+static const void* decode3_experts_pick(bool biased, bool ids64) {
+    return biased ? (ids64 ? (const void*)gemv_w4_decode3_experts_kernel<Tag, true, true> : (const void*)gemv_w4_decode3_experts_kernel<Tag, true, false>)
+                  : (ids64 ? (const void*)gemv_w4_decode3_experts_kernel<Tag, false, true> : (const void*)gemv_w4_decode3_experts_kernel<Tag, false, false>);
+}
+const void* gemv_w4_decode3_experts_fn(int tag, bool biased, bool ids64) {
+    return tag == 0 ? decode3_experts_pick<half_tag>(biased, ids64) : decode3_experts_pick<bf16_tag>(biased, ids64);
+}
+
 const void* gemv_w4_decode3_fn(int tag, bool nt) {
     return tag == 0 ? (nt ? (const void*)gemv_w4_decode3_kernel<half_tag, true> : (const void*)gemv_w4_decode3_kernel<half_tag, false>)
                     : (nt ? (const void*)gemv_w4_decode3_kernel<bf16_tag, true> : (const void*)gemv_w4_decode3_kernel<bf16_tag, false>);

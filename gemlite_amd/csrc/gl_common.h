@@ -616,6 +616,15 @@ struct GroupMember {
 struct Decode3BiasTail {
     const uint16_t* bias;
 };
+// gemv_w4_decode3_experts_kernel (gemv_decode.hip; gemlite_hip_forward_experts): what travels behind the 14 preloaded dwords, which are
+// expert 0's pointers, x row 0 and slot 0 of the output.  Slot s = blockIdx.y uses expert ids[s]: the strides are bytes, 64-bit
+struct ExpertsTail {
+    const void* ids;        // int32 or int64 (the kernel's IDS64), n_slots entries
+    const uint16_t* bias;   // expert 0's (the BIASED forms)
+    int64_t stride_w, stride_meta, stride_bias;  // between experts
+    int64_t stride_x, stride_out;                // between x rows / output slots
+    uint32_t n_experts, slots_per_x_row;
+};
 template <bool BIASED>
 struct GroupTable {
     GroupMember m[DECODE3_GMAX - 1];

@@ -1,0 +1,256 @@
+"""GemLiteExperts: the experts of a mixture-of-experts layer as ONE decode launch whose expert ids are read on the GPU.
+
+``layer(x)`` bakes a layer's weight pointers into the graph node at capture time; which experts a token uses is the router's top-k, a
+device tensor known only when the graph replays.  ``GemLiteExperts`` stacks E identical A16W4 layers into one ``[E, K/8, N]`` weight
+tensor (scales / zeros ``[E, K/g, N]``, bias ``[E, N]``) and runs ``gemlite_hip_forward_experts`` (include/gemlite_hip.h): slot ``s`` of the
+``expert_ids`` tensor is one M = 1 GEMV of expert ``expert_ids[s]``, bit-identical to that expert's own decode launch; the id is loaded
+by the kernel, so the call can be captured once and replayed with other ids.  An id outside ``[0, E)`` (-1: "not on this rank") gives a
+row of zeros.  Domain: DESIGN.md §3.1.3 — 4-bit weights in 32-bit words, fp16 / bf16, grouped scales / zeros, N % 16 == 0, K % 256 == 0.
+There is no slow path: layers outside the domain are refused by ``from_layers``.
+"""
+import threading
+from typing import List, Optional, Sequence
+
+import torch
+from torch import Tensor
+
+from . import _hip
+from . import core
+from .dtypes import DTYPE_TO_TORCH, TORCH_TO_DTYPE, DType
+
+MAX_SLOTS = 65535  # of one launch (grid.y)
+
+_TEMPLATES: dict = {}
+_TEMPLATES_LOCK = threading.Lock()
+
+
+def _first(t: Tensor) -> Tensor:
+    """Expert 0's slice of a stacked tensor (absent metadata and a scalar zero are not stacked)."""
+    return t[0] if t.dim() == 3 else t
+
+
+def _build_template(W_q: Tensor, scales: Tensor, zeros: Tensor, bias: Optional[Tensor], meta_args) -> bytes:
+    """The static half of a gemlite_hip_experts_args: expert 0 as a layer (core._build_template), the expert count and strides."""
+    e = _hip.ExpertsArgs()
+    e.struct_size = _hip.C.sizeof(_hip.ExpertsArgs)
+    e.layer = _hip.ForwardArgs.from_buffer_copy(core._build_template(_first(W_q), _first(scales), _first(zeros), meta_args))
+    e.layer.M = 1
+    e.layer.stride_xk, e.layer.stride_om, e.layer.stride_on = 1, W_q.shape[2], 1
+    e.n_experts = W_q.shape[0]
+    e.stride_expert_w = W_q.stride(0) * W_q.element_size()
+    meta = scales if scales.dim() == 3 else (zeros if zeros.dim() == 3 else None)
+    e.stride_expert_meta = 0 if meta is None else meta.stride(0) * meta.element_size()
+    if bias is not None:
+        e.bias = bias.data_ptr()
+        e.stride_expert_bias = bias.stride(0) * bias.element_size()
+    return bytes(e)
+
+
+def _static_args(W_q: Tensor, scales: Tensor, zeros: Tensor, bias: Optional[Tensor], meta_args) -> "_hip.ExpertsArgs":
+    """A FRESH gemlite_hip_experts_args with the static fields filled in; the image is cached per everything it is derived from."""
+    key = core._template_key(W_q, scales, zeros, meta_args) + (
+        (None,) if bias is None else (bias.data_ptr(), tuple(bias.shape), bias.stride(), bias.dtype))
+    t = _TEMPLATES.get(key)
+    if t is None:
+        t = _build_template(W_q, scales, zeros, bias, meta_args)
+        with _TEMPLATES_LOCK:
+            while len(_TEMPLATES) >= 1024:
+                _TEMPLATES.pop(next(iter(_TEMPLATES)), None)
+            _TEMPLATES[key] = t
+    return _hip.ExpertsArgs.from_buffer_copy(t)
+
+
+def _call_args(x2: Tensor, ids: Tensor, out_ptr: int, bias: Optional[Tensor], tensor_args, meta_args, slots_per_x_row: int):
+    W_q, scales, zeros = tensor_args
+    e = _static_args(W_q, scales, zeros, bias, meta_args)
+    e.layer.x, e.layer.out = x2.data_ptr(), out_ptr
+    e.layer.input_dtype = TORCH_TO_DTYPE[x2.dtype].value
+    e.layer.stride_xm = x2.stride(0)
+    e.ids = ids.data_ptr()
+    e.ids_dtype = TORCH_TO_DTYPE[ids.dtype].value
+    e.n_slots = ids.numel()
+    e.slots_per_x_row = slots_per_x_row
+    e.stride_x_row = x2.stride(0)
+    e.stride_out_slot = W_q.shape[2]
+    return e
+
+
+def _split(x: Tensor, expert_ids: Tensor, K: int):
+    """-> (rows of x, slots per row of x): x [..., K] is one row per token, shared by its top_k slots; x [..., top_k, K] one row per slot."""
+    if expert_ids.dim() < 1:
+        raise ValueError("expert_ids should be [..., top_k]")
+    lead, top_k = tuple(expert_ids.shape[:-1]), expert_ids.shape[-1]
+    if tuple(x.shape) == lead + (K,):
+        return expert_ids.numel() // max(top_k, 1), top_k
+    if tuple(x.shape) == lead + (top_k, K):
+        return expert_ids.numel(), 1
+    raise ValueError(f"x is {tuple(x.shape)}; expert_ids {tuple(expert_ids.shape)} asks for {lead + (K,)} or {lead + (top_k, K)}")
+
+
+def _forward_impl(x: Tensor, expert_ids: Tensor, bias: Optional[Tensor], tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    W_q = tensor_args[0]
+    N, K = W_q.shape[2], W_q.shape[1] * meta_args[4]
+    lib = _hip.load()
+    for t, name in ((x, "x"), (expert_ids, "expert_ids"), (W_q, "W_q")):
+        _hip.require_gpu_tensor(t, name)
+    if x.device != W_q.device or expert_ids.device != W_q.device:
+        raise _hip.GemliteHipError(f"x is on {x.device}, expert_ids on {expert_ids.device}, the packed weights on {W_q.device}")
+    if expert_ids.dtype not in (torch.int32, torch.int64):
+        raise NotImplementedError(f"expert_ids are {expert_ids.dtype}: int32 or int64")
+    rows, spx = _split(x, expert_ids, K)
+    out = torch.empty(tuple(expert_ids.shape) + (N,), dtype=x.dtype, device=x.device)
+    if expert_ids.numel() == 0:
+        return out
+    x2 = x.contiguous().view(rows, K)
+    ids = expert_ids.contiguous()
+    e = _call_args(x2, ids, out.data_ptr(), bias, tensor_args, meta_args, spx)
+    with _hip.on_device(x.device):  # launches go to the tensor's device and torch's current stream there
+        rc = lib.gemlite_hip_forward_experts(_hip.C.byref(e), _hip.current_stream_handle(x.device))
+    _hip.raise_for_status(rc, "gemlite_hip_forward_experts")
+    return out
+
+
+@torch.library.custom_op("gemlite::forward_experts", mutates_args=())
+def forward_experts(x: Tensor, expert_ids: Tensor, bias: Optional[Tensor], tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    return _forward_impl(x, expert_ids, bias, tensor_args, meta_args)
+
+
+@torch.library.register_fake("gemlite::forward_experts")
+def _forward_experts_fake(x, expert_ids, bias, tensor_args, meta_args):
+    W_q = tensor_args[0]
+    _split(x, expert_ids, W_q.shape[1] * meta_args[4])
+    return torch.empty(tuple(expert_ids.shape) + (W_q.shape[2],), device=x.device, dtype=x.dtype)
+
+
+class GemLiteExperts(torch.nn.Module):
+    """E stacked A16W4 layers; ``experts(x, expert_ids)`` -> ``[..., top_k, N]`` in one launch (module docstring)."""
+
+    def __init__(self):
+        super().__init__()
+        self.W_q = self.scales = self.zeros = self.bias = None
+        self.metadata = self.orig_shape = self.n_experts = None
+        self._meta: List[int] = []
+        self._views: dict = {}
+
+    # ---------------------------------------------------------------------------------------- build
+    @classmethod
+    def from_layers(cls, layers: Sequence["core.GemLiteLinearHIP"], del_orig: bool = False) -> "GemLiteExperts":
+        layers = list(layers)
+        if not layers:
+            raise ValueError("from_layers needs at least one layer")
+        first = layers[0]
+        if getattr(first, "elements_per_sample", None) is None or not isinstance(getattr(first, "W_q", None), Tensor):
+            raise ValueError("from_layers takes packed GemLiteLinear layers (call .pack() first)")
+        meta = first.get_meta_args()
+
+        def same(a: Optional[Tensor], b: Optional[Tensor]) -> bool:
+            if a is None or b is None:
+                return a is b
+            return a.shape == b.shape and a.dtype == b.dtype and a.device == b.device
+
+        for i, layer in enumerate(layers[1:], 1):
+            if getattr(layer, "elements_per_sample", None) is None or layer.get_meta_args() != meta:
+                raise ValueError(f"layer {i} differs from layer 0 in bits, group size, modes or dtypes: "
+                                 f"{getattr(layer, 'elements_per_sample', None) and layer.get_meta_args()} vs {meta}")
+            for name in ("W_q", "scales", "zeros", "bias"):
+                if not same(getattr(layer, name), getattr(first, name)):
+                    raise ValueError(f"layer {i} differs from layer 0 in the shape, dtype or device of `{name}`")
+        if first.zeros.numel() == 1 and any(int(l.zeros) != int(first.zeros) for l in layers[1:]):
+            raise ValueError("the layers carry different scalar zeros: one scalar zero is shared by all experts")
+
+        self = cls()
+        self._meta = [int(v) for v in meta]
+        stack = lambda name: torch.stack([getattr(l, name).data for l in layers]).contiguous()  # noqa: E731
+        W_q = stack("W_q")
+        scales = stack("scales") if first.scales.numel() > 0 else first.scales.data
+        zeros = stack("zeros") if first.zeros.numel() > 1 else first.zeros.data
+        bias = None if first.bias is None else stack("bias")
+        self._check_domain(W_q, scales, zeros, bias)
+        as_param = lambda t: torch.nn.Parameter(t, requires_grad=False)  # noqa: E731
+        dev = W_q.device
+        self.W_q = as_param(W_q)
+        self.bias = None if bias is None else as_param(bias)
+        self.scales, self.zeros = as_param(scales), as_param(zeros)
+        self.metadata = as_param(torch.tensor(self._meta, device=dev, dtype=torch.int32))
+        self.orig_shape = as_param(torch.tensor([first.out_features, first.in_features], device=dev, dtype=torch.int32))
+        self.n_experts = as_param(torch.tensor(len(layers), device=dev, dtype=torch.int32))
+        self._set_shapes(first.out_features, first.in_features, len(layers))
+        if del_orig:
+            for layer in layers:
+                layer.W_q = layer.scales = layer.zeros = layer.bias = None
+        return self
+
+    def _set_shapes(self, out_features: int, in_features: int, n: int):
+        self.out_features, self.in_features, self.num_experts = int(out_features), int(in_features), int(n)
+        self._views = {}
+
+    def _check_domain(self, W_q: Tensor, scales: Tensor, zeros: Tensor, bias: Optional[Tensor]):
+        """The library's own answer (gemlite_hip_experts_query plans and never launches, with or without a GPU), on the stacked tensors
+        with stand-ins for x / out / ids; the most common refusals first, in words."""
+        m = self._meta
+        if m[0] or m[5] not in (DType.FP16.value, DType.BF16.value) or m[6] != m[5]:
+            raise NotImplementedError("GemLiteExperts: weight-only layers with fp16 / bf16 activations and outputs of the same type")
+        if m[1] != 4 or m[4] != 8 or W_q.dtype != torch.int32:
+            raise NotImplementedError(f"GemLiteExperts: 4-bit weights packed in 32-bit words (W_nbits={m[1]}, {W_q.dtype} words)")
+        if m[9] != 0 or not 1 <= m[10] <= 4:
+            raise NotImplementedError(f"GemLiteExperts: grouped scales / zeros (W_group_mode 1..4, no channel scales); "
+                                      f"got W_group_mode={m[10]}, channel_scale_mode={m[9]}")
+        e = _static_args(W_q, scales, zeros, bias, m)
+        e.layer.x = e.layer.out = e.ids = 0x1000
+        e.layer.stride_xm = e.stride_x_row = e.layer.K
+        e.ids_dtype = DType.INT32.value
+        e.n_slots = e.slots_per_x_row = 1
+        e.stride_out_slot = e.layer.N
+        rc = _hip.load().gemlite_hip_experts_query(_hip.C.byref(e))
+        if rc != _hip.OK:
+            raise NotImplementedError(f"GemLiteExperts: N={e.layer.N} K={e.layer.K} group_size={m[2]} W_group_mode={m[10]}: "
+                                      f"{_hip.status_string(rc)} (domain: N % 16 == 0, K % 256 == 0, a power-of-two group_size >= 32, "
+                                      "16-byte aligned contiguous weights)")
+
+    # ------------------------------------------------------------------------------- (de)serialise
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        self.W_q = state_dict.pop("W_q", None)
+        self.bias = state_dict.pop("bias", None)
+        self.scales = state_dict.pop("scales", None)
+        self.zeros = state_dict.pop("zeros", None)
+        self.metadata = state_dict.pop("metadata")
+        self.orig_shape = state_dict.pop("orig_shape")
+        self.n_experts = state_dict.pop("n_experts")
+        self._meta = [int(v) for v in self.metadata]
+        out_features, in_features = (int(v) for v in self.orig_shape)
+        if int(self.n_experts) != self.W_q.shape[0]:
+            raise ValueError(f"n_experts is {int(self.n_experts)}, W_q holds {self.W_q.shape[0]} experts")
+        self._set_shapes(out_features, in_features, self.W_q.shape[0])
+        self._check_domain(self.W_q, self.scales, self.zeros, self.bias)
+
+    # ----------------------------------------------------------------------------------- arguments
+    def get_tensor_args(self):
+        return [self.W_q, self.scales, self.zeros]
+
+    def get_meta_args(self):
+        return list(self._meta)
+
+    def expert(self, e: int) -> "core.GemLiteLinearHIP":
+        """A GemLiteLinear VIEW on expert e's slices (no copy): per-expert calls, tests, dequantize()."""
+        e = int(e)
+        if not 0 <= e < self.num_experts:
+            raise IndexError(f"expert {e} of {self.num_experts}")
+        lin = self._views.get(e)
+        if lin is None:
+            m = self._meta
+            lin = core.GemLiteLinearHIP(m[1], m[2], self.in_features, self.out_features, DType(m[5]), DType(m[6]))
+            lin.load_state_dict({
+                "W_q": self.W_q.data[e], "bias": None if self.bias is None else self.bias.data[e],
+                "scales": self.scales.data[e] if self.scales.dim() == 3 else self.scales.data,
+                "zeros": self.zeros.data[e] if self.zeros.dim() == 3 else self.zeros.data,
+                "metadata": list(m), "orig_shape": (self.out_features, self.in_features)})
+            self._views[e] = lin
+        return lin
+
+    # ------------------------------------------------------------------------------------- forward
+    def forward(self, x: Tensor, expert_ids: Tensor) -> Tensor:
+        if x.dtype != DTYPE_TO_TORCH[self._meta[5]]:
+            raise NotImplementedError(f"GemLiteExperts: x is {x.dtype}, the experts take {DTYPE_TO_TORCH[self._meta[5]]}")
+        if torch.compiler.is_compiling():
+            return forward_experts(x, expert_ids, self.bias, self.get_tensor_args(), self._meta)
+        return _forward_impl(x, expert_ids, self.bias, self.get_tensor_args(), self._meta)

@@ -410,6 +410,36 @@ const char* gemlite_hip_kernel_name_ex(const gemlite_hip_forward_args* args, con
 int gemlite_hip_capture_group_compatible_ex(const gemlite_hip_forward_args* a, const gemlite_hip_forward_ext* ea,
                                              const gemlite_hip_forward_args* b, const gemlite_hip_forward_ext* eb);
 
+/* Experts of a mixture-of-experts layer: ONE launch of n_slots M = 1 GEMVs whose expert ids are read ON THE GPU, so the call can be
+ * captured in a graph once and replayed with other ids.  The E experts are identical layers stacked at fixed byte strides; slot s
+ *   reads x row s / slots_per_x_row (layer.x + row * stride_x_row elements), uses expert e = ids[s] (weights layer.w_q + e * stride_expert_w
+ *   bytes, scales / zero tensor + e * stride_expert_meta, bias + e * stride_expert_bias; a scalar zero is shared by all experts), and
+ *   writes its N outputs at layer.out + s * stride_out_slot elements — bit-identical to the M = 1 decode launch (gemv_w4_decode3_kernel)
+ *   of expert e on that row, with the bias added as gemlite_hip_forward_ex adds it.
+ * An id outside [0, n_experts) — negative, too large, an int64 with a high dword — is never dereferenced: that slot's N outputs are
+ * zeros (no bias) and nothing else is touched (expert-parallel serving marks "not on this rank" with -1).
+ * Domain: W_nbits 4 in 32-bit words; fp16 / bf16 with input = output = scale (= zero tensor) dtype, a scalar zero as INT32;
+ * channel_scale_mode 0; W_group_mode 1..4; group_size a power of two >= 32 that divides K; M = 1; N % 16 == 0; K % 256 == 0; unit inner
+ * strides; 16-byte aligned w_q and x rows, 8-byte aligned metadata, expert strides in multiples of 16 / 8 / 2 bytes (weights / metadata /
+ * bias); 1 <= n_slots <= 65535; inside one expert the 2^32 / 2^31 byte-offset limits of the decode kernel (expert strides are 64-bit).
+ * Everything is validated before the launch: GEMLITE_ERR_BAD_ARGUMENT (null pointers, struct_size, non-positive counts, misaligned
+ * or negative strides), GEMLITE_ERR_UNSUPPORTED (dtypes, bit width, modes, ids dtype, inner strides), GEMLITE_ERR_BAD_SHAPE (M, N, K, group
+ * size, slot count, offset limits).  layer.matmul_type / tuning / workspace are not read.
+ *   gemlite_hip_experts_query   validates and never launches or dereferences; works without a GPU */
+typedef struct gemlite_hip_experts_args {
+    uint32_t struct_size;           /* sizeof(gemlite_hip_experts_args), ABI guard */
+    int32_t ids_dtype;              /* GEMLITE_DT_INT32 | GEMLITE_DT_INT64 */
+    gemlite_hip_forward_args layer; /* expert 0: w_q / scales / zeros / shapes / strides / modes; x = row 0, out = slot 0; M must be 1 */
+    const void* ids;                /* device, n_slots entries */
+    const void* bias;               /* expert 0's bias[N] of the output type, or NULL */
+    int64_t n_slots, n_experts, slots_per_x_row;
+    int64_t stride_expert_w, stride_expert_meta, stride_expert_bias; /* bytes between experts */
+    int64_t stride_x_row, stride_out_slot;                           /* elements */
+    int64_t reserved[2];
+} gemlite_hip_experts_args;
+int gemlite_hip_forward_experts(const gemlite_hip_experts_args* args, void* stream);
+int gemlite_hip_experts_query(const gemlite_hip_experts_args* args);
+
 /* Per-token dynamic activation quantisation: for each row m of x[M,K] (fp16/bf16/fp32)
  *   s[m] = max(amax(|x[m,:]|) / qmax, 1e-6) (fp32);  y = clamp(x / s, qmin, qmax);
  *   int8: round half away from zero;  fp8: round-to-nearest-even cast.
