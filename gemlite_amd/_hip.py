@@ -217,6 +217,22 @@ class ExpertsArgs(C.Structure):
     ]
 
 
+class ExpertsFusedArgs(C.Structure):
+    """struct gemlite_hip_experts_fused_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("epilogue", C.c_int32),
+        ("experts", ExpertsArgs),
+        ("activation", C.c_int32),
+        ("weights_dtype", C.c_int32),
+        ("weights", C.c_void_p),
+        ("slots_per_token", C.c_int64),
+        ("reserved", C.c_int64 * 3),
+    ]
+
+
+EXPERTS_GLU, EXPERTS_COMBINE, ACT_SILU = 1, 2, 1  # gemlite_hip_experts_fused_args.epilogue / .activation
 BIAS_NOT_ADDED = 1  # gemlite_hip_forward_ex: launched without the bias, the caller adds it
 
 _lib = None
@@ -319,6 +335,10 @@ def load():
         lib.gemlite_hip_forward_experts.argtypes = [C.POINTER(ExpertsArgs), C.c_void_p]
         lib.gemlite_hip_experts_query.restype = C.c_int
         lib.gemlite_hip_experts_query.argtypes = [C.POINTER(ExpertsArgs)]
+        lib.gemlite_hip_forward_experts_fused.restype = C.c_int
+        lib.gemlite_hip_forward_experts_fused.argtypes = [C.POINTER(ExpertsFusedArgs), C.c_void_p]
+        lib.gemlite_hip_experts_fused_query.restype = C.c_int
+        lib.gemlite_hip_experts_fused_query.argtypes = [C.POINTER(ExpertsFusedArgs)]
         if lib.gemlite_hip_abi_version() != ABI_VERSION:
             raise GemliteHipError("libgemlite_hip.so ABI version mismatch; rebuild it")
         _lib = lib
@@ -341,6 +361,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize", "gemlite_hip_quantize_groups_hqq",
     "gemlite_hip_quantize_rows",
     "gemlite_hip_forward_experts", "gemlite_hip_experts_query",
+    "gemlite_hip_forward_experts_fused", "gemlite_hip_experts_fused_query",
 )
 
 

@@ -64,6 +64,7 @@ const void* dequantize_words_kernel_fn(int nbits);
 const void* dequantize_rows_kernel_fn(int fmt);
 const void* dequantize_any_kernel_fn();
 const void* gemv_w4_decode3_experts_fn(int tag, bool biased, bool ids64);  // gemv_decode.hip
+const void* gemv_w4_decode3_experts_fused_fn(int tag, int epilogue, bool biased, bool ids64);  // gemv_decode.hip
 // capture_group.hip: independent decode3 (or rows) launches of one stream capture folded into one grouped launch
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
@@ -1301,6 +1302,71 @@ int gemlite_hip_forward_experts(const gemlite_hip_experts_args* args, void* stre
     const int dv = check_device(&dev);
     if (dv != GEMLITE_OK) return dv;
     Decode3Args& d = L.d3;
+    void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
+                     (void*)&d.nch_total, (void*)&d.modes, (void*)&L.tail};
+    return launch(L.fn, L.grid, dim3(1024, 1, 1), kargs, 0, (hipStream_t)stream);
+}
+
+// ---- experts with a fused epilogue (gemv_decode.hip: gemv_w4_decode3_experts_fused_kernel): the nested request by experts_plan's rules,
+// unchanged, then the epilogue's own.  GLU: grid (I / 16, slots), a block holds a slot's gate tile and up tile; COMBINE: grid (N / 16,
+// tokens), a block holds one tile of a token's slots_per_token slots.
+struct ExpertsFusedLaunch {
+    ExpertsLaunch base;
+    ExpertsFusedTail tail;
+    const void* fn;
+    dim3 grid;
+};
+
+static int experts_fused_plan(const gemlite_hip_experts_fused_args* f, ExpertsFusedLaunch& L) {
+    if (!f || f->struct_size != sizeof(gemlite_hip_experts_fused_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    const int v = experts_plan(&f->experts, L.base);
+    if (v != GEMLITE_OK) return v;
+    const gemlite_hip_experts_args& e = f->experts;
+    const int64_t tiles = e.layer.N / 16;
+    L.tail.e = L.base.tail;
+    L.tail.weights = nullptr;
+    L.tail.members = 2;
+    L.tail.half_tiles = 0;
+    L.tail.w_f32 = 0;
+    uint32_t modes = L.base.d3.modes & ~32u;  // (the tile pairing is decided on the tiles of THIS grid)
+    if (f->epilogue == GEMLITE_EXPERTS_GLU) {
+        if (f->activation != GEMLITE_ACT_SILU) return GEMLITE_ERR_UNSUPPORTED;
+        if (e.layer.N % 32 != 0) return GEMLITE_ERR_BAD_SHAPE;
+        const int64_t half = tiles / 2;
+        L.tail.half_tiles = (uint32_t)half;
+        if ((half & 15) == 0) modes |= 32u;
+        L.grid = dim3((unsigned)half, (unsigned)e.n_slots, 1);
+    } else if (f->epilogue == GEMLITE_EXPERTS_COMBINE) {
+        const bool w32 = f->weights_dtype == GEMLITE_DT_FP32;
+        if (!w32 && f->weights_dtype != e.layer.output_dtype) return GEMLITE_ERR_UNSUPPORTED;
+        if (!f->weights || ((uintptr_t)f->weights % (w32 ? 4 : 2)) != 0 || f->slots_per_token <= 0) return GEMLITE_ERR_BAD_ARGUMENT;
+        if (f->slots_per_token > DECODE3_GMAX || e.n_slots % f->slots_per_token != 0) return GEMLITE_ERR_BAD_SHAPE;
+        L.tail.weights = f->weights;
+        L.tail.members = (uint32_t)f->slots_per_token;
+        L.tail.w_f32 = w32 ? 1u : 0u;
+        if ((tiles & 15) == 0) modes |= 32u;
+        L.grid = dim3((unsigned)tiles, (unsigned)(e.n_slots / f->slots_per_token), 1);
+    } else {
+        return GEMLITE_ERR_UNSUPPORTED;
+    }
+    L.base.d3.modes = modes;
+    L.fn = gemv_w4_decode3_experts_fused_fn(e.layer.input_dtype == GEMLITE_DT_FP16 ? 0 : 1, f->epilogue, e.bias != nullptr, e.ids_dtype == GEMLITE_DT_INT64);
+    return GEMLITE_OK;
+}
+
+int gemlite_hip_experts_fused_query(const gemlite_hip_experts_fused_args* args) {
+    ExpertsFusedLaunch L;
+    return experts_fused_plan(args, L);
+}
+
+int gemlite_hip_forward_experts_fused(const gemlite_hip_experts_fused_args* args, void* stream) {
+    ExpertsFusedLaunch L;
+    const int v = experts_fused_plan(args, L);
+    if (v != GEMLITE_OK) return v;
+    int dev = 0;
+    const int dv = check_device(&dev);
+    if (dv != GEMLITE_OK) return dv;
+    Decode3Args& d = L.base.d3;
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                      (void*)&d.nch_total, (void*)&d.modes, (void*)&L.tail};
     return launch(L.fn, L.grid, dim3(1024, 1, 1), kargs, 0, (hipStream_t)stream);

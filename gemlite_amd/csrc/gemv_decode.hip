@@ -16,7 +16,7 @@
 // 16 waves x 64 lanes, lane (g = lane >> 2, c = lane & 3) owns columns 4c .. 4c + 3 of a 16-column tile and packed rows
 // chunk * 512 + wave * 32 + 2 g + {0, 1}.
 //
-// Three kernels, the form of each spelled in its template parameters; they share the device helpers of dec3 (an item's arithmetic, the row
+// Four kernels, the form of each spelled in its template parameters; they share the device helpers of dec3 (an item's arithmetic, the row
 // sums, the final reduction with the bias add and the store), so per layer a group runs the single-layer code in the same order and every
 // layer's output is bit-identical to its own launch:
 //   kernel                                               argument behind the 14 dwords    launched by
@@ -25,6 +25,9 @@
 //   gemv_w4_decode3_group_kernel<Tag, BIASED, SX, HL>    GroupTable<BIASED> by value      capture_group.hip, by rewriting a capture's node
 //   gemv_w4_decode3_experts_kernel<Tag, BIASED, IDS64>   ExpertsTail by value             gemlite_hip_forward_experts (api.hip): the single-layer
 //                                                                                         block per (tile, slot), the expert id read on the GPU
+//   gemv_w4_decode3_experts_fused_kernel<Tag, BIASED,    ExpertsFusedTail by value        gemlite_hip_forward_experts_fused (api.hip): several
+//                                        IDS64, EPI>                                      (expert, tile) members per block, SwiGLU or the
+//                                                                                         routing-weight sum in the epilogue
 //     BIASED  the bias add in the epilogue (gl_common.h has the arithmetic); the lanes that store ask for their bias element in front of
 //             the barrier, so it arrives under the reduction
 //     SX      SHARED X, for a group whose members all read the same x.  What a lane derives from x — the pair dwords (x0,x4)(x1,x5)(x2,x6)
@@ -606,6 +609,219 @@ void gemv_w4_decode3_experts_kernel(const char* wb, const char* xb, const char* 
     if ((lane & 12) == 0) *(f32x4*)(red + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
     __syncthreads();
     if (wave == 0) finish<Tag, BIASED>(red, braw, out, tile);
+}
+
+namespace dec3 {
+// finish() up to the store: the member's rounded 16-bit output of column lane & 15, in every lane (the same sums in the same order)
+template <typename Tag, bool BIASED>
+__device__ __forceinline__ uint16_t finish_value(const float* red, uint16_t braw) {
+    using TR = F16Traits<Tag>;
+    const int lane = threadIdx.x & 63;
+    constexpr int PER = NW;
+    const int o = lane & 15, part = lane >> 4;
+    float v = 0.f;
+#pragma unroll
+    for (int r = 0; r < PER; ++r) v += red[(part * PER + r) * TC + o];
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    uint16_t h = TR::from_float(v);
+    if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));
+    return h;
+}
+}  // namespace dec3
+
+// The fused epilogues of an expert MLP (gemlite_hip_forward_experts_fused): a block holds several MEMBERS — (expert, tile) pairs — that
+// share its 16 waves the way the layers of a grouped block do with H = 1 and per-wave x: decode3_wave_split(members, wave) gives a wave
+// its member and its virtual waves [v0, v1); virtual wave v is the chunks v, v + 16, ... in ascending order, flushed with row_sum to the
+// partial rows v * 4 + r of the member's own 4 KiB of LDS (a virtual wave without a chunk writes zeros); after one barrier a member's
+// region is summed in finish()'s order.  So a member's rounded output is bit-identical to that expert's own gemv_w4_decode3_kernel
+// launch, and to its slot of gemv_w4_decode3_experts_kernel.  The member's bases are computed by the wave from the id it loads itself
+// (a scalar load; 64-bit scalar arithmetic on base + id * stride, 32-bit offsets inside an expert), the loop is the experts kernel's
+// two-chunk double buffer over the wave's flat item list.
+//   EPI = GEMLITE_EXPERTS_GLU      grid (I / 16, slots), I = N / 2: block (t, s) holds tile t (gate, columns [0, I)) and tile t + I / 16
+//                                  (up, columns [I, 2 I)) of expert ids[s] on x row s / slots_per_x_row, 8 waves each; with g16 / u16 the
+//                                  members' rounded outputs (bias included) wave 0 stores from_float(silu(g16) * u16), silu(v) =
+//                                  v / (1 + exp(-v)) in fp32.  An invalid id: the block stores 16 zeros and leaves (block-uniform).
+//   EPI = GEMLITE_EXPERTS_COMBINE  grid (N / 16, tokens): block (t, tok) holds tile t of the slots tok * spt + k, k < spt <= 16, each with
+//                                  its own id, x row and bias row.  A member with an invalid id requests nothing (its waves go straight to
+//                                  the barrier, uniform per wave) and contributes exactly 0.  Wave k rounds member k as finish() does and
+//                                  leaves w[slot_k] * to_float(y16_k) in LDS; behind a second barrier wave 0 adds the products in
+//                                  ascending k from 0.f and stores one rounded row per token.
+template <typename Tag, bool BIASED, bool IDS64, int EPI>
+__global__ __launch_bounds__(1024, 1)
+void gemv_w4_decode3_experts_fused_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
+                                          uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes, const ExpertsFusedTail tail) {
+    using namespace dec3;
+    using TR = F16Traits<Tag>;
+    constexpr bool GLU = EPI == GEMLITE_EXPERTS_GLU;
+    __shared__ __attribute__((aligned(16))) float red[(GLU ? 2 : DECODE3_GMAX) * RED];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 3, g = lane >> 2;
+    int tile = blockIdx.x;  // GLU: of the I / 16 tiles of one half
+    if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
+        const int xcd = tile & 7, idx = tile >> 3;
+        tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
+    }
+    const int members = GLU ? 2 : (int)tail.members;
+    auto load_id = [&](uint32_t slot) -> uint64_t {
+        // (int32: a negative id is >= 2^31 as unsigned and n_experts is below 2^31; int64: the high dword takes part in the comparison)
+        if constexpr (IDS64) {
+            return (uint64_t)((const int64_t*)tail.e.ids)[slot];
+        } else {
+            return (uint64_t)(uint32_t)((const int32_t*)tail.e.ids)[slot];
+        }
+    };
+    const Decode3WaveSplit split = decode3_wave_split(members, wave);
+    const int li = split.layer < 0 ? 0 : split.layer;
+    // this wave's member: its slot (GLU: the block's), its tile (GLU: the up half lies I / 16 tiles further)
+    const uint32_t slot = GLU ? blockIdx.y : blockIdx.y * (uint32_t)members + (uint32_t)li;
+    const int mtile = GLU ? tile + li * (int)tail.half_tiles : tile;
+    const uint64_t e = load_id(slot);
+    out += (uint64_t)blockIdx.y * (uint64_t)tail.e.stride_out;
+    if constexpr (GLU) {
+        if (e >= (uint64_t)tail.e.n_experts) {
+            if (tid < TC) out[tile * TC + tid] = 0;
+            return;
+        }
+    }
+    float* const rd = red + li * RED;
+
+    if (split.layer >= 0 && e < (uint64_t)tail.e.n_experts) {
+        wb += e * (uint64_t)tail.e.stride_w;
+        sp += e * (uint64_t)tail.e.stride_meta;
+        if (!(modes & M_ZSCALAR)) zp += e * (uint64_t)tail.e.stride_meta;  // (one scalar zero is shared by all experts)
+        xb += (uint64_t)(slot / tail.e.slots_per_x_row) * (uint64_t)tail.e.stride_x;
+
+        const uint32_t n0 = (uint32_t)(mtile * TC + c * 4);
+        const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
+        const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
+        const uint32_t wo0 = (uint32_t)(g * R) * sw4 + n0 * 4u;  // this lane's first row of chunk 0
+        const uint32_t xo0 = (uint32_t)lane * 8u;                 // a chunk's 512 bytes of x, 8 per lane
+
+        // chunk gc of the member: the packed rows gc * 32 .. gc * 32 + 31 (the single-layer wave gc & 15 reads them as its chunk gc >> 4)
+        auto load_chunk = [&](Chunk& ck, int gc) {
+            const uint32_t wo = wo0 + (uint32_t)(gc * CHUNK) * sw4;
+#pragma unroll
+            for (int i = 0; i < R; ++i) ck.w[i] = __builtin_nontemporal_load((const u32x4*)(wb + (wo + (uint32_t)i * sw4)));
+            ck.xq = *(const u32x2*)(xb + (xo0 + (uint32_t)(gc * CHUNK) * 16u));
+            const uint32_t row = (uint32_t)(gc * CHUNK + g * R);
+            const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
+            // (absent metadata is still "loaded" — from the expert's weights, always in bounds — so the loop stays branch-free)
+            ck.s = *(const u32x2*)((need_s ? sp : wb) + (need_s ? mo : 0u));
+            ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
+        };
+        // the wave's items: its virtual waves in ascending order, each one's chunks in ascending order (a virtual wave >= nch_total has none)
+        const int v0 = split.v0, v1 = split.v1, nv = v1 - v0, rem = (nch_total & (NW - 1)) - v0;
+        const int n = (nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem));
+        int rv = v0, rgc = v0;  // request cursor: virtual wave, chunk
+        auto request = [&](Chunk& ck) {
+            load_chunk(ck, rgc);
+            rgc += NW;
+            if (rgc >= nch_total) rgc = ++rv;
+        };
+        Chunk cur, nxt;
+        if (n > 0) request(cur);
+        if (n > 1) request(nxt);
+
+        float tot[4] = {0.f, 0.f, 0.f, 0.f};
+        const float scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
+        const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
+        const bool b_times_s = w_mode == 3;
+        uint32_t wmask[Item<Tag, false>::WP];
+#pragma unroll
+        for (int i = 0; i < Item<Tag, false>::WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
+        const Item<Tag, false> item{{}, wmask, need_s, need_z, scalar_zero, bz, b_times_s, tot};
+        // a virtual wave's end, the single-layer code: DPP row sums, the partial row to the member's LDS region
+        auto flush = [&](int v) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) tot[j] = row_sum(tot[j]);
+            if ((lane & 12) == 0) *(f32x4*)(rd + ((v * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) tot[j] = 0.f;
+        };
+        int cv = v0, cgc = v0;  // compute cursor
+#pragma unroll 1
+        for (int it = 0; it < n; ++it) {
+            item.template run<false>(cur);
+            cgc += NW;
+            if (cgc >= nch_total) {
+                flush(cv);
+                cgc = ++cv;
+            }
+            if (it + 1 < n) {
+                cur = nxt;
+                if (it + 2 < n) request(nxt);
+            }
+        }
+#pragma unroll 1
+        for (int v = cv; v < v1; ++v) flush(v);  // virtual waves without a chunk still write their rows
+    }
+
+    if constexpr (GLU) {
+        // wave 0 finishes both members; it asks for their bias elements in front of the barrier
+        uint16_t bg = 0, bu = 0;
+        if constexpr (BIASED) {
+            if (wave == 0 && lane < 16) {
+                const uint16_t* b = (const uint16_t*)((const char*)tail.e.bias + e * (uint64_t)tail.e.stride_bias);
+                bg = b[tile * TC + lane];
+                bu = b[(tile + (int)tail.half_tiles) * TC + lane];
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const float gv = TR::to_float(finish_value<Tag, BIASED>(red, bg));
+            const float uv = TR::to_float(finish_value<Tag, BIASED>(red + RED, bu));
+            const float act = gv / (1.f + expf(-gv));
+            if (lane < 16) out[tile * TC + lane] = TR::from_float(act * uv);
+        }
+    } else {
+        // waves 0 .. members - 1 finish one member each: the id again (a scalar load), the routing weight, the bias element
+        const bool fin = wave < members;
+        bool fvalid = false;
+        float wk = 0.f;
+        uint16_t braw = 0;
+        if (fin) {
+            const uint32_t fslot = blockIdx.y * (uint32_t)members + (uint32_t)wave;
+            const uint64_t ef = load_id(fslot);
+            fvalid = ef < (uint64_t)tail.e.n_experts;
+            if (fvalid) {
+                wk = tail.w_f32 ? ((const float*)tail.weights)[fslot] : TR::to_float(((const uint16_t*)tail.weights)[fslot]);
+                if constexpr (BIASED) {
+                    if (lane < 16) braw = ((const uint16_t*)((const char*)tail.e.bias + ef * (uint64_t)tail.e.stride_bias))[tile * TC + lane];
+                }
+            }
+        }
+        __syncthreads();
+        if (fin) {
+            // (the product is rounded on its own, in the wave that holds the weight; row 0 of the member's region carries it: the wave's
+            // reads of the region are in front of this write in its own LDS queue, and no other wave touches the region)
+            float p = 0.f;
+            if (fvalid) p = wk * TR::to_float(finish_value<Tag, BIASED>(red + wave * RED, braw));
+            if (lane < 16) red[wave * RED + lane] = p;
+        }
+        __syncthreads();
+        if (wave == 0 && lane < 16) {
+            float acc = 0.f;
+#pragma unroll 1
+            for (int k = 0; k < members; ++k) acc += red[k * RED + lane];
+            out[tile * TC + lane] = TR::from_float(acc);
+        }
+    }
+}
+
+// tag: 0 fp16 | 1 bf16
+template <typename Tag, int EPI>
+static const void* decode3_experts_fused_pick(bool biased, bool ids64) {
+    return biased ? (ids64 ? (const void*)gemv_w4_decode3_experts_fused_kernel<Tag, true, true, EPI> : (const void*)gemv_w4_decode3_experts_fused_kernel<Tag, true, false, EPI>)
+                  : (ids64 ? (const void*)gemv_w4_decode3_experts_fused_kernel<Tag, false, true, EPI> : (const void*)gemv_w4_decode3_experts_fused_kernel<Tag, false, false, EPI>);
+}
+const void* gemv_w4_decode3_experts_fused_fn(int tag, int epilogue, bool biased, bool ids64) {
+    if (epilogue == GEMLITE_EXPERTS_GLU)
+        return tag == 0 ? decode3_experts_fused_pick<half_tag, GEMLITE_EXPERTS_GLU>(biased, ids64) : decode3_experts_fused_pick<bf16_tag, GEMLITE_EXPERTS_GLU>(biased, ids64);
+    return tag == 0 ? decode3_experts_fused_pick<half_tag, GEMLITE_EXPERTS_COMBINE>(biased, ids64)
+                    : decode3_experts_fused_pick<bf16_tag, GEMLITE_EXPERTS_COMBINE>(biased, ids64);
 }
 
 // tag: 0 fp16 | 1 bf16

@@ -625,6 +625,15 @@ struct ExpertsTail {
     int64_t stride_x, stride_out;                // between x rows / output slots
     uint32_t n_experts, slots_per_x_row;
 };
+// gemv_w4_decode3_experts_fused_kernel (gemlite_hip_forward_experts_fused): the experts tail, then what the epilogue needs.  stride_out is
+// between the output rows of the launch: slots (GLU) or tokens (COMBINE)
+struct ExpertsFusedTail {
+    ExpertsTail e;
+    const void* weights;  // COMBINE: the routing weights, n_slots entries in the order of ids; fp32 (w_f32) or the output type
+    uint32_t members;     // COMBINE: slots per token = members of a block, 1 .. DECODE3_GMAX
+    uint32_t half_tiles;  // GLU: I / 16, the tiles between a block's gate tile and its up tile
+    uint32_t w_f32;
+};
 template <bool BIASED>
 struct GroupTable {
     GroupMember m[DECODE3_GMAX - 1];

@@ -7,6 +7,10 @@ tensor (scales / zeros ``[E, K/g, N]``, bias ``[E, N]``) and runs ``gemlite_hip_
 by the kernel, so the call can be captured once and replayed with other ids.  An id outside ``[0, E)`` (-1: "not on this rank") gives a
 row of zeros.  Domain: DESIGN.md §3.1.3 — 4-bit weights in 32-bit words, fp16 / bf16, grouped scales / zeros, N % 16 == 0, K % 256 == 0.
 There is no slow path: layers outside the domain are refused by ``from_layers``.
+
+``GemLiteExpertsMLP`` runs a whole expert MLP in two such launches (``gemlite_hip_forward_experts_fused``):
+``gate_up.forward_glu`` stores ``silu(gate) * up`` of experts stacked ``[gate; up]`` along N, ``down.forward_combine`` stores the
+routing-weight sum over a token's slots.  Every member is rounded as its slot of ``forward``; the epilogues run in fp32 on those values.
 """
 import threading
 from typing import List, Optional, Sequence
@@ -122,8 +126,94 @@ def _forward_experts_fake(x, expert_ids, bias, tensor_args, meta_args):
     return torch.empty(tuple(expert_ids.shape) + (W_q.shape[2],), device=x.device, dtype=x.dtype)
 
 
+# ---- the fused epilogues (gemlite_hip_forward_experts_fused): GLU on the gate/up launch, the routing-weight combine on the down launch ----
+def _fused_args(e: "_hip.ExpertsArgs", epilogue: int, weights_ptr: int = 0, weights_dtype: int = 0, slots_per_token: int = 0):
+    f = _hip.ExpertsFusedArgs()
+    f.struct_size = _hip.C.sizeof(_hip.ExpertsFusedArgs)
+    f.epilogue = epilogue
+    f.experts = e
+    f.activation = _hip.ACT_SILU
+    f.weights_dtype = weights_dtype
+    f.weights = weights_ptr or None
+    f.slots_per_token = slots_per_token
+    return f
+
+
+def _weights_like(weights: Tensor, expert_ids: Tensor, x: Tensor):
+    if tuple(weights.shape) != tuple(expert_ids.shape):
+        raise ValueError(f"weights are {tuple(weights.shape)}, expert_ids {tuple(expert_ids.shape)}: one weight per slot")
+    if weights.dtype not in (torch.float32, x.dtype):
+        raise NotImplementedError(f"weights are {weights.dtype}: float32 or {x.dtype}")
+
+
+def _fused_impl(epilogue: int, x: Tensor, expert_ids: Tensor, weights: Optional[Tensor], bias: Optional[Tensor],
+                tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    W_q = tensor_args[0]
+    N, K = W_q.shape[2], W_q.shape[1] * meta_args[4]
+    glu = epilogue == _hip.EXPERTS_GLU
+    lib = _hip.load()
+    tensors = ((x, "x"), (expert_ids, "expert_ids"), (W_q, "W_q")) + (() if glu else ((weights, "weights"),))
+    for t, name in tensors:
+        _hip.require_gpu_tensor(t, name)
+    if any(t.device != W_q.device for t, _ in tensors):
+        raise _hip.GemliteHipError("x, expert_ids, weights and the packed weights live on different devices: "
+                                   + ", ".join(f"{name} on {t.device}" for t, name in tensors))
+    if expert_ids.dtype not in (torch.int32, torch.int64):
+        raise NotImplementedError(f"expert_ids are {expert_ids.dtype}: int32 or int64")
+    rows, spx = _split(x, expert_ids, K)
+    if glu:
+        width = N // 2
+        out = torch.empty(tuple(expert_ids.shape) + (width,), dtype=x.dtype, device=x.device)
+    else:
+        _weights_like(weights, expert_ids, x)
+        width = N
+        out = torch.empty(tuple(expert_ids.shape[:-1]) + (width,), dtype=x.dtype, device=x.device)
+    if expert_ids.numel() == 0:
+        return out.zero_()  # (COMBINE with top_k = 0: a sum without terms)
+    x2 = x.contiguous().view(rows, K)
+    ids = expert_ids.contiguous()
+    e = _call_args(x2, ids, out.data_ptr(), bias, tensor_args, meta_args, spx)
+    e.stride_out_slot = width
+    if glu:
+        f = _fused_args(e, epilogue)
+    else:
+        w = weights.contiguous()
+        f = _fused_args(e, epilogue, w.data_ptr(), TORCH_TO_DTYPE[w.dtype].value, expert_ids.shape[-1])
+    with _hip.on_device(x.device):
+        rc = lib.gemlite_hip_forward_experts_fused(_hip.C.byref(f), _hip.current_stream_handle(x.device))
+    _hip.raise_for_status(rc, "gemlite_hip_forward_experts_fused")
+    return out
+
+
+@torch.library.custom_op("gemlite::forward_experts_glu", mutates_args=())
+def forward_experts_glu(x: Tensor, expert_ids: Tensor, bias: Optional[Tensor], tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    return _fused_impl(_hip.EXPERTS_GLU, x, expert_ids, None, bias, tensor_args, meta_args)
+
+
+@torch.library.register_fake("gemlite::forward_experts_glu")
+def _forward_experts_glu_fake(x, expert_ids, bias, tensor_args, meta_args):
+    W_q = tensor_args[0]
+    _split(x, expert_ids, W_q.shape[1] * meta_args[4])
+    return torch.empty(tuple(expert_ids.shape) + (W_q.shape[2] // 2,), device=x.device, dtype=x.dtype)
+
+
+@torch.library.custom_op("gemlite::forward_experts_combine", mutates_args=())
+def forward_experts_combine(x: Tensor, expert_ids: Tensor, weights: Tensor, bias: Optional[Tensor], tensor_args: List[Tensor],
+                            meta_args: List[int]) -> Tensor:
+    return _fused_impl(_hip.EXPERTS_COMBINE, x, expert_ids, weights, bias, tensor_args, meta_args)
+
+
+@torch.library.register_fake("gemlite::forward_experts_combine")
+def _forward_experts_combine_fake(x, expert_ids, weights, bias, tensor_args, meta_args):
+    W_q = tensor_args[0]
+    _split(x, expert_ids, W_q.shape[1] * meta_args[4])
+    _weights_like(weights, expert_ids, x)
+    return torch.empty(tuple(expert_ids.shape[:-1]) + (W_q.shape[2],), device=x.device, dtype=x.dtype)
+
+
 class GemLiteExperts(torch.nn.Module):
-    """E stacked A16W4 layers; ``experts(x, expert_ids)`` -> ``[..., top_k, N]`` in one launch (module docstring)."""
+    """E stacked A16W4 layers; ``experts(x, expert_ids)`` -> ``[..., top_k, N]`` in one launch (module docstring).
+    ``forward_glu`` / ``forward_combine`` are the same launch with the rest of an expert MLP in its epilogue (GemLiteExpertsMLP)."""
 
     def __init__(self):
         super().__init__()
@@ -131,11 +221,12 @@ class GemLiteExperts(torch.nn.Module):
         self.metadata = self.orig_shape = self.n_experts = None
         self._meta: List[int] = []
         self._views: dict = {}
+        self._fused_ok: dict = {}
 
     # ---------------------------------------------------------------------------------------- build
-    @classmethod
-    def from_layers(cls, layers: Sequence["core.GemLiteLinearHIP"], del_orig: bool = False) -> "GemLiteExperts":
-        layers = list(layers)
+    @staticmethod
+    def _check_same(layers: list) -> list:
+        """-> the meta args all `layers` share; refuses layers that differ in them or in the shape, dtype or device of a tensor."""
         if not layers:
             raise ValueError("from_layers needs at least one layer")
         first = layers[0]
@@ -157,14 +248,51 @@ class GemLiteExperts(torch.nn.Module):
                     raise ValueError(f"layer {i} differs from layer 0 in the shape, dtype or device of `{name}`")
         if first.zeros.numel() == 1 and any(int(l.zeros) != int(first.zeros) for l in layers[1:]):
             raise ValueError("the layers carry different scalar zeros: one scalar zero is shared by all experts")
+        return meta
 
-        self = cls()
-        self._meta = [int(v) for v in meta]
+    @classmethod
+    def from_layers(cls, layers: Sequence["core.GemLiteLinearHIP"], del_orig: bool = False) -> "GemLiteExperts":
+        layers = list(layers)
+        meta = cls._check_same(layers)
+        first = layers[0]
         stack = lambda name: torch.stack([getattr(l, name).data for l in layers]).contiguous()  # noqa: E731
         W_q = stack("W_q")
         scales = stack("scales") if first.scales.numel() > 0 else first.scales.data
         zeros = stack("zeros") if first.zeros.numel() > 1 else first.zeros.data
         bias = None if first.bias is None else stack("bias")
+        self = cls._from_stacked(meta, W_q, scales, zeros, bias, first.out_features, first.in_features)
+        if del_orig:
+            for layer in layers:
+                layer.W_q = layer.scales = layer.zeros = layer.bias = None
+        return self
+
+    @classmethod
+    def from_gate_up(cls, gate_layers: Sequence["core.GemLiteLinearHIP"], up_layers: Sequence["core.GemLiteLinearHIP"],
+                     del_orig: bool = False) -> "GemLiteExperts":
+        """Experts whose layer e is gate e and up e side by side along N — columns [0, I) the gate, [I, 2 I) the up, the w13 layout
+        ``forward_glu`` reads.  The packing runs along K, so the packed words, scales, zeros and bias concatenate on their last axis."""
+        gate_layers, up_layers = list(gate_layers), list(up_layers)
+        if len(gate_layers) != len(up_layers):
+            raise ValueError(f"{len(gate_layers)} gate layers, {len(up_layers)} up layers")
+        meta = cls._check_same(gate_layers + up_layers)
+        first = gate_layers[0]
+        pair = lambda name: torch.stack([torch.cat([getattr(g, name).data, getattr(u, name).data], dim=-1)  # noqa: E731
+                                         for g, u in zip(gate_layers, up_layers)]).contiguous()
+        W_q = pair("W_q")
+        scales = pair("scales") if first.scales.numel() > 0 else first.scales.data
+        zeros = pair("zeros") if first.zeros.numel() > 1 else first.zeros.data
+        bias = None if first.bias is None else pair("bias")
+        self = cls._from_stacked(meta, W_q, scales, zeros, bias, 2 * first.out_features, first.in_features)
+        if del_orig:
+            for layer in gate_layers + up_layers:
+                layer.W_q = layer.scales = layer.zeros = layer.bias = None
+        return self
+
+    @classmethod
+    def _from_stacked(cls, meta, W_q: Tensor, scales: Tensor, zeros: Tensor, bias: Optional[Tensor], out_features: int,
+                      in_features: int) -> "GemLiteExperts":
+        self = cls()
+        self._meta = [int(v) for v in meta]
         self._check_domain(W_q, scales, zeros, bias)
         as_param = lambda t: torch.nn.Parameter(t, requires_grad=False)  # noqa: E731
         dev = W_q.device
@@ -172,17 +300,15 @@ class GemLiteExperts(torch.nn.Module):
         self.bias = None if bias is None else as_param(bias)
         self.scales, self.zeros = as_param(scales), as_param(zeros)
         self.metadata = as_param(torch.tensor(self._meta, device=dev, dtype=torch.int32))
-        self.orig_shape = as_param(torch.tensor([first.out_features, first.in_features], device=dev, dtype=torch.int32))
-        self.n_experts = as_param(torch.tensor(len(layers), device=dev, dtype=torch.int32))
-        self._set_shapes(first.out_features, first.in_features, len(layers))
-        if del_orig:
-            for layer in layers:
-                layer.W_q = layer.scales = layer.zeros = layer.bias = None
+        self.orig_shape = as_param(torch.tensor([out_features, in_features], device=dev, dtype=torch.int32))
+        self.n_experts = as_param(torch.tensor(W_q.shape[0], device=dev, dtype=torch.int32))
+        self._set_shapes(out_features, in_features, W_q.shape[0])
         return self
 
     def _set_shapes(self, out_features: int, in_features: int, n: int):
         self.out_features, self.in_features, self.num_experts = int(out_features), int(in_features), int(n)
         self._views = {}
+        self._fused_ok = {}
 
     def _check_domain(self, W_q: Tensor, scales: Tensor, zeros: Tensor, bias: Optional[Tensor]):
         """The library's own answer (gemlite_hip_experts_query plans and never launches, with or without a GPU), on the stacked tensors
@@ -254,3 +380,83 @@ class GemLiteExperts(torch.nn.Module):
         if torch.compiler.is_compiling():
             return forward_experts(x, expert_ids, self.bias, self.get_tensor_args(), self._meta)
         return _forward_impl(x, expert_ids, self.bias, self.get_tensor_args(), self._meta)
+
+    def _check_fused(self, epilogue: int, top_k: int):
+        """The library's answer for a fused epilogue on these experts (gemlite_hip_experts_fused_query on stand-ins, as _check_domain asks
+        it), once per (epilogue, top_k), in words."""
+        rc = self._fused_ok.get((epilogue, top_k))
+        if rc is None:
+            e = _static_args(self.W_q, self.scales, self.zeros, self.bias, self._meta)
+            e.layer.x = e.layer.out = e.ids = 0x1000
+            e.layer.stride_xm = e.stride_x_row = e.layer.K
+            e.ids_dtype = DType.INT32.value
+            e.n_slots, e.slots_per_x_row = max(top_k, 1), 1
+            e.stride_out_slot = e.layer.N
+            f = _fused_args(e, epilogue, 0x1000, DType.FP32.value, top_k)
+            rc = self._fused_ok[(epilogue, top_k)] = _hip.load().gemlite_hip_experts_fused_query(_hip.C.byref(f))
+        if rc != _hip.OK:
+            what = (f"forward_glu: N={self.out_features} (domain: N % 32 == 0, the [gate; up] halves in whole 16-column tiles)"
+                    if epilogue == _hip.EXPERTS_GLU else f"forward_combine: top_k={top_k} (domain: 1 <= top_k <= 16; top_k > 16 is not fused)")
+            raise NotImplementedError(f"GemLiteExperts.{what}: {_hip.status_string(rc)}")
+
+    def _check_x(self, x: Tensor):
+        if x.dtype != DTYPE_TO_TORCH[self._meta[5]]:
+            raise NotImplementedError(f"GemLiteExperts: x is {x.dtype}, the experts take {DTYPE_TO_TORCH[self._meta[5]]}")
+
+    def forward_glu(self, x: Tensor, expert_ids: Tensor) -> Tensor:
+        """-> ``[..., top_k, N // 2]``: ``silu(y[..., :I]) * y[..., I:]`` of ``y = forward(x, expert_ids)``, in the same one launch."""
+        self._check_x(x)
+        if torch.compiler.is_compiling():
+            return forward_experts_glu(x, expert_ids, self.bias, self.get_tensor_args(), self._meta)
+        self._check_fused(_hip.EXPERTS_GLU, 1)
+        return _fused_impl(_hip.EXPERTS_GLU, x, expert_ids, None, self.bias, self.get_tensor_args(), self._meta)
+
+    def forward_combine(self, x: Tensor, expert_ids: Tensor, weights: Tensor) -> Tensor:
+        """-> ``[..., N]``: ``(forward(x, expert_ids) * weights.unsqueeze(-1)).sum(-2)`` with an fp32 sum, in the same one launch."""
+        self._check_x(x)
+        if expert_ids.dim() < 1:
+            raise ValueError("expert_ids should be [..., top_k]")
+        if torch.compiler.is_compiling():
+            return forward_experts_combine(x, expert_ids, weights, self.bias, self.get_tensor_args(), self._meta)
+        self._check_fused(_hip.EXPERTS_COMBINE, max(int(expert_ids.shape[-1]), 1))
+        return _fused_impl(_hip.EXPERTS_COMBINE, x, expert_ids, weights, self.bias, self.get_tensor_args(), self._meta)
+
+
+class GemLiteExpertsMLP(torch.nn.Module):
+    """The expert MLP of a mixture-of-experts layer in two launches: ``mlp(x, topk_ids, topk_weights)`` -> ``[..., hidden]`` is
+    ``down.forward_combine(gate_up.forward_glu(x, ids), ids, w)``.  ``gate_up`` holds [gate; up] along N (GemLiteExperts.from_gate_up).
+    Without arguments: an empty module for ``load_state_dict``."""
+
+    def __init__(self, gate_up: Optional[GemLiteExperts] = None, down: Optional[GemLiteExperts] = None):
+        super().__init__()
+        if (gate_up is None) != (down is None):
+            raise ValueError("GemLiteExpertsMLP takes both gate_up and down, or neither (load_state_dict fills them)")
+        self.gate_up = GemLiteExperts() if gate_up is None else gate_up
+        self.down = GemLiteExperts() if down is None else down
+        if gate_up is not None:
+            self._check()
+
+    def _check(self):
+        g, d = self.gate_up, self.down
+        if g.out_features != 2 * d.in_features:
+            raise ValueError(f"gate_up has {g.out_features} outputs, down {d.in_features} inputs: gate_up.out_features == 2 * down.in_features")
+        if d.out_features != g.in_features:
+            raise ValueError(f"down has {d.out_features} outputs, gate_up {g.in_features} inputs: the MLP maps hidden to hidden")
+        if g.num_experts != d.num_experts:
+            raise ValueError(f"gate_up holds {g.num_experts} experts, down {d.num_experts}")
+        if g.get_meta_args()[5] != d.get_meta_args()[5] or g.W_q.device != d.W_q.device:
+            raise ValueError("gate_up and down differ in dtype or device")
+        self.hidden_size, self.intermediate_size, self.num_experts = g.in_features, d.in_features, g.num_experts
+
+    @classmethod
+    def from_layers(cls, gate_layers, up_layers, down_layers, del_orig: bool = False) -> "GemLiteExpertsMLP":
+        return cls(GemLiteExperts.from_gate_up(gate_layers, up_layers, del_orig), GemLiteExperts.from_layers(down_layers, del_orig))
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        for name in ("gate_up", "down"):
+            prefix = name + "."
+            getattr(self, name).load_state_dict({k[len(prefix):]: state_dict.pop(k) for k in list(state_dict) if k.startswith(prefix)})
+        self._check()
+
+    def forward(self, x: Tensor, topk_ids: Tensor, topk_weights: Tensor) -> Tensor:
+        return self.down.forward_combine(self.gate_up.forward_glu(x, topk_ids), topk_ids, topk_weights)

@@ -440,6 +440,37 @@ typedef struct gemlite_hip_experts_args {
 int gemlite_hip_forward_experts(const gemlite_hip_experts_args* args, void* stream);
 int gemlite_hip_experts_query(const gemlite_hip_experts_args* args);
 
+/* The same launch with the rest of an expert MLP fused into its epilogue: an expert MLP is two launches, gate/up (GLU) and down (COMBINE).
+ * `experts` is a complete gemlite_hip_forward_experts request (its own struct_size set) and is validated by the same rules first; every
+ * member (slot, 16-column tile) is computed and rounded exactly as gemlite_hip_forward_experts computes it, bias included.
+ *   GEMLITE_EXPERTS_GLU      the N columns of an expert are [gate; up] halves of I = N / 2 columns (the w13 layout of HF / vLLM
+ *                            checkpoints).  With g, u the rounded gate / up outputs of slot s, its I outputs at experts.layer.out +
+ *                            s * stride_out_slot are round(silu(g) * u), silu(v) = v / (1 + exp(-v)) in fp32, one rounding.  A slot whose
+ *                            id is outside [0, n_experts) gets I zeros.
+ *   GEMLITE_EXPERTS_COMBINE  token t = the slots t * slots_per_token + k, k < slots_per_token, each with its own id, x row
+ *                            (slot / slots_per_x_row) and bias row.  With y_k the rounded output of slot k its N outputs at experts.layer.out
+ *                            + t * stride_out_slot are round(sum_k weights[slot_k] * y_k): fp32, ascending k from 0, one rounding.  A slot
+ *                            with an invalid id is never dereferenced and contributes exactly 0; a token without a valid id gets N zeros.
+ * Refusals beyond those of the nested request: GEMLITE_ERR_BAD_ARGUMENT (null struct, struct_size, COMBINE: null or misaligned weights,
+ * slots_per_token <= 0), GEMLITE_ERR_UNSUPPORTED (epilogue, activation, weights_dtype), GEMLITE_ERR_BAD_SHAPE (GLU: N % 32 != 0; COMBINE:
+ * slots_per_token > 16 or not a divisor of n_slots).  Fields of the other epilogue are not read.
+ *   gemlite_hip_experts_fused_query   validates and never launches or dereferences; works without a GPU */
+#define GEMLITE_EXPERTS_GLU 1
+#define GEMLITE_EXPERTS_COMBINE 2
+#define GEMLITE_ACT_SILU 1
+typedef struct gemlite_hip_experts_fused_args {
+    uint32_t struct_size;             /* sizeof(gemlite_hip_experts_fused_args), ABI guard */
+    int32_t epilogue;                 /* GEMLITE_EXPERTS_GLU | GEMLITE_EXPERTS_COMBINE */
+    gemlite_hip_experts_args experts; /* exactly as for gemlite_hip_forward_experts */
+    int32_t activation;               /* GLU: GEMLITE_ACT_SILU */
+    int32_t weights_dtype;            /* COMBINE: GEMLITE_DT_FP32 or the output dtype */
+    const void* weights;              /* COMBINE: device, n_slots entries in the order of ids */
+    int64_t slots_per_token;          /* COMBINE: 1..16, divides n_slots */
+    int64_t reserved[3];
+} gemlite_hip_experts_fused_args;
+int gemlite_hip_forward_experts_fused(const gemlite_hip_experts_fused_args* args, void* stream);
+int gemlite_hip_experts_fused_query(const gemlite_hip_experts_fused_args* args);
+
 /* Per-token dynamic activation quantisation: for each row m of x[M,K] (fp16/bf16/fp32)
  *   s[m] = max(amax(|x[m,:]|) / qmax, 1e-6) (fp32);  y = clamp(x / s, qmin, qmax);
  *   int8: round half away from zero;  fp8: round-to-nearest-even cast.
