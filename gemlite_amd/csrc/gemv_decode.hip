@@ -641,7 +641,7 @@ __device__ __forceinline__ uint16_t finish_value(const float* red, uint16_t braw
 //   EPI = GEMLITE_EXPERTS_GLU      grid (I / 16, slots), I = N / 2: block (t, s) holds tile t (gate, columns [0, I)) and tile t + I / 16
 //                                  (up, columns [I, 2 I)) of expert ids[s] on x row s / slots_per_x_row, 8 waves each; with g16 / u16 the
 //                                  members' rounded outputs (bias included) wave 0 stores from_float(silu(g16) * u16), silu(v) =
-//                                  v / (1 + exp(-v)) in fp32.  An invalid id: the block stores 16 zeros and leaves (block-uniform).
+//                                  v / (1 + exp(-v)) in fp32 (v exp(v / 2) exp(v / 2) below -88, where exp(-v) overflows).  An invalid id: the block stores 16 zeros and leaves (block-uniform).
 //   EPI = GEMLITE_EXPERTS_COMBINE  grid (N / 16, tokens): block (t, tok) holds tile t of the slots tok * spt + k, k < spt <= 16, each with
 //                                  its own id, x row and bias row.  A member with an invalid id requests nothing (its waves go straight to
 //                                  the barrier, uniform per wave) and contributes exactly 0.  Wave k rounds member k as finish() does and
@@ -773,7 +773,14 @@ void gemv_w4_decode3_experts_fused_kernel(const char* wb, const char* xb, const 
         if (wave == 0) {
             const float gv = TR::to_float(finish_value<Tag, BIASED>(red, bg));
             const float uv = TR::to_float(finish_value<Tag, BIASED>(red + RED, bu));
-            const float act = gv / (1.f + expf(-gv));
+            float act = gv / (1.f + expf(-gv));
+            // (below -88 exp(-g) leaves fp32 and the quotient is -0, while silu(g) = g exp(g) is a normal bf16 number down to about -92 and
+            // a subnormal one down to -97: there g exp(g / 2) exp(g / 2), whose factors stay normal.  g = -Inf gives -Inf * 0 = NaN, as the
+            // quotient does; every g >= -88 takes the quotient, bit for bit what it was)
+            if (gv < -88.f) {
+                const float hv = expf(0.5f * gv);
+                act = (gv * hv) * hv;
+            }
             if (lane < 16) out[tile * TC + lane] = TR::from_float(act * uv);
         }
     } else {

@@ -445,8 +445,10 @@ int gemlite_hip_experts_query(const gemlite_hip_experts_args* args);
  * member (slot, 16-column tile) is computed and rounded exactly as gemlite_hip_forward_experts computes it, bias included.
  *   GEMLITE_EXPERTS_GLU      the N columns of an expert are [gate; up] halves of I = N / 2 columns (the w13 layout of HF / vLLM
  *                            checkpoints).  With g, u the rounded gate / up outputs of slot s, its I outputs at experts.layer.out +
- *                            s * stride_out_slot are round(silu(g) * u), silu(v) = v / (1 + exp(-v)) in fp32, one rounding.  A slot whose
- *                            id is outside [0, n_experts) gets I zeros.
+ *                            s * stride_out_slot are round(silu(g) * u), silu(v) = v / (1 + exp(-v)) in fp32, one rounding; for v < -88, where
+ *                            exp(-v) leaves fp32, silu(v) = v exp(v / 2) exp(v / 2), so the result stays within one ulp of the output
+ *                            type down to its smallest subnormal.  g = +Inf gives sign(u) Inf (NaN for u = 0), g = -Inf gives NaN
+ *                            (-Inf / (1 + Inf); torch's silu gives the same).  A slot whose id is outside [0, n_experts) gets I zeros.
  *   GEMLITE_EXPERTS_COMBINE  token t = the slots t * slots_per_token + k, k < slots_per_token, each with its own id, x row
  *                            (slot / slots_per_x_row) and bias row.  With y_k the rounded output of slot k its N outputs at experts.layer.out
  *                            + t * stride_out_slot are round(sum_k weights[slot_k] * y_k): fp32, ascending k from 0, one rounding.  A slot

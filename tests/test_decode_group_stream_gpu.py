@@ -137,3 +137,27 @@ def test_adjacent_outputs_of_one_allocation_and_the_guard_bytes_around_them(N, m
     assert bool((raw[:guard] == -1).all()) and bool((raw[guard + members * N:] == -1).all()), "a store outside every member's out"
     for i, w in enumerate(want):
         assert torch.equal(buf[guard + i * N: guard + (i + 1) * N].view(1, N), w), f"layer {i}"
+
+
+@pytest.mark.parametrize("tdt", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+def test_members_of_six_magnitudes_and_one_with_a_nan_keep_to_themselves(tdt):
+    """The per-wave-x form: every member has its own x, one activation profile of test_magnitude_range_gpu each (amplitude 1e-4 beside
+    amplitude 10 in one block), and member 2 carries a NaN.  Every member, the poisoned one included, equals its eager launch as raw bits."""
+    from tests.test_magnitude_range_gpu import PROFILES, profile_row
+    N = K = 4096
+    members = min(6, _gmax())
+    lins = [_layer(N, K, 128, tdt, seed=900 + i) for i in range(members)]
+    rng = np.random.default_rng(9)
+    xs = [torch.from_numpy(profile_row(PROFILES[i], K, rng)).to(tdt).view(1, K).to(DEV) for i in range(members)]
+    xs[2][0, 1234] = float("nan")
+    want = [lin(x).clone() for lin, x in zip(lins, xs)]
+    torch.cuda.synchronize()
+    assert not bool(torch.isfinite(want[2]).any()) and all(bool(torch.isfinite(w).all()) for i, w in enumerate(want) if i != 2)
+    g, outs, seen, joined = _capture(lambda: [lin(x) for lin, x in zip(lins, xs)])
+    assert seen == members and joined == members - 1
+    assert _hip.load().gemlite_hip_capture_group_last_form() == 1  # per-wave x
+    for o in outs:
+        o.zero_()
+    _replay(g, 2)
+    for i, (o, w) in enumerate(zip(outs, want)):
+        assert torch.equal(o.view(torch.int16), w.view(torch.int16)), f"member {i} ({PROFILES[i]})"

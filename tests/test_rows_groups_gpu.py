@@ -217,6 +217,32 @@ def test_members_with_their_own_x_and_out_between_guard_bytes(N, K, M, biased):
     assert torch.equal(xbuf.view(torch.int16), xbuf_before)
 
 
+@pytest.mark.parametrize("N,K,M,tdt", [(272, 512, 17, F16), (256, 4096, 33, B16)], ids=["272x512_M17_fp16", "256x4096_M33_bf16"])
+def test_members_of_five_magnitudes_and_one_with_a_nan_keep_to_themselves(N, K, M, tdt):
+    """Every member has its own x, all rows of one activation profile of test_magnitude_range_gpu (amplitude 1e-4 beside amplitude 10 in
+    one launch), and one row of member 2 carries a NaN.  Every member, the poisoned one included, equals its eager launch as raw bits."""
+    from tests.test_magnitude_range_gpu import PROFILES, profile_row
+    core.TUNING_OVERRIDE = FORCE
+    n = 5
+    lins = [_layer(N, K, tdt, seed=10 + i) for i in range(n)]
+    rng = np.random.default_rng(M)
+    xs = [torch.from_numpy(np.stack([profile_row(PROFILES[i], K, rng) for _ in range(M)])).to(tdt).to(DEV) for i in range(n)]
+    xs[2][M // 2, K // 3] = float("nan")
+    _rows_or_skip(lins[0], xs[0])
+    want = _eager(list(zip(lins, xs)))
+    bad = ~torch.isfinite(want[2]).all(dim=1)
+    assert bad.tolist() == [m == M // 2 for m in range(M)] and all(bool(torch.isfinite(w).all()) for i, w in enumerate(want) if i != 2)
+    g, outs, seen, joined = _capture(lambda: [lin(x) for lin, x in zip(lins, xs)])
+    assert seen == n and joined == n - 1
+    for o in outs:
+        o.zero_()
+    for _ in range(2):
+        g.replay()
+    torch.cuda.synchronize()
+    for i, (o, w) in enumerate(zip(outs, want)):
+        assert torch.equal(o.view(torch.int16), w.view(torch.int16)), f"member {i} ({PROFILES[i]})"
+
+
 # ---- 4. a replay follows a new x ------------------------------------------------------------------------------------------------------
 def test_replays_follow_a_new_x():
     core.TUNING_OVERRIDE = FORCE
