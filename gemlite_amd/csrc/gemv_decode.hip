@@ -16,18 +16,22 @@
 // 16 waves x 64 lanes, lane (g = lane >> 2, c = lane & 3) owns columns 4c .. 4c + 3 of a 16-column tile and packed rows
 // chunk * 512 + wave * 32 + 2 g + {0, 1}.
 //
-// Four kernels, the form of each spelled in its template parameters; they share the device helpers of dec3 (an item's arithmetic, the row
-// sums, the final reduction with the bias add and the store), so per layer a group runs the single-layer code in the same order and every
-// layer's output is bit-identical to its own launch:
+// Four kernels, the form of each spelled in its template parameters.  Three of them are a prologue (the tile, for an expert its id and
+// bases, the member's 4 KiB of partial rows), dec3::run_member (one wave's share of one member: requests, Item::run, row sums, partial
+// rows) and an epilogue (the bias request, the barrier, finish() or GLU or COMBINE); the grouped kernel has the same items in the same
+// order behind its own counted-request ring.  All four share Item, row_sum and finish(), so a layer's, a group member's and an expert
+// slot's output is bit-identical to the layer's own launch:
 //   kernel                                               argument behind the 14 dwords    launched by
 //   gemv_w4_decode3_kernel<Tag, NT, BIASED>              unsigned* counters (timeline) |  the planner: dependent chains, eager and profiled
-//                                                        Decode3BiasTail (BIASED)         launches, a group of one
+//                                                        Decode3BiasTail (BIASED)         launches, a group of one.  Wave w runs virtual wave w
 //   gemv_w4_decode3_group_kernel<Tag, BIASED, SX, HL>    GroupTable<BIASED> by value      capture_group.hip, by rewriting a capture's node
-//   gemv_w4_decode3_experts_kernel<Tag, BIASED, IDS64>   ExpertsTail by value             gemlite_hip_forward_experts (api.hip): the single-layer
-//                                                                                         block per (tile, slot), the expert id read on the GPU
+//   gemv_w4_decode3_experts_kernel<Tag, BIASED, IDS64>   ExpertsTail by value             gemlite_hip_forward_experts (api.hip): a block per
+//                                                                                         (tile, slot), the expert id read on the GPU, then
+//                                                                                         as the single-layer kernel
 //   gemv_w4_decode3_experts_fused_kernel<Tag, BIASED,    ExpertsFusedTail by value        gemlite_hip_forward_experts_fused (api.hip): several
-//                                        IDS64, EPI>                                      (expert, tile) members per block, SwiGLU or the
-//                                                                                         routing-weight sum in the epilogue
+//                                        IDS64, EPI>                                      (expert, tile) members per block, a wave runs the
+//                                                                                         virtual waves decode3_wave_split() gives it; SwiGLU
+//                                                                                         or the routing-weight sum in the epilogue
 //     BIASED  the bias add in the epilogue (gl_common.h has the arithmetic); the lanes that store ask for their bias element in front of
 //             the barrier, so it arrives under the reduction
 //     SX      SHARED X, for a group whose members all read the same x.  What a lane derives from x — the pair dwords (x0,x4)(x1,x5)(x2,x6)
@@ -71,7 +75,7 @@ __device__ __forceinline__ float dpp_movf(float v) {
 //        grouped launches only (capture_group.hip; gl_common.h: decode3_group_modes): 16..20 members | 21..22 log2(tiles per block) |
 //        23 span placement of the tile groups | 24..31 grid.y
 constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
-constexpr int R = 2, NW = 16, CHUNK = 32, TC = 16, CSTRIDE = NW * CHUNK;
+constexpr int R = 2, NW = 16, CHUNK = 32, TC = 16;
 constexpr int RED = NW * 4 * TC;  // floats of one partial-row region: [NW * 4 DPP rows][16 columns], 4 KiB
 
 // What a lane holds of one item (a chunk of one virtual wave): its two weight rows, scales, zeros, its 8 bytes of x (per-wave x) ...
@@ -173,10 +177,11 @@ __device__ __forceinline__ float row_sum(float v) {
     return v;
 }
 
-// One wave sums the 64 partial rows of a 4 KiB region and stores the tile's 16 outputs (braw: the bias element of lane < 16)
-// (Red: the region as the kernel names it — the single-layer kernel's own array, a pointer into the group's)
-template <typename Tag, bool BIASED, typename Red>
-__device__ __forceinline__ void finish(const Red& red, uint16_t braw, uint16_t* out, int tile) {
+// One wave sums the 64 partial rows of a 4 KiB region and stores the tile's 16 outputs (braw: the bias element of lane < 16).
+// STORE = false: no store; -> the rounded 16-bit output of column lane & 15, in every lane, for an epilogue that goes on with it
+// (Red: the region as the kernel names it — the kernel's own array, or a pointer into it)
+template <typename Tag, bool BIASED, bool STORE = true, typename Red>
+__device__ __forceinline__ auto finish(const Red& red, uint16_t braw, uint16_t* out, int tile) {
     using TR = F16Traits<Tag>;
     const int lane = threadIdx.x & 63;
     constexpr int PER = NW;  // partial rows per lane quarter: 4 NW rows over 4 quarters
@@ -189,7 +194,148 @@ __device__ __forceinline__ void finish(const Red& red, uint16_t braw, uint16_t* 
     uint16_t h = TR::from_float(v);
     // (two roundings, as the matmul launch followed by torch's add has them; a sum of two converted values: nothing to contract)
     if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));
-    if (lane < 16) out[tile * TC + o] = h;
+    if constexpr (STORE) {
+        if (lane < 16) out[tile * TC + o] = h;
+    } else {
+        return h;
+    }
+}
+template <typename Tag, bool BIASED, typename Red>
+__device__ __forceinline__ uint16_t finish_value(const Red& red, uint16_t braw) {
+    return finish<Tag, BIASED, false>(red, braw, nullptr, 0);
+}
+
+// Block b's tile, one tile per block.  M_PAIR: adjacent half-line tiles on one XCD (speed only; any mapping is correct)
+__device__ __forceinline__ int pair_tile(uint32_t modes, int b) {
+    if (!(modes & M_PAIR)) return b;
+    const int xcd = b & 7, idx = b >> 3;
+    return (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
+}
+
+// One wave's share of one MEMBER — a layer, or an expert's tile: the member's virtual waves [v0, v1), where virtual wave v is the chunks
+// v, v + 16, ... below nch_total (chunk gc: the packed rows gc * 32 .. gc * 32 + 31 and their 512 bytes of x).  The wave's items — its
+// virtual waves in ascending order, each one's chunks in ascending order — are a flat list of known length, run through two chunk
+// buffers: the first two requests, then per item the arithmetic (Item::run<false>) and the request of the item after the next.  `tot` adds a
+// virtual wave's chunks in ascending order; at its end the two row_ror sums, the partial row v * 4 + (lane >> 4) of the member's 4 KiB
+// region `rd`, `tot` back to zero; a virtual wave without a chunk writes zeros (K < 4096).  So a member's region, and what finish() makes
+// of it, is the same bits whichever kernel ran it and however its virtual waves were dealt to the block's waves.
+//   NT     non-temporal weight loads
+//   ONE    v1 == v0 + 1: no cursors, no wrap test per item, one flush
+//   probe  probe(1) behind the first two requests, probe(2) behind the last item (the single-layer kernel's timeline stamps)
+// The four bases are the member's own (uniform: SGPR pairs); the offsets inside a member are 32-bit.
+template <typename Tag, bool NT, bool ONE, typename Probe>
+__device__ __forceinline__ void run_member(const char* wb, const char* xb, const char* sp, const char* zp, uint32_t sw4, uint32_t mstride2,
+                                           int nch_total, uint32_t modes, int tile, int v0, int v1, float* rd, const Probe& probe) {
+    const int lane = threadIdx.x & 63, c = lane & 3, g = lane >> 2;
+    const uint32_t n0 = (uint32_t)(tile * TC + c * 4);
+    const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
+    const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
+
+    const uint32_t row0 = (uint32_t)(v0 * CHUNK + g * R);  // this lane's first row of chunk v0
+    const uint32_t wo0 = row0 * sw4 + n0 * 4u;
+    const uint32_t xo0 = (uint32_t)(v0 * CHUNK) * 16u + (uint32_t)lane * 8u;  // a chunk's 512 bytes of x, 8 per lane
+    // chunk v0 + d of the member
+    auto load_chunk = [&](Chunk& ck, int d) {
+        const uint32_t wo = wo0 + (uint32_t)(d * CHUNK) * sw4;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const u32x4* src = (const u32x4*)(wb + (wo + (uint32_t)i * sw4));
+            ck.w[i] = NT ? __builtin_nontemporal_load(src) : *src;
+        }
+        ck.xq = *(const u32x2*)(xb + (xo0 + (uint32_t)(d * CHUNK) * 16u));
+        const uint32_t row = row0 + (uint32_t)(d * CHUNK);
+        const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
+        // (absent metadata is still "loaded" — from the member's weights, always in bounds — so the loop stays branch-free)
+        ck.s = *(const u32x2*)((need_s ? sp : wb) + (need_s ? mo : 0u));
+        ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
+    };
+    // items of this wave (a virtual wave >= nch_total has none)
+    int n;
+    if constexpr (ONE) {
+        n = (nch_total - v0 + NW - 1) / NW;
+    } else {
+        const int nv = v1 - v0, rem = (nch_total & (NW - 1)) - v0;
+        n = (nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem));
+    }
+    int rv = v0, rgc = v0;  // request cursor: virtual wave, chunk (ONE: item i is chunk v0 + 16 i)
+    auto request = [&](Chunk& ck, int i) {
+        if constexpr (ONE) {
+            load_chunk(ck, i * NW);
+        } else {
+            load_chunk(ck, rgc - v0);
+            rgc += NW;
+            if (rgc >= nch_total) rgc = ++rv;
+        }
+    };
+    Chunk cur, nxt;
+    if (n > 0) request(cur, 0);
+    if (n > 1) request(nxt, 1);
+    probe(1);
+
+    float tot[4] = {0.f, 0.f, 0.f, 0.f};
+    const float scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
+    const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
+    const bool b_times_s = w_mode == 3;
+    uint32_t wmask[Item<Tag, false>::WP];
+#pragma unroll
+    for (int i = 0; i < Item<Tag, false>::WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
+    const Item<Tag, false> item{{}, wmask, need_s, need_z, scalar_zero, bz, b_times_s, tot};
+    // a virtual wave's end: DPP row sums, the partial row to the member's region
+    auto flush = [&](int v) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tot[j] = row_sum(tot[j]);
+        if ((lane & 12) == 0) *(f32x4*)(rd + ((v * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tot[j] = 0.f;
+    };
+    int cv = v0, cgc = v0;  // compute cursor
+#pragma unroll 1
+    for (int it = 0; it < n; ++it) {
+        item.template run<false>(cur);
+        if constexpr (!ONE) {
+            cgc += NW;
+            if (cgc >= nch_total) {
+                flush(cv);
+                cgc = ++cv;
+            }
+        }
+        if (it + 1 < n) {
+            cur = nxt;
+            if (it + 2 < n) request(nxt, it + 2);
+        }
+    }
+    probe(2);
+    if constexpr (ONE) {
+        flush(v0);
+    } else {
+#pragma unroll 1
+        for (int v = cv; v < v1; ++v) flush(v);  // virtual waves without a chunk still write their rows
+    }
+}
+
+// An experts launch, the prologue of a member.  The id of a slot is a SCALAR load (uniform per wave; int32 or int64 as the router wrote
+// it); an id outside [0, n_experts) is never turned into an address
+template <bool IDS64>
+__device__ __forceinline__ uint64_t expert_id(const ExpertsTail& t, uint32_t slot) {
+    // (int32: a negative id is >= 2^31 as unsigned and n_experts is below 2^31; int64: the high dword takes part in the comparison)
+    if constexpr (IDS64) {
+        return (uint64_t)((const int64_t*)t.ids)[slot];
+    } else {
+        return (uint64_t)(uint32_t)((const int32_t*)t.ids)[slot];
+    }
+}
+__device__ __forceinline__ bool expert_valid(const ExpertsTail& t, uint64_t e) { return e < (uint64_t)t.n_experts; }
+// Expert e's bases: base + e * stride in 64-bit scalar arithmetic (a stacked tensor is far beyond 4 GiB; the offsets inside an expert
+// stay 32-bit), and the x row of the slot
+__device__ __forceinline__ void expert_bases(const ExpertsTail& t, uint64_t e, uint32_t slot, uint32_t modes, const char*& wb,
+                                             const char*& xb, const char*& sp, const char*& zp) {
+    wb += e * (uint64_t)t.stride_w;
+    sp += e * (uint64_t)t.stride_meta;
+    if (!(modes & M_ZSCALAR)) zp += e * (uint64_t)t.stride_meta;  // (one scalar zero is shared by all experts)
+    xb += (uint64_t)(slot / t.slots_per_x_row) * (uint64_t)t.stride_x;
+}
+__device__ __forceinline__ const uint16_t* expert_bias(const ExpertsTail& t, uint64_t e) {
+    return (const uint16_t*)((const char*)t.bias + e * (uint64_t)t.stride_bias);
 }
 
 }  // namespace dec3
@@ -204,36 +350,7 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 3, g = lane >> 2;
-    int tile = blockIdx.x;
-    if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
-        const int xcd = tile & 7, idx = tile >> 3;
-        tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
-    }
-    const uint32_t n0 = (uint32_t)(tile * TC + c * 4);
-    const int nchunks = (nch_total - wave + NW - 1) / NW;  // chunks wave, wave + NW, ...
-    const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
-    const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
-
-    const uint32_t row0 = (uint32_t)(wave * CHUNK + g * R);  // this lane's first row of chunk 0
-    const uint32_t wo0 = row0 * sw4 + n0 * 4u;
-    const uint32_t xo0 = (uint32_t)(wave * CHUNK) * 16u + (uint32_t)lane * 8u;  // the wave's 512 bytes of x, 8 per lane
-
-    auto load_chunk = [&](Chunk& ck, int chunk) {
-        const uint32_t wo = wo0 + (uint32_t)(chunk * CSTRIDE) * sw4;
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            const u32x4* src = (const u32x4*)(wb + (wo + (uint32_t)i * sw4));
-            ck.w[i] = NT ? __builtin_nontemporal_load(src) : *src;
-        }
-        ck.xq = *(const u32x2*)(xb + (xo0 + (uint32_t)(chunk * CSTRIDE) * 16u));
-        const uint32_t row = row0 + (uint32_t)(chunk * CSTRIDE);
-        const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
-        // (absent metadata is still "loaded" — from the weight buffer, always in bounds — so the loop stays branch-free)
-        ck.s = *(const u32x2*)((need_s ? sp : wb) + (need_s ? mo : 0u));
-        ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
-    };
-
+    const int tile = pair_tile(modes, (int)blockIdx.x);
     // opt-in timeline (GEMLITE_TF_TIMELINE): the mode bit is a preloaded SGPR, so a normal launch never touches `counters` (the one
     // argument behind the preloaded 14 dwords) and never waits for a kernarg load
     auto stamp = [&](int i) {
@@ -245,35 +362,11 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
         }
     };
     stamp(0);
-    Chunk cur, nxt;
-    if (nchunks > 0) load_chunk(cur, 0);
-    if (nchunks > 1) load_chunk(nxt, 1);
-    stamp(1);
-
-    float tot[4] = {0.f, 0.f, 0.f, 0.f};
-    const float scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
-    const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
-    const bool b_times_s = w_mode == 3;
-    uint32_t wmask[Item<Tag, false>::WP];
-#pragma unroll
-    for (int i = 0; i < Item<Tag, false>::WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
-    const Item<Tag, false> item{{}, wmask, need_s, need_z, scalar_zero, bz, b_times_s, tot};
-#pragma unroll 1
-    for (int ch = 0; ch < nchunks; ++ch) {
-        item.template run<false>(cur);
-        if (ch + 1 < nchunks) {
-            cur = nxt;
-            if (ch + 2 < nchunks) load_chunk(nxt, ch + 2);
-        }
-    }
-    stamp(2);
+    run_member<Tag, NT, true>(wb, xb, sp, zp, sw4, mstride2, nch_total, modes, tile, wave, wave + 1, red, stamp);
     uint16_t braw = 0;
     if constexpr (BIASED) {
         if (wave == 0 && lane < 16) braw = counters.bias[tile * TC + lane];
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) tot[j] = row_sum(tot[j]);
-    if ((lane & 12) == 0) *(f32x4*)(red + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
     __syncthreads();
     if (wave == 0) finish<Tag, BIASED>(red, braw, out, tile);
     stamp(3);
@@ -519,14 +612,11 @@ void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp
 }
 
 // The experts of a mixture-of-experts layer (gemlite_hip_forward_experts): grid (N / 16, slots), block (tile, s) is the single-layer block
-// of expert ids[s] on x row s / slots_per_x_row — the body of gemv_w4_decode3_kernel<Tag, true, BIASED> line for line (the same waves and
-// chunks in the same order, Item::run<false>, row_sum, the block's own 4 KiB of partial rows, finish), so every slot is bit-identical
-// to that expert's own launch.  What differs lies in front of the first request: the id is a SCALAR load the block does itself (uniform
-// per block; int32 or int64 as the router wrote it), the expert's bases are base + id * stride in 64-bit scalar arithmetic (a stacked
-// tensor is far beyond 4 GiB; the offsets inside an expert stay 32-bit), and the x row / output slot come from blockIdx.y.  The first 14
-// dwords are the decode3 set (preloaded), the tail is read with scalar loads and the id load follows it: two dependent scalar round trips
-// in front of the weight requests, where the single-layer kernel has none (no user SGPR is left to preload the ids pointer into).
-// An id outside [0, n_experts) is never turned into an address: the block writes its 16 zeros and leaves (a uniform branch).
+// of expert ids[s] on x row s / slots_per_x_row: wave w runs virtual wave w of the member into the block's own 4 KiB of partial rows, so
+// every slot is bit-identical to that expert's own launch.  What differs lies in front of the first request (dec3::expert_id, expert_bases): the
+// first 14 dwords are the decode3 set (preloaded), the tail is read with scalar loads and the id load follows it: two dependent scalar
+// round trips in front of the weight requests, where the single-layer kernel has none (no user SGPR is left to preload the ids pointer
+// into).  A block with an invalid id writes its 16 zeros and leaves (a uniform branch).
 template <typename Tag, bool BIASED, bool IDS64>
 __global__ __launch_bounds__(1024, 1)
 void gemv_w4_decode3_experts_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
@@ -536,108 +626,29 @@ void gemv_w4_decode3_experts_kernel(const char* wb, const char* xb, const char* 
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 3, g = lane >> 2;
-    int tile = blockIdx.x;
-    if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
-        const int xcd = tile & 7, idx = tile >> 3;
-        tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
-    }
+    const int tile = pair_tile(modes, (int)blockIdx.x);
     const uint32_t slot = blockIdx.y;
-    // (int32: a negative id is >= 2^31 as unsigned and n_experts is below 2^31; int64: the high dword takes part in the comparison)
-    uint64_t e;
-    if constexpr (IDS64) {
-        e = (uint64_t)((const int64_t*)tail.ids)[slot];
-    } else {
-        e = (uint64_t)(uint32_t)((const int32_t*)tail.ids)[slot];
-    }
+    const uint64_t e = expert_id<IDS64>(tail, slot);
     out += (uint64_t)slot * (uint64_t)tail.stride_out;
-    if (e >= (uint64_t)tail.n_experts) {
+    if (!expert_valid(tail, e)) {
         if (tid < TC) out[tile * TC + tid] = 0;
         return;
     }
-    wb += e * (uint64_t)tail.stride_w;
-    sp += e * (uint64_t)tail.stride_meta;
-    if (!(modes & M_ZSCALAR)) zp += e * (uint64_t)tail.stride_meta;  // (one scalar zero is shared by all experts)
-    xb += (uint64_t)(slot / tail.slots_per_x_row) * (uint64_t)tail.stride_x;
-
-    const uint32_t n0 = (uint32_t)(tile * TC + c * 4);
-    const int nchunks = (nch_total - wave + NW - 1) / NW;  // chunks wave, wave + NW, ...
-    const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
-    const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
-
-    const uint32_t row0 = (uint32_t)(wave * CHUNK + g * R);  // this lane's first row of chunk 0
-    const uint32_t wo0 = row0 * sw4 + n0 * 4u;
-    const uint32_t xo0 = (uint32_t)(wave * CHUNK) * 16u + (uint32_t)lane * 8u;  // the wave's 512 bytes of x, 8 per lane
-
-    auto load_chunk = [&](Chunk& ck, int chunk) {
-        const uint32_t wo = wo0 + (uint32_t)(chunk * CSTRIDE) * sw4;
-#pragma unroll
-        for (int i = 0; i < R; ++i) ck.w[i] = __builtin_nontemporal_load((const u32x4*)(wb + (wo + (uint32_t)i * sw4)));
-        ck.xq = *(const u32x2*)(xb + (xo0 + (uint32_t)(chunk * CSTRIDE) * 16u));
-        const uint32_t row = row0 + (uint32_t)(chunk * CSTRIDE);
-        const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
-        // (absent metadata is still "loaded" — from the expert's weights, always in bounds — so the loop stays branch-free)
-        ck.s = *(const u32x2*)((need_s ? sp : wb) + (need_s ? mo : 0u));
-        ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
-    };
-    Chunk cur, nxt;
-    if (nchunks > 0) load_chunk(cur, 0);
-    if (nchunks > 1) load_chunk(nxt, 1);
-
-    float tot[4] = {0.f, 0.f, 0.f, 0.f};
-    const float scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
-    const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
-    const bool b_times_s = w_mode == 3;
-    uint32_t wmask[Item<Tag, false>::WP];
-#pragma unroll
-    for (int i = 0; i < Item<Tag, false>::WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
-    const Item<Tag, false> item{{}, wmask, need_s, need_z, scalar_zero, bz, b_times_s, tot};
-#pragma unroll 1
-    for (int ch = 0; ch < nchunks; ++ch) {
-        item.template run<false>(cur);
-        if (ch + 1 < nchunks) {
-            cur = nxt;
-            if (ch + 2 < nchunks) load_chunk(nxt, ch + 2);
-        }
-    }
+    expert_bases(tail, e, slot, modes, wb, xb, sp, zp);
+    run_member<Tag, true, true>(wb, xb, sp, zp, sw4, mstride2, nch_total, modes, tile, wave, wave + 1, red, [](int) {});
     uint16_t braw = 0;
     if constexpr (BIASED) {
-        if (wave == 0 && lane < 16) braw = ((const uint16_t*)((const char*)tail.bias + e * (uint64_t)tail.stride_bias))[tile * TC + lane];
+        if (wave == 0 && lane < 16) braw = expert_bias(tail, e)[tile * TC + lane];
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) tot[j] = row_sum(tot[j]);
-    if ((lane & 12) == 0) *(f32x4*)(red + ((wave * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
     __syncthreads();
     if (wave == 0) finish<Tag, BIASED>(red, braw, out, tile);
 }
 
-namespace dec3 {
-// finish() up to the store: the member's rounded 16-bit output of column lane & 15, in every lane (the same sums in the same order)
-template <typename Tag, bool BIASED>
-__device__ __forceinline__ uint16_t finish_value(const float* red, uint16_t braw) {
-    using TR = F16Traits<Tag>;
-    const int lane = threadIdx.x & 63;
-    constexpr int PER = NW;
-    const int o = lane & 15, part = lane >> 4;
-    float v = 0.f;
-#pragma unroll
-    for (int r = 0; r < PER; ++r) v += red[(part * PER + r) * TC + o];
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    uint16_t h = TR::from_float(v);
-    if constexpr (BIASED) h = TR::from_float(TR::to_float(h) + TR::to_float(braw));
-    return h;
-}
-}  // namespace dec3
-
 // The fused epilogues of an expert MLP (gemlite_hip_forward_experts_fused): a block holds several MEMBERS — (expert, tile) pairs — that
 // share its 16 waves the way the layers of a grouped block do with H = 1 and per-wave x: decode3_wave_split(members, wave) gives a wave
-// its member and its virtual waves [v0, v1); virtual wave v is the chunks v, v + 16, ... in ascending order, flushed with row_sum to the
-// partial rows v * 4 + r of the member's own 4 KiB of LDS (a virtual wave without a chunk writes zeros); after one barrier a member's
-// region is summed in finish()'s order.  So a member's rounded output is bit-identical to that expert's own gemv_w4_decode3_kernel
-// launch, and to its slot of gemv_w4_decode3_experts_kernel.  The member's bases are computed by the wave from the id it loads itself
-// (a scalar load; 64-bit scalar arithmetic on base + id * stride, 32-bit offsets inside an expert), the loop is the experts kernel's
-// two-chunk double buffer over the wave's flat item list.
+// its member and its virtual waves [v0, v1), the wave computes the member's bases from the id it loads itself (dec3::expert_id, expert_bases) and
+// runs its share into the member's own 4 KiB of LDS; after one barrier a member's region is summed in finish()'s order.  So a member's
+// rounded output is bit-identical to that expert's own gemv_w4_decode3_kernel launch, and to its slot of gemv_w4_decode3_experts_kernel.
 //   EPI = GEMLITE_EXPERTS_GLU      grid (I / 16, slots), I = N / 2: block (t, s) holds tile t (gate, columns [0, I)) and tile t + I / 16
 //                                  (up, columns [I, 2 I)) of expert ids[s] on x row s / slots_per_x_row, 8 waves each; with g16 / u16 the
 //                                  members' rounded outputs (bias included) wave 0 stores from_float(silu(g16) * u16), silu(v) =
@@ -658,105 +669,24 @@ void gemv_w4_decode3_experts_fused_kernel(const char* wb, const char* xb, const 
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c = lane & 3, g = lane >> 2;
-    int tile = blockIdx.x;  // GLU: of the I / 16 tiles of one half
-    if (modes & M_PAIR) {  // adjacent half-line tiles on one XCD (speed only; any mapping is correct)
-        const int xcd = tile & 7, idx = tile >> 3;
-        tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
-    }
+    const int tile = pair_tile(modes, (int)blockIdx.x);  // GLU: of the I / 16 tiles of one half
     const int members = GLU ? 2 : (int)tail.members;
-    auto load_id = [&](uint32_t slot) -> uint64_t {
-        // (int32: a negative id is >= 2^31 as unsigned and n_experts is below 2^31; int64: the high dword takes part in the comparison)
-        if constexpr (IDS64) {
-            return (uint64_t)((const int64_t*)tail.e.ids)[slot];
-        } else {
-            return (uint64_t)(uint32_t)((const int32_t*)tail.e.ids)[slot];
-        }
-    };
     const Decode3WaveSplit split = decode3_wave_split(members, wave);
     const int li = split.layer < 0 ? 0 : split.layer;
     // this wave's member: its slot (GLU: the block's), its tile (GLU: the up half lies I / 16 tiles further)
     const uint32_t slot = GLU ? blockIdx.y : blockIdx.y * (uint32_t)members + (uint32_t)li;
     const int mtile = GLU ? tile + li * (int)tail.half_tiles : tile;
-    const uint64_t e = load_id(slot);
+    const uint64_t e = expert_id<IDS64>(tail.e, slot);
     out += (uint64_t)blockIdx.y * (uint64_t)tail.e.stride_out;
     if constexpr (GLU) {
-        if (e >= (uint64_t)tail.e.n_experts) {
+        if (!expert_valid(tail.e, e)) {
             if (tid < TC) out[tile * TC + tid] = 0;
             return;
         }
     }
-    float* const rd = red + li * RED;
-
-    if (split.layer >= 0 && e < (uint64_t)tail.e.n_experts) {
-        wb += e * (uint64_t)tail.e.stride_w;
-        sp += e * (uint64_t)tail.e.stride_meta;
-        if (!(modes & M_ZSCALAR)) zp += e * (uint64_t)tail.e.stride_meta;  // (one scalar zero is shared by all experts)
-        xb += (uint64_t)(slot / tail.e.slots_per_x_row) * (uint64_t)tail.e.stride_x;
-
-        const uint32_t n0 = (uint32_t)(mtile * TC + c * 4);
-        const int w_mode = (int)(modes & 15u), gs_shift = (int)((modes >> 8) & 255u);
-        const bool need_s = w_mode >= 2, need_z = (w_mode == 1 || w_mode >= 3) && !(modes & M_ZSCALAR);
-        const uint32_t wo0 = (uint32_t)(g * R) * sw4 + n0 * 4u;  // this lane's first row of chunk 0
-        const uint32_t xo0 = (uint32_t)lane * 8u;                 // a chunk's 512 bytes of x, 8 per lane
-
-        // chunk gc of the member: the packed rows gc * 32 .. gc * 32 + 31 (the single-layer wave gc & 15 reads them as its chunk gc >> 4)
-        auto load_chunk = [&](Chunk& ck, int gc) {
-            const uint32_t wo = wo0 + (uint32_t)(gc * CHUNK) * sw4;
-#pragma unroll
-            for (int i = 0; i < R; ++i) ck.w[i] = __builtin_nontemporal_load((const u32x4*)(wb + (wo + (uint32_t)i * sw4)));
-            ck.xq = *(const u32x2*)(xb + (xo0 + (uint32_t)(gc * CHUNK) * 16u));
-            const uint32_t row = (uint32_t)(gc * CHUNK + g * R);
-            const uint32_t mo = (uint32_t)((row * 8u) >> gs_shift) * mstride2 + n0 * 2u;
-            // (absent metadata is still "loaded" — from the expert's weights, always in bounds — so the loop stays branch-free)
-            ck.s = *(const u32x2*)((need_s ? sp : wb) + (need_s ? mo : 0u));
-            ck.z = *(const u32x2*)((need_z ? zp : wb) + (need_z ? mo : 0u));
-        };
-        // the wave's items: its virtual waves in ascending order, each one's chunks in ascending order (a virtual wave >= nch_total has none)
-        const int v0 = split.v0, v1 = split.v1, nv = v1 - v0, rem = (nch_total & (NW - 1)) - v0;
-        const int n = (nch_total / NW) * nv + (rem < 0 ? 0 : (rem > nv ? nv : rem));
-        int rv = v0, rgc = v0;  // request cursor: virtual wave, chunk
-        auto request = [&](Chunk& ck) {
-            load_chunk(ck, rgc);
-            rgc += NW;
-            if (rgc >= nch_total) rgc = ++rv;
-        };
-        Chunk cur, nxt;
-        if (n > 0) request(cur);
-        if (n > 1) request(nxt);
-
-        float tot[4] = {0.f, 0.f, 0.f, 0.f};
-        const float scalar_zero = (modes & M_ZSCALAR) ? (float)((const int32_t*)zp)[0] : 0.f;
-        const float bz = (w_mode == 1 || w_mode == 3) ? -1.f : (w_mode == 4 ? 1.f : 0.f);
-        const bool b_times_s = w_mode == 3;
-        uint32_t wmask[Item<Tag, false>::WP];
-#pragma unroll
-        for (int i = 0; i < Item<Tag, false>::WP; ++i) wmask[i] = (15u * 0x00010001u) << (4 * i);
-        const Item<Tag, false> item{{}, wmask, need_s, need_z, scalar_zero, bz, b_times_s, tot};
-        // a virtual wave's end, the single-layer code: DPP row sums, the partial row to the member's LDS region
-        auto flush = [&](int v) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) tot[j] = row_sum(tot[j]);
-            if ((lane & 12) == 0) *(f32x4*)(rd + ((v * 4 + (lane >> 4)) * TC + c * 4)) = (f32x4){tot[0], tot[1], tot[2], tot[3]};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) tot[j] = 0.f;
-        };
-        int cv = v0, cgc = v0;  // compute cursor
-#pragma unroll 1
-        for (int it = 0; it < n; ++it) {
-            item.template run<false>(cur);
-            cgc += NW;
-            if (cgc >= nch_total) {
-                flush(cv);
-                cgc = ++cv;
-            }
-            if (it + 1 < n) {
-                cur = nxt;
-                if (it + 2 < n) request(nxt);
-            }
-        }
-#pragma unroll 1
-        for (int v = cv; v < v1; ++v) flush(v);  // virtual waves without a chunk still write their rows
+    if (split.layer >= 0 && expert_valid(tail.e, e)) {
+        expert_bases(tail.e, e, slot, modes, wb, xb, sp, zp);
+        run_member<Tag, true, false>(wb, xb, sp, zp, sw4, mstride2, nch_total, modes, mtile, split.v0, split.v1, red + li * RED, [](int) {});
     }
 
     if constexpr (GLU) {
@@ -764,7 +694,7 @@ void gemv_w4_decode3_experts_fused_kernel(const char* wb, const char* xb, const 
         uint16_t bg = 0, bu = 0;
         if constexpr (BIASED) {
             if (wave == 0 && lane < 16) {
-                const uint16_t* b = (const uint16_t*)((const char*)tail.e.bias + e * (uint64_t)tail.e.stride_bias);
+                const uint16_t* b = expert_bias(tail.e, e);
                 bg = b[tile * TC + lane];
                 bu = b[(tile + (int)tail.half_tiles) * TC + lane];
             }
@@ -791,12 +721,12 @@ void gemv_w4_decode3_experts_fused_kernel(const char* wb, const char* xb, const 
         uint16_t braw = 0;
         if (fin) {
             const uint32_t fslot = blockIdx.y * (uint32_t)members + (uint32_t)wave;
-            const uint64_t ef = load_id(fslot);
-            fvalid = ef < (uint64_t)tail.e.n_experts;
+            const uint64_t ef = expert_id<IDS64>(tail.e, fslot);
+            fvalid = expert_valid(tail.e, ef);
             if (fvalid) {
                 wk = tail.w_f32 ? ((const float*)tail.weights)[fslot] : TR::to_float(((const uint16_t*)tail.weights)[fslot]);
                 if constexpr (BIASED) {
-                    if (lane < 16) braw = ((const uint16_t*)((const char*)tail.e.bias + ef * (uint64_t)tail.e.stride_bias))[tile * TC + lane];
+                    if (lane < 16) braw = expert_bias(tail.e, ef)[tile * TC + lane];
                 }
             }
         }
@@ -818,51 +748,57 @@ void gemv_w4_decode3_experts_fused_kernel(const char* wb, const char* xb, const 
     }
 }
 
-// tag: 0 fp16 | 1 bf16
-template <typename Tag, int EPI>
-static const void* decode3_experts_fused_pick(bool biased, bool ids64) {
-    return biased ? (ids64 ? (const void*)gemv_w4_decode3_experts_fused_kernel<Tag, true, true, EPI> : (const void*)gemv_w4_decode3_experts_fused_kernel<Tag, true, false, EPI>)
-                  : (ids64 ? (const void*)gemv_w4_decode3_experts_fused_kernel<Tag, false, true, EPI> : (const void*)gemv_w4_decode3_experts_fused_kernel<Tag, false, false, EPI>);
+// The accessors: runtime arguments -> the kernel form.  with_tag (0 fp16 | 1 bf16) and with_bool hand their argument on as a TYPE
+// (decltype(T); B() is a constant expression), so every form is spelled once
+template <typename F>
+static const void* with_tag(int tag, F&& f) {
+    return tag == 0 ? f(half_tag{}) : f(bf16_tag{});
 }
-const void* gemv_w4_decode3_experts_fused_fn(int tag, int epilogue, bool biased, bool ids64) {
-    if (epilogue == GEMLITE_EXPERTS_GLU)
-        return tag == 0 ? decode3_experts_fused_pick<half_tag, GEMLITE_EXPERTS_GLU>(biased, ids64) : decode3_experts_fused_pick<bf16_tag, GEMLITE_EXPERTS_GLU>(biased, ids64);
-    return tag == 0 ? decode3_experts_fused_pick<half_tag, GEMLITE_EXPERTS_COMBINE>(biased, ids64)
-                    : decode3_experts_fused_pick<bf16_tag, GEMLITE_EXPERTS_COMBINE>(biased, ids64);
-}
-
-// tag: 0 fp16 | 1 bf16
-template <typename Tag>
-static const void* decode3_experts_pick(bool biased, bool ids64) {
-    return biased ? (ids64 ? (const void*)gemv_w4_decode3_experts_kernel<Tag, true, true> : (const void*)gemv_w4_decode3_experts_kernel<Tag, true, false>)
-                  : (ids64 ? (const void*)gemv_w4_decode3_experts_kernel<Tag, false, true> : (const void*)gemv_w4_decode3_experts_kernel<Tag, false, false>);
-}
-const void* gemv_w4_decode3_experts_fn(int tag, bool biased, bool ids64) {
-    return tag == 0 ? decode3_experts_pick<half_tag>(biased, ids64) : decode3_experts_pick<bf16_tag>(biased, ids64);
+template <typename F>
+static const void* with_bool(bool b, F&& f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 const void* gemv_w4_decode3_fn(int tag, bool nt) {
-    return tag == 0 ? (nt ? (const void*)gemv_w4_decode3_kernel<half_tag, true> : (const void*)gemv_w4_decode3_kernel<half_tag, false>)
-                    : (nt ? (const void*)gemv_w4_decode3_kernel<bf16_tag, true> : (const void*)gemv_w4_decode3_kernel<bf16_tag, false>);
+    return with_tag(tag, [&](auto T) {
+        return with_bool(nt, [&](auto NT) { return (const void*)gemv_w4_decode3_kernel<decltype(T), NT()>; });
+    });
 }
 const void* gemv_w4_decode3_bias_fn(int tag, bool nt) {
-    return tag == 0 ? (nt ? (const void*)gemv_w4_decode3_kernel<half_tag, true, true> : (const void*)gemv_w4_decode3_kernel<half_tag, false, true>)
-                    : (nt ? (const void*)gemv_w4_decode3_kernel<bf16_tag, true, true> : (const void*)gemv_w4_decode3_kernel<bf16_tag, false, true>);
+    return with_tag(tag, [&](auto T) {
+        return with_bool(nt, [&](auto NT) { return (const void*)gemv_w4_decode3_kernel<decltype(T), NT(), true>; });
+    });
 }
-
+const void* gemv_w4_decode3_experts_fn(int tag, bool biased, bool ids64) {
+    return with_tag(tag, [&](auto T) {
+        return with_bool(biased, [&](auto B) {
+            return with_bool(ids64, [&](auto I) { return (const void*)gemv_w4_decode3_experts_kernel<decltype(T), B(), I()>; });
+        });
+    });
+}
+const void* gemv_w4_decode3_experts_fused_fn(int tag, int epilogue, bool biased, bool ids64) {
+    return with_tag(tag, [&](auto T) {
+        return with_bool(biased, [&](auto B) {
+            return with_bool(ids64, [&](auto I) {
+                return with_bool(epilogue == GEMLITE_EXPERTS_GLU, [&](auto G) {
+                    constexpr int EPI = G() ? GEMLITE_EXPERTS_GLU : GEMLITE_EXPERTS_COMBINE;
+                    return (const void*)gemv_w4_decode3_experts_fused_kernel<decltype(T), B(), I(), EPI>;
+                });
+            });
+        });
+    });
+}
 // Every grouped form (h: the tiles per wave, 1 / 2 / 4; anything else: 1)
-template <typename Tag, bool BIASED, bool SX>
-static const void* decode3_group_pick(int h) {
-    return h == 4 ? (const void*)gemv_w4_decode3_group_kernel<Tag, BIASED, SX, 2>
-                  : (h == 2 ? (const void*)gemv_w4_decode3_group_kernel<Tag, BIASED, SX, 1> : (const void*)gemv_w4_decode3_group_kernel<Tag, BIASED, SX, 0>);
-}
-template <typename Tag>
-static const void* decode3_group_pick(bool biased, bool shared_x, int h) {
-    return biased ? (shared_x ? decode3_group_pick<Tag, true, true>(h) : decode3_group_pick<Tag, true, false>(h))
-                  : (shared_x ? decode3_group_pick<Tag, false, true>(h) : decode3_group_pick<Tag, false, false>(h));
-}
 const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h) {
-    return tag == 0 ? decode3_group_pick<half_tag>(biased, shared_x, h) : decode3_group_pick<bf16_tag>(biased, shared_x, h);
+    return with_tag(tag, [&](auto T) {
+        return with_bool(biased, [&](auto B) {
+            return with_bool(shared_x, [&](auto SX) {
+                return h == 4 ? (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 2>
+                              : (h == 2 ? (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 1>
+                                        : (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 0>);
+            });
+        });
+    });
 }
 
 }  // namespace gl
