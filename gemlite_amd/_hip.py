@@ -232,6 +232,20 @@ class ExpertsFusedArgs(C.Structure):
     ]
 
 
+class ExpertsRowsArgs(C.Structure):
+    """struct gemlite_hip_experts_rows_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("rows_per_block", C.c_int32),
+        ("experts", ExpertsArgs),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("reserved", C.c_int64 * 2),
+    ]
+
+
+EXPERTS_ROWS_MAX_EXPERTS = 4096  # GEMLITE_EXPERTS_ROWS_MAX_EXPERTS of the header
 EXPERTS_GLU, EXPERTS_COMBINE, ACT_SILU = 1, 2, 1  # gemlite_hip_experts_fused_args.epilogue / .activation
 BIAS_NOT_ADDED = 1  # gemlite_hip_forward_ex: launched without the bias, the caller adds it
 
@@ -339,6 +353,14 @@ def load():
         lib.gemlite_hip_forward_experts_fused.argtypes = [C.POINTER(ExpertsFusedArgs), C.c_void_p]
         lib.gemlite_hip_experts_fused_query.restype = C.c_int
         lib.gemlite_hip_experts_fused_query.argtypes = [C.POINTER(ExpertsFusedArgs)]
+        lib.gemlite_hip_experts_rows_workspace_bytes.restype = C.c_uint64
+        lib.gemlite_hip_experts_rows_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32]
+        for name in ("gemlite_hip_experts_rows_per_block", "gemlite_hip_experts_rows_query"):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [C.POINTER(ExpertsRowsArgs)]
+        for name in ("gemlite_hip_experts_route", "gemlite_hip_forward_experts_rows"):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [C.POINTER(ExpertsRowsArgs), C.c_void_p]
         if lib.gemlite_hip_abi_version() != ABI_VERSION:
             raise GemliteHipError("libgemlite_hip.so ABI version mismatch; rebuild it")
         _lib = lib
@@ -362,6 +384,8 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_quantize_rows",
     "gemlite_hip_forward_experts", "gemlite_hip_experts_query",
     "gemlite_hip_forward_experts_fused", "gemlite_hip_experts_fused_query",
+    "gemlite_hip_experts_rows_workspace_bytes", "gemlite_hip_experts_rows_per_block", "gemlite_hip_experts_route",
+    "gemlite_hip_forward_experts_rows", "gemlite_hip_experts_rows_query",
 )
 
 

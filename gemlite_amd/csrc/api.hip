@@ -65,6 +65,9 @@ const void* dequantize_rows_kernel_fn(int fmt);
 const void* dequantize_any_kernel_fn();
 const void* gemv_w4_decode3_experts_fn(int tag, bool biased, bool ids64);  // gemv_decode.hip
 const void* gemv_w4_decode3_experts_fused_fn(int tag, int epilogue, bool biased, bool ids64);  // gemv_decode.hip
+const void* gemm_wn_rows_experts_fn(int tag, int mt, int spg, bool biased);  // gemm_wn_rows_experts.hip
+size_t gemm_wn_rows_experts_lds_bytes();
+const void* experts_route_fn(bool ids64);  // experts_route.hip
 // capture_group.hip: independent decode3 (or rows) launches of one stream capture folded into one grouped launch
 int capture_group_limit();
 void capture_group_stats(uint64_t* seen, uint64_t* joined);
@@ -1370,6 +1373,125 @@ int gemlite_hip_forward_experts_fused(const gemlite_hip_experts_fused_args* args
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                      (void*)&d.nch_total, (void*)&d.modes, (void*)&L.tail};
     return launch(L.fn, L.grid, dim3(1024, 1, 1), kargs, 0, (hipStream_t)stream);
+}
+
+// ---- experts on a batch (gemm_wn_rows_experts.hip: gemm_w4_rows_experts_kernel; experts_route.hip: experts_route_kernel): the nested
+// request by experts_plan's rules, unchanged, then the rows kernel's own (plan_gemm_wn_rows), then the workspace.  Two launches: the route
+// writes the work table, the rows launch — grid (N / 16, Bmax) — consumes it; neither reads anything on the host.
+struct ExpertsRowsLaunch {
+    ExpertsLaunch base;
+    ExpertsRowsTail tail;
+    const void *fn, *route_fn;
+    dim3 grid;
+    int R;
+    uint32_t sxm2, som;
+};
+
+static bool experts_rows_r_ok(int64_t r) { return r == 16 || r == 32 || r == 48 || r == 64; }
+
+uint64_t gemlite_hip_experts_rows_workspace_bytes(int64_t n_slots, int64_t n_experts, int32_t rows_per_block) {
+    if (n_slots <= 0 || n_slots > 65535 || n_experts <= 0 || n_experts > GEMLITE_EXPERTS_ROWS_MAX_EXPERTS || !experts_rows_r_ok(rows_per_block)) return 0;
+    const int64_t bmax = experts_rows_bmax(n_slots, n_experts, rows_per_block);
+    return (uint64_t)(EXPERTS_ROWS_HEADER + bmax + bmax * rows_per_block) * 4u;
+}
+
+// Default R: the smallest block that holds the mean slot count per expert, n_slots / min(E, n_slots), PLUS A QUARTER; capped by the
+// registers of the group size (groups of 32: 32 rows).  The first rule was the mean itself; profiles/r23/probe_experts_rows*.log replaced
+// it: a work block of 32 / 64 rows costs 1.2 / 1.6 blocks of 16 (4096^2, 16 blocks: 101.7 / 121.1 / 162.8 us), a second block of the same
+// expert costs a whole one, and under random routing about half the experts lie above the mean — at a mean of exactly 16 (Mixtral, 64
+// tokens) R = 16 needed 13 / 12 blocks for 8 experts and ran 277.7 / 170.6 us (gate/up / down) against 218.4 / 151.4 with R = 32.  Far
+// below 16 slots per expert (Qwen3-30B-A3B up to 128 tokens) R = 16 stays 1.2 x ahead of 32.
+static int experts_rows_default_r(int64_t n_slots, int64_t n_experts, int cap) {
+    const int64_t mean = n_slots / (n_experts < n_slots ? n_experts : n_slots), want = mean + mean / 4;
+    const int r = want <= 16 ? 16 : (want <= 32 ? 32 : (want <= 48 ? 48 : 64));
+    return r < cap ? r : cap;
+}
+
+static int experts_rows_plan(const gemlite_hip_experts_rows_args* r, ExpertsRowsLaunch& L, bool with_workspace) {
+    if (!r || r->struct_size != sizeof(gemlite_hip_experts_rows_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    const int v = experts_plan(&r->experts, L.base);
+    if (v != GEMLITE_OK) return v;
+    const gemlite_hip_experts_args& e = r->experts;
+    const gemlite_hip_forward_args& a = e.layer;
+    // the rows kernel's own rules (plan_gemm_wn_rows): packed pairs of outputs, 32-bit offsets inside an expert, an x extent below 2^31
+    // (the 0x80000000 offset of an empty row must lie beyond the descriptor of ALL of x)
+    if (((uintptr_t)a.out % 4) != 0 || (e.stride_out_slot % 2) != 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (e.n_experts > GEMLITE_EXPERTS_ROWS_MAX_EXPERTS) return GEMLITE_ERR_BAD_SHAPE;
+    const Decode3Args& d = L.base.d3;
+    const int64_t rows = a.K / 8, x_rows = (e.n_slots + e.slots_per_x_row - 1) / e.slots_per_x_row;
+    const int64_t x_bytes = (x_rows - 1) * e.stride_x_row * 2 + a.K * 2;
+    if (rows * a.stride_wk * 4 + a.N * 4 >= (1ll << 32) || x_bytes >= (1ll << 31) || e.stride_out_slot >= (1ll << 31)) return GEMLITE_ERR_BAD_SHAPE;
+    const uint32_t gs_shift = (d.modes >> 8) & 255u;
+    if (gs_shift < 31 && ((a.K >> gs_shift) * (int64_t)(d.mstride2 / 2) + a.N) * 2 >= (1ll << 32)) return GEMLITE_ERR_BAD_SHAPE;
+    const int spg = gs_shift >= 7 ? 4 : (gs_shift == 6 ? 2 : 1), cap = spg == 1 ? 32 : 64;
+    if (r->rows_per_block != 0 && !experts_rows_r_ok(r->rows_per_block)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (r->rows_per_block > cap) return GEMLITE_ERR_BAD_SHAPE;  // (groups of 32: the 48- / 64-row forms need more than 256 registers)
+    L.R = r->rows_per_block ? r->rows_per_block : experts_rows_default_r(e.n_slots, e.n_experts, cap);
+    const int64_t bmax = experts_rows_bmax(e.n_slots, e.n_experts, L.R);
+    if (with_workspace) {
+        if (!r->workspace || ((uintptr_t)r->workspace % 4) != 0 ||
+            r->workspace_bytes < gemlite_hip_experts_rows_workspace_bytes(e.n_slots, e.n_experts, L.R))
+            return GEMLITE_ERR_WORKSPACE;
+    }
+    const bool f16 = a.input_dtype == GEMLITE_DT_FP16;
+    L.fn = gemm_wn_rows_experts_fn(f16 ? 0 : 1, L.R / 16, spg, e.bias != nullptr);
+    if (!L.fn) return GEMLITE_ERR_UNSUPPORTED;
+    L.route_fn = experts_route_fn(e.ids_dtype == GEMLITE_DT_INT64);
+    L.tail.table = (const int32_t*)r->workspace;
+    L.tail.bias = (const uint16_t*)e.bias;
+    L.tail.stride_w = e.stride_expert_w;
+    L.tail.stride_meta = e.stride_expert_meta;
+    L.tail.stride_bias = e.stride_expert_bias;
+    L.tail.n_experts = (uint32_t)e.n_experts;
+    L.tail.slots_per_x_row = L.base.tail.slots_per_x_row;
+    L.tail.n_slots = (uint32_t)e.n_slots;
+    L.tail.x_bytes = (uint32_t)x_bytes;
+    L.sxm2 = (uint32_t)(e.stride_x_row * 2);
+    L.som = (uint32_t)e.stride_out_slot;
+    L.grid = dim3((unsigned)(a.N / 16), (unsigned)bmax, 1);
+    return GEMLITE_OK;
+}
+
+int gemlite_hip_experts_rows_query(const gemlite_hip_experts_rows_args* args) {
+    ExpertsRowsLaunch L;
+    return experts_rows_plan(args, L, true);
+}
+
+int gemlite_hip_experts_rows_per_block(const gemlite_hip_experts_rows_args* args) {
+    ExpertsRowsLaunch L;
+    const int v = experts_rows_plan(args, L, false);
+    return v != GEMLITE_OK ? v : L.R;
+}
+
+int gemlite_hip_experts_route(const gemlite_hip_experts_rows_args* args, void* stream) {
+    ExpertsRowsLaunch L;
+    const int v = experts_rows_plan(args, L, true);
+    if (v != GEMLITE_OK) return v;
+    int dev = 0;
+    const int dv = check_device(&dev);
+    if (dv != GEMLITE_OK) return dv;
+    const void* ids = args->experts.ids;
+    int32_t* table = (int32_t*)args->workspace;
+    uint32_t n_slots = (uint32_t)args->experts.n_slots, n_experts = L.tail.n_experts, R = (uint32_t)L.R, bmax = L.grid.y;
+    void* kargs[] = {(void*)&ids, (void*)&table, (void*)&n_slots, (void*)&n_experts, (void*)&R, (void*)&bmax};
+    return launch(L.route_fn, dim3(1, 1, 1), dim3(1024, 1, 1), kargs, 0, (hipStream_t)stream);
+}
+
+int gemlite_hip_forward_experts_rows(const gemlite_hip_experts_rows_args* args, void* stream) {
+    ExpertsRowsLaunch L;
+    const int v = experts_rows_plan(args, L, true);
+    if (v != GEMLITE_OK) return v;
+    int dev = 0;
+    const int dv = check_device(&dev);
+    if (dv != GEMLITE_OK) return dv;
+    const size_t lds = gemm_wn_rows_experts_lds_bytes();
+    const int le = ensure_lds(L.fn, lds, dev);
+    if (le != GEMLITE_OK) return le;
+    Decode3Args& d = L.base.d3;
+    int M = L.R;
+    void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
+                     (void*)&d.nch_total, (void*)&d.modes, (void*)&M, (void*)&L.sxm2, (void*)&L.som, (void*)&L.tail};
+    return launch(L.fn, L.grid, dim3(64 * 8, 1, 1), kargs, lds, (hipStream_t)stream);
 }
 
 int gemlite_hip_scale_activations_per_token(const void* x, void* y, float* scales, int64_t M, int64_t K,

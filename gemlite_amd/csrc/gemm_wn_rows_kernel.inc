@@ -6,12 +6,27 @@
 //       table behind the scalars (gl_common.h: GroupTable<biased>), selected by blockIdx.y — uniform, so scalar loads, once
 //       per wave and in front of the first request.  Everything behind the selection is the single-layer body; the row blocks along grid.y
 //       are compiled out (launches with row blocks never group).  GL_ROWS5_GROUP undefined or 0: the two forms above, token for token.
+//   GL_ROWS5_EXPERTS = 1 (gemm_wn_rows_experts.hip: gemm_w4_rows_experts_kernel / gemm_w4_rows_bias_experts_kernel): the EXPERTS forms — grid
+//       (tiles, Bmax), block (tile, b) computes work block b of the table experts_route_kernel wrote (gl_common.h: ExpertsRowsTail): up to
+//       16 MT slots of ONE expert.  The block leaves at once if b is beyond the used count; the expert's bases are 64-bit scalar arithmetic
+//       (as dec3::expert_bases); row r of the block is the x row of slot block_rows[b][r] (GATHER: the source offset of the LDS-DMA
+//       request; a -1 entry takes the out-of-range offset and reads zeros like the rows >= M of the other forms) and is stored at that
+//       slot's output row (SCATTER); a block of the invalid bucket stores zeros.  Everything between is the single-layer body, and a row
+//       of the MFMA result depends on no other row: a slot is bit-identical to its row of the single-layer form.  Undefined or 0: the
+//       forms above, token for token.
 #if defined(GL_ROWS5_GROUP) && GL_ROWS5_GROUP
 #define GL_ROWS5_GROUPED 1
 #else
 #define GL_ROWS5_GROUPED 0
 #endif
-#if GL_ROWS5_GROUPED
+#if defined(GL_ROWS5_EXPERTS) && GL_ROWS5_EXPERTS
+#define GL_ROWS5_EXP 1
+#else
+#define GL_ROWS5_EXP 0
+#endif
+#if GL_ROWS5_EXP
+#define GL_ROWS5_BIAS_PARAM , const ExpertsRowsTail tail
+#elif GL_ROWS5_GROUPED
 #define GL_ROWS5_BIAS_PARAM , const GroupTable<GL_ROWS5_BIAS != 0> tab
 #elif GL_ROWS5_BIAS
 #define GL_ROWS5_BIAS_PARAM , const uint16_t* bias
@@ -50,7 +65,29 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
         const int xcd = tile & 7, idx = tile >> 3;
         tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
     }
-#if GL_ROWS5_GROUPED
+#if GL_ROWS5_EXP
+    // this block's work block: beyond the used count -> nothing to do (uniform, in front of any address arithmetic)
+    const int32_t* const wtab = tail.table;
+    if ((int)blockIdx.y >= wtab[0]) return;
+    const uint32_t expert = (uint32_t)wtab[EXPERTS_ROWS_HEADER + blockIdx.y];
+    const int32_t* const brow = wtab + EXPERTS_ROWS_HEADER + gridDim.y + (size_t)blockIdx.y * (16 * MT);  // the block's 16 MT slots, -1 = none
+    M = 16 * MT;
+    if (expert >= tail.n_experts) {  // the invalid bucket: zeros to this tile of its slots, nothing is dereferenced
+        for (int o = tid; o < MT * 16 * (TCN / 2); o += NW * 64) {
+            const int m = o / (TCN / 2), cp = o % (TCN / 2);
+            const int slot = brow[m];
+            if ((uint32_t)slot < tail.n_slots) *(uint32_t*)(out + (size_t)slot * som + (size_t)(tile * TCN + cp * 2)) = 0u;
+        }
+        return;
+    }
+    // the expert's bases: 64-bit scalar arithmetic, the offsets inside an expert stay 32-bit (one scalar zero is shared by all experts)
+    wb += (uint64_t)expert * (uint64_t)tail.stride_w;
+    sp += (uint64_t)expert * (uint64_t)tail.stride_meta;
+    if (!(modes & M_ZSCALAR)) zp += (uint64_t)expert * (uint64_t)tail.stride_meta;
+#if GL_ROWS5_BIAS
+    const uint16_t* bias = (const uint16_t*)((const char*)tail.bias + (uint64_t)expert * (uint64_t)tail.stride_bias);
+#endif
+#elif GL_ROWS5_GROUPED
     // this block's member: the preloaded scalars (member 0) or the by-value table — blockIdx.y is uniform, so these are scalar loads
     const int member = (int)blockIdx.y;
     if (member > 0) {
@@ -95,9 +132,18 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
 #pragma unroll
     for (int q = 0; q < DPI; ++q) {
         const int r = q * RPI + lane / PPR, pp = lane % PPR;
+#if GL_ROWS5_EXP
+        const int slot = brow[r];  // gather: the x row of the slot (the descriptor covers all of x, its extent is below 2^31)
+        xvo[q] = (uint32_t)slot < tail.n_slots ? ((uint32_t)slot / tail.slots_per_x_row) * sxm2 + (uint32_t)((pp ^ fswz(r)) * 16) : 0x80000000u;
+#else
         xvo[q] = r < M ? (uint32_t)r * sxm2 + (uint32_t)((pp ^ fswz(r)) * 16) : 0x80000000u;
+#endif
     }
+#if GL_ROWS5_EXP
+    const async::srd_t rsX = async::make_srd(xb, tail.x_bytes);
+#else
     const async::srd_t rsX = async::make_srd(xb, (uint32_t)(M - 1) * sxm2 + (uint32_t)nch_total * (uint32_t)(KCH * 2));
+#endif
     const uint32_t xlds = async::lds_addr_of(wl);
     uint32_t abase[MT];  // byte offset of this lane's A fragment (k-step 0 of a piece) inside a buffer; k-step s' = abase ^ (s' << 6)
 #pragma unroll
@@ -283,18 +329,30 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
                 v1 *= TR::to_float((uint16_t)(sw >> 16));
             }
         }
+#if GL_ROWS5_EXP
+        const int oslot = brow[m];  // scatter: the row's slot; nothing is stored for a -1 entry
+        uint16_t* const orow = out + (size_t)(uint32_t)oslot * som;
+#define GL_ROWS5_STORE_IF ((uint32_t)oslot < tail.n_slots)
+#define GL_ROWS5_OUT_ROW orow
+#else
+#define GL_ROWS5_STORE_IF (m < M)
+#define GL_ROWS5_OUT_ROW (out + (size_t)m * som)
+#endif
 #if GL_ROWS5_BIAS
         // the ROUNDED result plus bias[n] (the output's 16-bit type, broadcast over the rows), rounded again: the two roundings of "matmul, then
         // out += bias", bit for bit (a sum of two converted values: nothing to contract).  Two 2-byte loads: the bias needs 2-byte alignment only
         const uint16_t* bp = bias + (size_t)(tile * TCN + cp * 2);
         const uint16_t h0 = TR::from_float(TR::to_float(TR::from_float(v0)) + TR::to_float(bp[0]));
         const uint16_t h1 = TR::from_float(TR::to_float(TR::from_float(v1)) + TR::to_float(bp[1]));
-        if (m < M) *(uint32_t*)(out + (size_t)m * som + (size_t)(tile * TCN + cp * 2)) = (uint32_t)h0 | ((uint32_t)h1 << 16);
+        if (GL_ROWS5_STORE_IF) *(uint32_t*)(GL_ROWS5_OUT_ROW + (size_t)(tile * TCN + cp * 2)) = (uint32_t)h0 | ((uint32_t)h1 << 16);
 #else
-        if (m < M) *(uint32_t*)(out + (size_t)m * som + (size_t)(tile * TCN + cp * 2)) = (uint32_t)TR::from_float(v0) | ((uint32_t)TR::from_float(v1) << 16);
+        if (GL_ROWS5_STORE_IF) *(uint32_t*)(GL_ROWS5_OUT_ROW + (size_t)(tile * TCN + cp * 2)) = (uint32_t)TR::from_float(v0) | ((uint32_t)TR::from_float(v1) << 16);
 #endif
+#undef GL_ROWS5_STORE_IF
+#undef GL_ROWS5_OUT_ROW
     }
 }
 
 #undef GL_ROWS5_BIAS_PARAM
 #undef GL_ROWS5_GROUPED
+#undef GL_ROWS5_EXP

@@ -634,6 +634,20 @@ struct ExpertsFusedTail {
     uint32_t half_tiles;  // GLU: I / 16, the tiles between a block's gate tile and its up tile
     uint32_t w_f32;
 };
+// gemm_w4_rows_experts_kernel (gemm_wn_rows_experts.hip; gemlite_hip_forward_experts_rows): what travels behind the scalars of the rows
+// kernel.  The work table is written by experts_route_kernel (experts_route.hip): [0] used blocks, [1..3] zero, block_expert[Bmax] at
+// EXPERTS_ROWS_HEADER, block_rows[Bmax * R] behind it; Bmax = gridDim.y of the rows launch
+constexpr int EXPERTS_ROWS_HEADER = 4;
+struct ExpertsRowsTail {
+    const int32_t* table;
+    const uint16_t* bias;                        // expert 0's (the BIASED forms)
+    int64_t stride_w, stride_meta, stride_bias;  // bytes between experts
+    uint32_t n_experts, slots_per_x_row, n_slots;  // (an entry of the table that is no slot of this launch counts as -1: memory safety on a foreign table)
+    uint32_t x_bytes;                            // extent of ALL of x (below 2^31): num_records of the gather's buffer descriptor
+};
+inline int64_t experts_rows_bmax(int64_t n_slots, int64_t n_experts, int64_t R) {
+    return (n_slots + R - 1) / R + (n_experts + 1 < n_slots ? n_experts + 1 : n_slots);
+}
 template <bool BIASED>
 struct GroupTable {
     GroupMember m[DECODE3_GMAX - 1];

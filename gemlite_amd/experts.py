@@ -11,6 +11,10 @@ There is no slow path: layers outside the domain are refused by ``from_layers``.
 ``GemLiteExpertsMLP`` runs a whole expert MLP in two such launches (``gemlite_hip_forward_experts_fused``):
 ``gate_up.forward_glu`` stores ``silu(gate) * up`` of experts stacked ``[gate; up]`` along N, ``down.forward_combine`` stores the
 routing-weight sum over a token's slots.  Every member is rounded as its slot of ``forward``; the epilogues run in fp32 on those values.
+
+Batches: ``experts.route(ids)`` sorts the slots by expert on the GPU into work blocks (an ``ExpertsRouting``) and
+``experts.forward_batched(x, ids, routing)`` streams every expert's weights once per work block through the MFMA rows kernel
+(``gemlite_hip_experts_route`` / ``gemlite_hip_forward_experts_rows``).  Opt-in: ``forward`` never dispatches to it.
 """
 import threading
 from typing import List, Optional, Sequence
@@ -211,6 +215,167 @@ def _forward_experts_combine_fake(x, expert_ids, weights, bias, tensor_args, met
     return torch.empty(tuple(expert_ids.shape[:-1]) + (W_q.shape[2],), device=x.device, dtype=x.dtype)
 
 
+# ---- batches (gemlite_hip_experts_route + gemlite_hip_forward_experts_rows): the slots are sorted by expert on the GPU
+# and every expert's weights stream once per work block of up to R slots through the MFMA rows kernel ----
+ROWS_PER_BLOCK = (16, 32, 48, 64)
+ROWS_DOMAIN = ("domain: rows_per_block 16 / 32 / 48 / 64 (groups of 32: 16 / 32), at most %d experts and %d slots, 4-byte aligned outputs, "
+               "all of x below 2^31 bytes" % (_hip.EXPERTS_ROWS_MAX_EXPERTS, MAX_SLOTS))
+
+
+def rows_blocks_max(n_slots: int, n_experts: int, rows_per_block: int) -> int:
+    """Bmax of the header: the work blocks a routing can need, which is grid.y of the rows launch."""
+    return -(-n_slots // rows_per_block) + min(n_experts + 1, n_slots)
+
+
+def rows_workspace_ints(n_slots: int, n_experts: int, rows_per_block: int) -> int:
+    """int32 entries of the work table: 4 of header, block_expert[Bmax], block_rows[Bmax * R] (gemlite_hip_experts_rows_workspace_bytes / 4)."""
+    b = rows_blocks_max(n_slots, n_experts, rows_per_block)
+    return 4 + b + b * rows_per_block
+
+
+def _rows_args(e: "_hip.ExpertsArgs", rows_per_block: int, workspace: Optional[Tensor]) -> "_hip.ExpertsRowsArgs":
+    r = _hip.ExpertsRowsArgs()
+    r.struct_size = _hip.C.sizeof(_hip.ExpertsRowsArgs)
+    r.rows_per_block = int(rows_per_block)
+    r.experts = e
+    if workspace is not None:
+        r.workspace = workspace.data_ptr()
+        r.workspace_bytes = workspace.numel() * workspace.element_size()
+    return r
+
+
+def _stand_in_args(bias: Optional[Tensor], tensor_args, meta_args, n_slots: int) -> "_hip.ExpertsArgs":
+    """A request with stand-ins for x / out / ids (one row per slot): what the host-only queries are asked with."""
+    W_q, scales, zeros = tensor_args
+    e = _static_args(W_q, scales, zeros, bias, meta_args)
+    e.layer.x = e.layer.out = e.ids = 0x1000
+    e.layer.stride_xm = e.stride_x_row = e.layer.K
+    e.ids_dtype = DType.INT32.value
+    e.n_slots, e.slots_per_x_row = max(int(n_slots), 1), 1
+    e.stride_out_slot = e.layer.N
+    return e
+
+
+def _raise_rows(rc: int, what: str):
+    if rc in (_hip.ERR_BAD_SHAPE, _hip.ERR_UNSUPPORTED, _hip.ERR_BAD_ARGUMENT, _hip.ERR_WORKSPACE):
+        raise NotImplementedError(f"{what}: {_hip.status_string(rc)} ({ROWS_DOMAIN})")
+    _hip.raise_for_status(rc, what)
+
+
+def _resolve_rows(bias: Optional[Tensor], tensor_args, meta_args, n_slots: int, rows_per_block: Optional[int]) -> int:
+    """The R the library resolves for these experts and this many slots (host only); refusals in words."""
+    want = 0 if rows_per_block is None else int(rows_per_block)
+    if want and want not in ROWS_PER_BLOCK:
+        raise ValueError(f"rows_per_block is {rows_per_block}: one of {ROWS_PER_BLOCK}, or None for the library's default")
+    if want > 32 and meta_args[2] == 32:
+        raise NotImplementedError(f"rows_per_block is {want}: groups of 32 take 16 or 32 rows per work block (the registers of the kernel)")
+    r = _rows_args(_stand_in_args(bias, tensor_args, meta_args, n_slots), want, None)
+    rc = _hip.load().gemlite_hip_experts_rows_per_block(_hip.C.byref(r))
+    if rc < 0:
+        _raise_rows(rc, f"GemLiteExperts.route: {n_slots} slots over {tensor_args[0].shape[0]} experts, rows_per_block={rows_per_block}")
+    return rc
+
+
+def _route_impl(expert_ids: Tensor, rows_per_block: int, bias: Optional[Tensor], tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    W_q = tensor_args[0]
+    lib = _hip.load()
+    for t, name in ((expert_ids, "expert_ids"), (W_q, "W_q")):
+        _hip.require_gpu_tensor(t, name)
+    if expert_ids.device != W_q.device:
+        raise _hip.GemliteHipError(f"expert_ids are on {expert_ids.device}, the packed weights on {W_q.device}")
+    if expert_ids.dtype not in (torch.int32, torch.int64):
+        raise NotImplementedError(f"expert_ids are {expert_ids.dtype}: int32 or int64")
+    n_slots = expert_ids.numel()
+    ws = torch.empty(rows_workspace_ints(max(n_slots, 1), W_q.shape[0], rows_per_block), dtype=torch.int32, device=W_q.device)
+    if n_slots == 0:
+        return ws.zero_()  # (no work block is used)
+    ids = expert_ids.contiguous()
+    e = _stand_in_args(bias, tensor_args, meta_args, n_slots)
+    e.ids, e.ids_dtype = ids.data_ptr(), TORCH_TO_DTYPE[ids.dtype].value
+    r = _rows_args(e, rows_per_block, ws)
+    with _hip.on_device(W_q.device):
+        rc = lib.gemlite_hip_experts_route(_hip.C.byref(r), _hip.current_stream_handle(W_q.device))
+    if rc != _hip.OK:
+        _raise_rows(rc, "gemlite_hip_experts_route")
+    return ws
+
+
+def _forward_rows_impl(x: Tensor, expert_ids: Tensor, workspace: Tensor, rows_per_block: int, bias: Optional[Tensor],
+                       tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    W_q = tensor_args[0]
+    N, K = W_q.shape[2], W_q.shape[1] * meta_args[4]
+    lib = _hip.load()
+    for t, name in ((x, "x"), (expert_ids, "expert_ids"), (workspace, "workspace"), (W_q, "W_q")):
+        _hip.require_gpu_tensor(t, name)
+    if x.device != W_q.device or expert_ids.device != W_q.device or workspace.device != W_q.device:
+        raise _hip.GemliteHipError(f"x is on {x.device}, expert_ids on {expert_ids.device}, the routing on {workspace.device}, "
+                                   f"the packed weights on {W_q.device}")
+    if expert_ids.dtype not in (torch.int32, torch.int64):
+        raise NotImplementedError(f"expert_ids are {expert_ids.dtype}: int32 or int64")
+    rows, spx = _split(x, expert_ids, K)
+    out = torch.empty(tuple(expert_ids.shape) + (N,), dtype=x.dtype, device=x.device)
+    if expert_ids.numel() == 0:
+        return out
+    if workspace.dtype != torch.int32 or not workspace.is_contiguous():
+        raise ValueError(f"the routing workspace is {workspace.dtype}, contiguous={workspace.is_contiguous()}: a contiguous int32 tensor")
+    x2 = x.contiguous().view(rows, K)
+    ids = expert_ids.contiguous()
+    r = _rows_args(_call_args(x2, ids, out.data_ptr(), bias, tensor_args, meta_args, spx), rows_per_block, workspace)
+    with _hip.on_device(x.device):
+        rc = lib.gemlite_hip_forward_experts_rows(_hip.C.byref(r), _hip.current_stream_handle(x.device))
+    if rc != _hip.OK:
+        _raise_rows(rc, "gemlite_hip_forward_experts_rows")
+    return out
+
+
+@torch.library.custom_op("gemlite::experts_route", mutates_args=())
+def experts_route(expert_ids: Tensor, rows_per_block: int, bias: Optional[Tensor], tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    return _route_impl(expert_ids, rows_per_block, bias, tensor_args, meta_args)
+
+
+@torch.library.register_fake("gemlite::experts_route")
+def _experts_route_fake(expert_ids, rows_per_block, bias, tensor_args, meta_args):
+    W_q = tensor_args[0]
+    return torch.empty(rows_workspace_ints(max(expert_ids.numel(), 1), W_q.shape[0], rows_per_block), device=W_q.device, dtype=torch.int32)
+
+
+@torch.library.custom_op("gemlite::forward_experts_rows", mutates_args=())
+def forward_experts_rows(x: Tensor, expert_ids: Tensor, workspace: Tensor, rows_per_block: int, bias: Optional[Tensor],
+                         tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    return _forward_rows_impl(x, expert_ids, workspace, rows_per_block, bias, tensor_args, meta_args)
+
+
+@torch.library.register_fake("gemlite::forward_experts_rows")
+def _forward_experts_rows_fake(x, expert_ids, workspace, rows_per_block, bias, tensor_args, meta_args):
+    W_q = tensor_args[0]
+    _split(x, expert_ids, W_q.shape[1] * meta_args[4])
+    return torch.empty(tuple(expert_ids.shape) + (W_q.shape[2],), device=x.device, dtype=x.dtype)
+
+
+class ExpertsRouting:
+    """The work table of one set of expert ids (``GemLiteExperts.route``): the slots sorted into work blocks of at most
+    ``rows_per_block`` slots of one expert, on the GPU.  Owns the workspace tensor; valid for every ``GemLiteExperts`` with ``n_experts``
+    experts that takes ``rows_per_block`` — the two stacks of an MLP share one.  The table is written when the route launch RUNS: inside
+    a captured graph it follows the ids of every replay."""
+    __slots__ = ("workspace", "rows_per_block", "n_slots", "n_experts")
+
+    def __init__(self, workspace: Tensor, rows_per_block: int, n_slots: int, n_experts: int):
+        if rows_per_block not in ROWS_PER_BLOCK:
+            raise ValueError(f"rows_per_block is {rows_per_block}: one of {ROWS_PER_BLOCK}")
+        need = rows_workspace_ints(max(n_slots, 1), n_experts, rows_per_block)
+        if workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.numel() < need:
+            raise ValueError(f"the workspace is {workspace.dtype} {tuple(workspace.shape)}: {n_slots} slots over {n_experts} experts in "
+                             f"blocks of {rows_per_block} need {need} int32 entries")
+        self.workspace, self.rows_per_block, self.n_slots, self.n_experts = workspace, int(rows_per_block), int(n_slots), int(n_experts)
+
+    @property
+    def blocks_max(self) -> int:
+        return rows_blocks_max(max(self.n_slots, 1), self.n_experts, self.rows_per_block)
+
+    def __repr__(self):
+        return f"ExpertsRouting(n_slots={self.n_slots}, n_experts={self.n_experts}, rows_per_block={self.rows_per_block})"
+
+
 class GemLiteExperts(torch.nn.Module):
     """E stacked A16W4 layers; ``experts(x, expert_ids)`` -> ``[..., top_k, N]`` in one launch (module docstring).
     ``forward_glu`` / ``forward_combine`` are the same launch with the rest of an expert MLP in its epilogue (GemLiteExpertsMLP)."""
@@ -381,6 +546,47 @@ class GemLiteExperts(torch.nn.Module):
             return forward_experts(x, expert_ids, self.bias, self.get_tensor_args(), self._meta)
         return _forward_impl(x, expert_ids, self.bias, self.get_tensor_args(), self._meta)
 
+    # ------------------------------------------------------------------------------------- batches
+    def rows_per_block(self, n_slots: int, rows_per_block: Optional[int] = None) -> int:
+        """The work-block size R the library resolves for `n_slots` slots on these experts (None: its default); host only."""
+        return _resolve_rows(self.bias, self.get_tensor_args(), self._meta, n_slots, rows_per_block)
+
+    def route(self, expert_ids: Tensor, rows_per_block: Optional[int] = None) -> ExpertsRouting:
+        """Sort the slots of ``expert_ids`` by expert into work blocks, in ONE launch that reads the ids on the GPU (no host
+        synchronisation; capturable).  The result feeds ``forward_batched`` of every stack with as many experts that takes its R."""
+        if expert_ids.dim() < 1:
+            raise ValueError("expert_ids should be [..., top_k]")
+        n_slots = expert_ids.numel()
+        if n_slots > MAX_SLOTS:
+            raise NotImplementedError(f"GemLiteExperts.route: {n_slots} slots; one routing holds at most {MAX_SLOTS}")
+        R = self.rows_per_block(n_slots, rows_per_block)
+        if torch.compiler.is_compiling():
+            ws = experts_route(expert_ids, R, self.bias, self.get_tensor_args(), self._meta)
+        else:
+            ws = _route_impl(expert_ids, R, self.bias, self.get_tensor_args(), self._meta)
+        return ExpertsRouting(ws, R, n_slots, self.num_experts)
+
+    def forward_batched(self, x: Tensor, expert_ids: Tensor, routing: Optional[ExpertsRouting] = None) -> Tensor:
+        """-> ``[..., top_k, N]`` like ``forward``, for MORE THAN ONE token: every expert's weights stream once per work block of the
+        routing through the MFMA rows kernel.  A valid slot is bit-identical to its row of that expert's own rows-kernel launch (NOT to
+        ``forward``, whose decode kernel sums K in another order); a slot with an id outside [0, E) is a row of zeros."""
+        self._check_x(x)
+        if expert_ids.dim() < 1:
+            raise ValueError("expert_ids should be [..., top_k]")
+        _split(x, expert_ids, self.in_features)
+        if routing is None:
+            routing = self.route(expert_ids)
+        elif not isinstance(routing, ExpertsRouting):
+            raise TypeError(f"routing is a {type(routing).__name__}: an ExpertsRouting from GemLiteExperts.route, or None")
+        if routing.n_slots != expert_ids.numel() or routing.n_experts != self.num_experts:
+            raise ValueError(f"the routing holds {routing.n_slots} slots over {routing.n_experts} experts; expert_ids has "
+                             f"{expert_ids.numel()} slots and these are {self.num_experts} experts")
+        if routing.rows_per_block > 32 and self._meta[2] == 32:
+            raise NotImplementedError(f"the routing has work blocks of {routing.rows_per_block} rows: groups of 32 take 16 or 32 "
+                                      "(route with rows_per_block=32, or with the stack of the smaller group size)")
+        args = (x, expert_ids, routing.workspace, routing.rows_per_block, self.bias, self.get_tensor_args(), self._meta)
+        return forward_experts_rows(*args) if torch.compiler.is_compiling() else _forward_rows_impl(*args)
+
     def _check_fused(self, epilogue: int, top_k: int):
         """The library's answer for a fused epilogue on these experts (gemlite_hip_experts_fused_query on stand-ins, as _check_domain asks
         it), once per (epilogue, top_k), in words."""
@@ -460,3 +666,21 @@ class GemLiteExpertsMLP(torch.nn.Module):
 
     def forward(self, x: Tensor, topk_ids: Tensor, topk_weights: Tensor) -> Tensor:
         return self.down.forward_combine(self.gate_up.forward_glu(x, topk_ids), topk_ids, topk_weights)
+
+    def rows_per_block(self, n_slots: int) -> int:
+        """The work-block size both stacks take: each one's own default where they agree, else the smaller (valid for both: only the
+        cap of groups of 32 separates the defaults of two stacks with the same experts and slots)."""
+        return min(self.gate_up.rows_per_block(n_slots), self.down.rows_per_block(n_slots))
+
+    def forward_batched(self, x: Tensor, topk_ids: Tensor, topk_weights: Tensor) -> Tensor:
+        """``forward`` for MORE THAN ONE token: ONE route, ``gate_up.forward_batched``, ``silu(gate) * up`` in torch (fp32, one rounding),
+        ``down.forward_batched`` on the SAME routing, the routing-weight sum in torch (fp32, one rounding) -> ``[..., hidden]``."""
+        if topk_ids.dim() < 1:
+            raise ValueError("topk_ids should be [..., top_k]")
+        _weights_like(topk_weights, topk_ids, x)
+        routing = self.gate_up.route(topk_ids, self.rows_per_block(topk_ids.numel()))
+        y = self.gate_up.forward_batched(x, topk_ids, routing).float()
+        inter = self.intermediate_size
+        h = (torch.nn.functional.silu(y[..., :inter]) * y[..., inter:]).to(x.dtype)
+        d = self.down.forward_batched(h, topk_ids, routing).float()
+        return (d * topk_weights.float().unsqueeze(-1)).sum(-2).to(x.dtype)

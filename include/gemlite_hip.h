@@ -473,6 +473,47 @@ typedef struct gemlite_hip_experts_fused_args {
 int gemlite_hip_forward_experts_fused(const gemlite_hip_experts_fused_args* args, void* stream);
 int gemlite_hip_experts_fused_query(const gemlite_hip_experts_fused_args* args);
 
+/* Experts for BATCHES (more than one token): the slots are sorted by expert ON THE GPU and every expert's weights stream once per work
+ * block of up to R = rows_per_block slots through the matrix core (gemm_w4_rows_experts_kernel, gemm_wn_rows_experts.hip: the body of
+ * gemm_w4_rows_kernel with gathered x rows and scattered output rows).  Two launches, no host synchronisation, both graph-capturable:
+ *   gemlite_hip_experts_route         reads experts.ids (experts.n_slots entries of experts.ids_dtype) and writes the work table into
+ *                                     `workspace`; it reads experts.ids / ids_dtype / n_slots / n_experts and nothing else of `experts`'
+ *                                     pointers, and validates the whole request as gemlite_hip_forward_experts_rows does.
+ *   gemlite_hip_forward_experts_rows  consumes a routed workspace: grid (N / 16, Bmax), block (tile, b) computes the 16 columns of tile for
+ *                                     the slots of work block b.  Slot s reads x row s / slots_per_x_row and writes layer.out +
+ *                                     s * stride_out_slot, as in gemlite_hip_forward_experts.
+ * Work table (int32): [0] the number of work blocks used, [1..3] zero, then block_expert[Bmax], then block_rows[Bmax * R] — the slot
+ * indices of each work block, padded with -1.  A work block holds at most R slots of ONE expert; an expert with c slots has ceil(c / R)
+ * blocks; ids outside [0, n_experts) (the test of gemlite_hip_forward_experts) form bucket n_experts, whose slots get N zeros.
+ * Bmax = ceil(n_slots / R) + min(n_experts + 1, n_slots); entries beyond the used count are unspecified and never read.  The order of
+ * the slots inside an expert's blocks is unspecified: no output depends on it.
+ * Numerics: every valid slot is bit-identical to gemm_w4_rows_kernel (tuning[0] = 9) of that expert with R / 16 row tiles on a matrix that
+ * holds the slot's x row, bias added as gemlite_hip_forward_ex adds it.  (The decode launches above sum K in another order.)
+ * rows_per_block: 0 = the library's default (the smallest of 16 / 32 / 48 / 64 that holds the mean slots per expert, m = n_slots /
+ * min(n_experts, n_slots), plus a quarter: m + m / 4 in integers), else 16 / 32 / 48 / 64; groups of 32 allow 16 / 32 only (registers).
+ * Domain: that of gemlite_hip_forward_experts, then the rows kernel's: 16-byte aligned x rows (stride_x_row % 8), 4-byte aligned out and
+ * an even stride_out_slot, n_experts <= GEMLITE_EXPERTS_ROWS_MAX_EXPERTS, n_slots <= 65535, the extent of x — (ceil(n_slots /
+ * slots_per_x_row) - 1) * stride_x_row * 2 + K * 2 bytes — below 2^31.  The workspace is non-null, 4-byte aligned and at least
+ * gemlite_hip_experts_rows_workspace_bytes long (GEMLITE_ERR_WORKSPACE otherwise).
+ *   gemlite_hip_experts_rows_workspace_bytes  bytes of the work table for (n_slots, n_experts, R = 16 / 32 / 48 / 64); 0 for arguments
+ *                                             outside the domain
+ *   gemlite_hip_experts_rows_per_block        the R the library resolves for `args` (workspace fields not read), or a negative status
+ *   gemlite_hip_experts_rows_query            validates and never launches or dereferences; works without a GPU */
+#define GEMLITE_EXPERTS_ROWS_MAX_EXPERTS 4096
+typedef struct gemlite_hip_experts_rows_args {
+    uint32_t struct_size;             /* sizeof(gemlite_hip_experts_rows_args), ABI guard */
+    int32_t rows_per_block;           /* 0 (default) | 16 | 32 | 48 | 64 */
+    gemlite_hip_experts_args experts; /* exactly as for gemlite_hip_forward_experts */
+    void* workspace;                  /* device, the work table */
+    uint64_t workspace_bytes;
+    int64_t reserved[2];
+} gemlite_hip_experts_rows_args;
+uint64_t gemlite_hip_experts_rows_workspace_bytes(int64_t n_slots, int64_t n_experts, int32_t rows_per_block);
+int gemlite_hip_experts_rows_per_block(const gemlite_hip_experts_rows_args* args);
+int gemlite_hip_experts_route(const gemlite_hip_experts_rows_args* args, void* stream);
+int gemlite_hip_forward_experts_rows(const gemlite_hip_experts_rows_args* args, void* stream);
+int gemlite_hip_experts_rows_query(const gemlite_hip_experts_rows_args* args);
+
 /* Per-token dynamic activation quantisation: for each row m of x[M,K] (fp16/bf16/fp32)
  *   s[m] = max(amax(|x[m,:]|) / qmax, 1e-6) (fp32);  y = clamp(x / s, qmin, qmax);
  *   int8: round half away from zero;  fp8: round-to-nearest-even cast.

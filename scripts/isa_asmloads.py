@@ -20,7 +20,7 @@ import isa_loops as L
 
 DECODE3_GROUPED = "gemv_w4_decode3_group_kernel"
 FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", DECODE3_GROUPED,
-            "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel")
+            "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel", "gemm_w4_rows_experts_kernel", "gemm_w4_rows_bias_experts_kernel")
 # gemv_wn_kernel (round 6: gvw::ring2_run): the prologue requests up to two chunks behind uniform branches and the last one to three chunks run in
 # straight-line code BEHIND the loop — replayed in address order (no branch is followed), prologue and tail included, every conditional request
 # issued and every run of alternative waits taken at its weakest member
@@ -32,9 +32,11 @@ FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_r
 # trip of that copy's loop would show is not seen.  (Both copies are the same source with one `if constexpr` apart.)
 LINEAR_WITH_TAIL = ("gemv_wn_kernel", DECODE3_GROUPED)
 # gemm_w4_rows_group_kernel / gemm_w4_rows_bias_group_kernel: the grouped forms of gemm_w4_rows_kernel (gemm_wn_rows_group.hip) — the same body
-# behind a scalar selection of the member's pointers, replayed like the single-layer forms
+# behind a scalar selection of the member's pointers, replayed like the single-layer forms; gemm_w4_rows_experts_kernel /
+# gemm_w4_rows_bias_experts_kernel (gemm_wn_rows_experts.hip): the same body behind the work table's loads, which hipcc waits for itself
 ALTERNATIVE_WAITS = ("gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", DECODE3_GROUPED,
-                     "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel")
+                     "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel", "gemm_w4_rows_experts_kernel",
+                     "gemm_w4_rows_bias_experts_kernel")
 DECODE3_GROUPED_FORMS = 24  # 2 dtypes x biased x shared x x H
 
 VREG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
