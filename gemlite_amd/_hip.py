@@ -308,6 +308,10 @@ def load():
         lib.gemlite_hip_capture_group_lines.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         lib.gemlite_hip_capture_group_last_lines.restype = C.c_int
         lib.gemlite_hip_capture_group_last_lines.argtypes = []
+        lib.gemlite_hip_capture_group_policy.restype = C.c_int
+        lib.gemlite_hip_capture_group_policy.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32]
+        lib.gemlite_hip_capture_group_last_policy.restype = C.c_int
+        lib.gemlite_hip_capture_group_last_policy.argtypes = []
         lib.gemlite_hip_capture_group_form.restype = C.c_int
         lib.gemlite_hip_capture_group_form.argtypes = [C.c_int32, C.c_int32, C.c_int64]
         lib.gemlite_hip_capture_group_shared_x_lds_bytes.restype = C.c_int64
@@ -379,6 +383,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_capture_group_last_form", "gemlite_hip_capture_group_form", "gemlite_hip_capture_group_shared_x_lds_bytes",
     "gemlite_hip_capture_group_geometry", "gemlite_hip_capture_group_tile_of",
     "gemlite_hip_capture_group_lines", "gemlite_hip_capture_group_last_lines",
+    "gemlite_hip_capture_group_policy", "gemlite_hip_capture_group_last_policy",
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
     "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize", "gemlite_hip_quantize_groups_hqq",
     "gemlite_hip_quantize_rows",

@@ -76,6 +76,8 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
 bool capture_group_shared_x_enabled();
 int capture_group_last_form();
 int capture_group_last_lines();
+int capture_group_last_policy();
+int capture_group_policy_forced();
 int capture_group_lines_wanted(int tiles, int members, int resident, int tb);
 Decode3TilesWanted capture_group_tiles_wanted(int tiles, int members, int resident);
 int ensure_lds(const void* fn, size_t lds, int dev);
@@ -1035,6 +1037,13 @@ int gemlite_hip_capture_group_geometry(int32_t tiles, int32_t members, int32_t r
 }
 
 int gemlite_hip_capture_group_last_lines(void) { return capture_group_last_lines(); }
+
+int gemlite_hip_capture_group_last_policy(void) { return capture_group_last_policy(); }
+
+int gemlite_hip_capture_group_policy(int32_t h, int32_t default_policy_loads, uint64_t w_bases_or, uint32_t pitch_bytes, int32_t forced) {
+    if ((h != 1 && h != 2 && h != 4) || forced < -2 || forced > 1) return -1;
+    return decode3_group_nt(h, default_policy_loads == 0, w_bases_or, pitch_bytes, forced == -2 ? capture_group_policy_forced() : forced) ? 1 : 0;
+}
 
 int gemlite_hip_capture_group_lines(int32_t tiles, int32_t members, int32_t resident, int32_t tb, int32_t h_want) {
     if (tiles < 1 || members < 1 || members > DECODE3_GMAX || resident < 1 || (tb != 1 && tb != 2 && tb != 4) || tiles % tb || h_want < 0 ||

@@ -39,6 +39,11 @@
 // rows.  H divides TB; it is chosen at every join (decode3_group_lines_default), and every H has kernel functions of its own.
 // GEMLITE_HIP_CAPTURE_GROUP_LINES=1|2|4 (development, read once) forces the H asked for; one that TB does not admit falls back 4 -> 2 -> 1.
 //
+// POLICY (gl_common.h: decode3_group_nt): a grouped node asks for its weights non-temporally when its waves ask for whole lines (H >= 2), its
+// members' own launches are non-temporal (no GEMLITE_TF_GEMV_DEFAULT_POLICY_LOADS in the layer's tuning) and every member's weight base and
+// the row pitch are multiples of 128 bytes; evaluated at every join, so one member 64 bytes into a line puts the group back on the
+// default-policy form.  GEMLITE_HIP_CAPTURE_GROUP_NT=0|1 (development, read once) forces the policy; a forced 1 still falls back where H = 1.
+//
 // ROWS GROUPS (family 2).  A serving engine captures one graph per batch size; with two or more requests in a step every 4- / 2-bit layer runs
 // gemm_w4_rows_kernel / gemm_w2_rows_kernel (gemm_wn_rows.hip, LaunchPlan::arg_kind == 2), and q / k / v, gate / up and the experts of a step
 // pay the launch boundary each.  They group under the same look-back, independence rule, member limit and counters: a rows launch joins
@@ -58,9 +63,9 @@
 
 namespace gl {
 
-// gemv_decode.hip: the grouped forms (h: tiles per wave), default-policy weight loads whatever the members' launches use.  A group holds
-// biased launches or unbiased ones, never both: their kernel functions differ, so same_launch() keeps them apart
-const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h);
+// gemv_decode.hip: the grouped forms (h: tiles per wave; nt: non-temporal weight requests, H >= 2 only).  A group holds biased launches
+// or unbiased ones, never both, and launches of one load policy: their kernel functions differ, so same_launch() keeps them apart
+const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h, bool nt);
 int ensure_lds(const void* fn, size_t lds, int dev);            // api.hip
 
 namespace {
@@ -151,6 +156,7 @@ struct Group {
     hipGraphNode_t node = nullptr;
     LaunchPlan lp{};  // member 0: kernel, grid, block, scalars
     bool same_x = true;  // every member so far reads member 0's x
+    uintptr_t w_or = 0;  // every member's weight base, OR-ed: the alignment decode3_group_nt() asks about
     GroupTable<true> tab{};  // members 1 .. and every member's bias; an unbiased kernel's argument is its prefix (gl_common.h)
     Footprint fp[DECODE3_GMAX];
     int members = 0;
@@ -158,6 +164,7 @@ struct Group {
 thread_local Group tl_group;
 thread_local int tl_last_form = 0;  // of the last group node this thread rewrote: decode3_group_form()
 thread_local int tl_last_lines = 0;  // and its H (0: no grouped decode node yet)
+thread_local int tl_last_policy = -1;  // and its weight-load policy: 0 default, 1 non-temporal (-1: no grouped decode node yet)
 
 bool capture_state(hipStream_t st, unsigned long long* id, hipGraph_t* graph, hipGraphNode_t* only_dep) {
     hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
@@ -214,7 +221,17 @@ int capture_group_lines_wanted(int tiles, int members, int resident, int tb) {
     return forced ? forced : decode3_group_lines_default(tiles, members, resident, tb);
 }
 
+// The policy try_join() hands decode3_group_nt(): what GEMLITE_HIP_CAPTURE_GROUP_NT forces (0 / 1), or -1: the rule
+int capture_group_policy_forced() {
+    static const int forced = [] {
+        const int v = env_int("GEMLITE_HIP_CAPTURE_GROUP_NT", -1);
+        return v < 0 ? -1 : (v ? 1 : 0);
+    }();
+    return forced;
+}
+
 int capture_group_last_form() { return tl_last_form; }
+int capture_group_last_policy() { return tl_last_policy; }
 int capture_group_last_lines() { return tl_last_lines; }
 
 void capture_group_stats(uint64_t* seen, uint64_t* joined) {
@@ -292,6 +309,7 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
             return false;
         tl_last_form = 3;
         tl_last_lines = 0;
+        tl_last_policy = -1;
         return true;
     }
     Decode3Args& d = g.lp.d3;
@@ -305,19 +323,23 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
                      (void*)&d.nch_total, (void*)&modes, (void*)&g.tab};
     const bool same_x = g.same_x && lp.d3.x == d.x;
     int form = decode3_group_form(members, same_x, d.nch_total, capture_group_shared_x_enabled());
-    // (every H has kernel functions of its own.  The cap is raised once per kernel and device, to the form's maximum: the size of a launch depends on its K)
-    const void* fn = gemv_w4_decode3_group_fn(g.lp.d3_group_tag, biased, form == 2, lines);
+    const uintptr_t w_or = g.w_or | (uintptr_t)lp.d3.w;
+    const bool nt = decode3_group_nt(lines, g.lp.d3_nt, (uint64_t)w_or, d.sw4, capture_group_policy_forced());
+    // (every H and either policy has kernel functions of its own.  The cap is raised once per kernel and device, to the form's maximum: the size of a launch depends on its K)
+    const void* fn = gemv_w4_decode3_group_fn(g.lp.d3_group_tag, biased, form == 2, lines, nt);
     if (form == 2 && ensure_lds(fn, (size_t)DECODE3_SHARED_X_MAX_LDS, dev) != GEMLITE_OK) {
         form = 1;
-        fn = gemv_w4_decode3_group_fn(g.lp.d3_group_tag, biased, false, lines);
+        fn = gemv_w4_decode3_group_fn(g.lp.d3_group_tag, biased, false, lines, nt);
     }
     const size_t lds = form == 2 ? (size_t)decode3_shared_x_lds_bytes(d.nch_total) : 0;
     if (!rewrite_node(g, GroupMember{lp.d3.w, lp.d3.x, lp.d3.s, lp.d3.z, lp.d3.out}, lp.bias, fb, fn, dim3((unsigned)geo.grid_x, (unsigned)geo.grid_y, 1), lds,
                       kargs))
         return false;
     g.same_x = same_x;
+    g.w_or = w_or;
     tl_last_form = form;
     tl_last_lines = lines;
+    tl_last_policy = nt ? 1 : 0;
     return true;
 }
 
@@ -341,8 +363,10 @@ void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPl
     g.node = dep;
     g.lp = lp;
     g.same_x = true;
+    g.w_or = (uintptr_t)lp.d3.w;
     tl_last_form = 0;  // (a group of one: no grouped node yet)
     tl_last_lines = 0;
+    tl_last_policy = -1;
     memset(&g.tab, 0, sizeof(g.tab));
     g.tab.bias[0] = lp.bias;
     g.fp[0] = footprint(a, lp);

@@ -24,7 +24,8 @@
 //   kernel                                               argument behind the 14 dwords    launched by
 //   gemv_w4_decode3_kernel<Tag, NT, BIASED>              unsigned* counters (timeline) |  the planner: dependent chains, eager and profiled
 //                                                        Decode3BiasTail (BIASED)         launches, a group of one.  Wave w runs virtual wave w
-//   gemv_w4_decode3_group_kernel<Tag, BIASED, SX, HL>    GroupTable<BIASED> by value      capture_group.hip, by rewriting a capture's node
+//   gemv_w4_decode3_group_kernel<Tag, BIASED, SX, HL,    GroupTable<BIASED> by value      capture_group.hip, by rewriting a capture's node
+//                                NT>
 //   gemv_w4_decode3_experts_kernel<Tag, BIASED, IDS64>   ExpertsTail by value             gemlite_hip_forward_experts (api.hip): a block per
 //                                                                                         (tile, slot), the expert id read on the GPU, then
 //                                                                                         as the single-layer kernel
@@ -391,11 +392,14 @@ void gemv_w4_decode3_kernel(const char* wb, const char* xb, const char* sp, cons
 // order; the four row pairs 4 r .. 4 r + 3 still meet in one 16-lane DPP row (r = p * 4 / H + the row inside the sub-wave) and
 // land in partial row v * 4 + r of the slot's region: bit-exact under every H.  What depended on g depends on the pass through
 // SCALAR adds to the uniform bases (weights, x, metadata row) and one constant inside the shared-x LDS offsets.
-// Default-policy weight loads only, whatever the members' own launches use: the two 16-column tiles of a 128-byte line are read by two
-// different waves — with one tile per block (TB = 1) in two blocks on two CUs of one XCD, which meet in that XCD's L2 only; with tile
-// groups (TB = 2, 4) by neighbouring waves of one block — and nothing keeps the two in step: the partner asks for its half some time
-// later, and a non-temporal line has left the L2 by then (11.6 MB fetched per layer against 9.5; profiles/r13/decode_group_waves.log §2).
-template <typename Tag, bool BIASED, bool SX, int HL>
+// NT: non-temporal weight requests, H = 2 and 4 only (gl_common.h: decode3_group_nt has the rule; x, scales and zeros keep the default
+// policy — several waves of a block share those lines).  With whole lines per request no weight line is asked for twice and the L2 has
+// nothing to keep: the bytes fetched are unchanged, a request is outstanding 11 % shorter (profiles/r24/decode_group_policy.log §c).
+// H = 1 stays default-policy by construction: the two 16-column tiles of a 128-byte line are read by two different waves — with one
+// tile per block (TB = 1) in two blocks on two CUs of one XCD, which meet in that XCD's L2 only; with tile groups by neighbouring waves of
+// one block — and nothing keeps the two in step: the partner asks for its half some time later, and a non-temporal line has left the L2
+// by then (11.6 MB fetched per layer against 9.5; profiles/r13/decode_group_waves.log §2).
+template <typename Tag, bool BIASED, bool SX, int HL, bool NT>
 __global__ __launch_bounds__(1024, DECODE3_GROUP_WAVES_PER_SIMD)
 void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
                                   uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
@@ -480,8 +484,8 @@ void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp
     int rv = v0, rp = 0, rgc = v0;  // request cursor: virtual wave, pass, chunk
     auto request = [&](Chunk& ck, int) __attribute__((always_inline)) {
         const char* wq = w_ + ((uint32_t)rgc * chunk_w + (uint32_t)rp * pass_w);
-        gvw::gld128<false>(ck.w[0], wq, vw0);
-        gvw::gld128<false>(ck.w[1], wq, vw1);
+        gvw::gld128<NT>(ck.w[0], wq, vw0);
+        gvw::gld128<NT>(ck.w[1], wq, vw1);
         if constexpr (!SX) gvw::gld64(ck.xq, x_ + ((uint32_t)rgc * (uint32_t)(CHUNK * 16) + (uint32_t)rp * pass_x), vx);
         const uint32_t grp = (((uint32_t)rgc << shl) >> shr) + (((uint32_t)rp << (8 - hl)) >> pass_ms);
         gvw::gld64(ck.s, sb + grp * ms_s, vs);
@@ -788,14 +792,22 @@ const void* gemv_w4_decode3_experts_fused_fn(int tag, int epilogue, bool biased,
         });
     });
 }
-// Every grouped form (h: the tiles per wave, 1 / 2 / 4; anything else: 1)
-const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h) {
+// Every grouped form (h: the tiles per wave, 1 / 2 / 4; anything else: 1.  nt: non-temporal weight requests, H = 2 and 4 only — with one
+// tile per wave the other half of a line belongs to another wave, and that form stays default-policy whatever is asked)
+const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h, bool nt) {
     return with_tag(tag, [&](auto T) {
         return with_bool(biased, [&](auto B) {
             return with_bool(shared_x, [&](auto SX) {
-                return h == 4 ? (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 2>
-                              : (h == 2 ? (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 1>
-                                        : (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 0>);
+                return with_bool(nt && (h == 2 || h == 4), [&](auto NT) {
+                    if constexpr (NT()) {
+                        return h == 4 ? (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 2, true>
+                                      : (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 1, true>;
+                    } else {
+                        return h == 4 ? (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 2, false>
+                                      : (h == 2 ? (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 1, false>
+                                                : (const void*)gemv_w4_decode3_group_kernel<decltype(T), B(), SX(), 0, false>);
+                    }
+                });
             });
         });
     });

@@ -972,7 +972,8 @@ bool plan_gemv_wn(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan& lp
                 lp.name = "gemv_w4_decode3_kernel<tile16,16w>";
                 lp.bias_of = lp.fn;
                 lp.fn_bias = gemv_w4_decode3_bias_fn(f16 ? 0 : 1, nt);
-                lp.d3_group_tag = f16 ? 0 : 1;  // (the grouped forms exist for both load policies and with or without the bias)
+                lp.d3_group_tag = f16 ? 0 : 1;  // (the grouped forms exist with or without the bias; their load policy follows d3_nt)
+                lp.d3_nt = nt;
                 lp.lds_bytes = 0;  // static LDS
                 lp.d3.w = (const char*)p.w;
                 lp.d3.x = (const char*)p.x;

@@ -762,6 +762,19 @@ inline int decode3_group_lines_default(int tiles, int members, int64_t resident,
     const int lb = (members + geo.grid_y - 1) / geo.grid_y;  // layers of the fullest block
     return (geo.tb == 4 && lb >= 4) ? 4 : 2;
 }
+// POLICY.  Does a grouped launch ask for its weights non-temporally (the NT forms of gemv_w4_decode3_group_kernel)?  Only when
+//   * H >= 2: one request instruction covers whole 128-byte lines.  With H = 1 the other half of a line belongs to another wave, which
+//     asks later, when a non-temporal line has left the L2 (profiles/r13/decode_group_waves.log §2);
+//   * the members' own launches are non-temporal (members_nt: the layer's tuning carries no GEMLITE_TF_GEMV_DEFAULT_POLICY_LOADS — the
+//     switch for a model whose weights stay in the Infinity Cache from step to step);
+//   * every member's weight base and the row pitch sw4 are multiples of 128 bytes (w_bases_or: the members' bases OR-ed together).
+//     Otherwise a line straddles two waves' requests again: slower, never wrong.
+// forced: -1 the rule; 0 / 1 GEMLITE_HIP_CAPTURE_GROUP_NT — a forced 1 overrides the last two conditions, never the first.
+GL_HD bool decode3_group_nt(int h, bool members_nt, uint64_t w_bases_or, uint32_t sw4, int forced = -1) {
+    if (h < 2 || forced == 0) return false;
+    if (forced > 0) return true;
+    return members_nt && ((w_bases_or | (uint64_t)sw4) & 127u) == 0;
+}
 // What capture_group.hip asks decode3_group_geometry() for when nothing is forced: {tb_want, span} from the group's shape.
 // THE RULE (measured: profiles/r16/decode_group_tiles.log §4 - §6): the interleaved placement, and the largest TB whose busiest CU gets
 // at most 5/4 of the work the busiest CU has with one tile per block.  Work of the busiest CU in (layer, tile) slots: rounds of blocks
@@ -830,6 +843,7 @@ struct LaunchPlan {
     const void* fn_bias_group = nullptr;
     // decode3 launches: the dtype tag capture_group.hip asks gemv_w4_decode3_group_fn() with, at every join (H, shared x: the join's choice)
     int d3_group_tag = -1;  // 0 fp16 | 1 bf16 | -1: the launch has no grouped forms
+    bool d3_nt = false;     // `fn` asks for its weights non-temporally (decode3_group_nt: a group follows its members)
 };
 
 }  // namespace gl

@@ -370,7 +370,18 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
  *                block's slots / H wave-slots are what _wave_split calls layers.  H divides TB: h_want = 4 falls back to 2, then 1.
  *                h_want = 0: what a capture picks (GEMLITE_HIP_CAPTURE_GROUP_LINES=1|2|4, read once, or the default rule).  -1 for an
  *                argument out of range
- *   _last_lines  host only: the H of the grouped decode node the calling thread rewrote last (0: none) */
+ *   _last_lines  host only: the H of the grouped decode node the calling thread rewrote last (0: none)
+ *   _policy      host only, DEVELOPMENT / TEST: does a grouped decode launch of H = `h` (1, 2, 4) tiles per wave ask for its weights
+ *                non-temporally?  1 only when h >= 2, the members' own launches are non-temporal (default_policy_loads = 0: the layers'
+ *                tuning[3] carries no GEMLITE_TF_GEMV_DEFAULT_POLICY_LOADS) and every member's weight base (w_bases_or: the bases OR-ed
+ *                together) and the row pitch in bytes are multiples of 128: one request then covers whole lines that nobody asks for again.
+ *                forced = 0 / 1 overrides the last two conditions (never h >= 2), -1 is the rule alone, -2 what a capture picks
+ *                (GEMLITE_HIP_CAPTURE_GROUP_NT=0|1, read once, or the rule).  0 / 1, or -1 for an argument out of range.
+ *                Weights that stay in the 256 MiB Infinity Cache from step to step are read 3 - 6 % faster with the default
+ *                policy (the crossover lies between 286 and 572 MB of weights per step): set GEMLITE_TF_GEMV_DEFAULT_POLICY_LOADS in
+ *                such a model's tuning[3]
+ *   _last_policy host only: the weight-load policy of the grouped decode node the calling thread rewrote last: 0 default, 1
+ *                non-temporal, -1 none */
 int gemlite_hip_capture_group_max(void);
 void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
@@ -383,6 +394,8 @@ int gemlite_hip_capture_group_geometry(int32_t tiles, int32_t members, int32_t r
 int gemlite_hip_capture_group_tile_of(int32_t tiles, int32_t tb, int32_t span, int32_t block);
 int gemlite_hip_capture_group_lines(int32_t tiles, int32_t members, int32_t resident, int32_t tb, int32_t h_want);
 int gemlite_hip_capture_group_last_lines(void);
+int gemlite_hip_capture_group_policy(int32_t h, int32_t default_policy_loads, uint64_t w_bases_or, uint32_t pitch_bytes, int32_t forced);
+int gemlite_hip_capture_group_last_policy(void);
 
 /* Bias in the launch (optional extension; gemlite_hip_forward_args and every entry point above are unchanged).  The M = 1 decode kernel
  * (gemv_w4_decode3_kernel, single and grouped) and the few-row kernels (gemm_w4_rows_kernel / gemm_w2_rows_kernel) have forms that add a

@@ -1,9 +1,11 @@
-"""Are the kernels of one device assembly file unchanged in another?   python scripts/compare_kernel_asm.py [--by-body] OLD.s NEW.s
+"""Are the kernels of one device assembly file unchanged in another?   python scripts/compare_kernel_asm.py [--by-body [--allow-new]] OLD.s NEW.s
 
 Both files come from `hipcc <the unit's flags> -S --cuda-device-only unit.hip`.  Every function of OLD must exist in NEW with the same
 instructions (comments, debug directives and local label numbers aside); functions only NEW has are counted.  Exit status 1 on a difference.
 --by-body: for a change that renames kernels.  Names are ignored (a function's own name inside its body too): the bodies of OLD and of NEW
-must be equal as multisets, and so must the resource figures of their "Kernel info" blocks (registers, scratch, LDS, occupancy)."""
+must be equal as multisets, and so must the resource figures of their "Kernel info" blocks (registers, scratch, LDS, occupancy).
+--allow-new: with --by-body, for a change that renames kernels AND adds some: bodies and resource lines that only NEW has are listed and
+counted, and only those of OLD without an equal in NEW are a difference."""
 import collections
 import re
 import subprocess
@@ -32,7 +34,7 @@ def funcs(path, resources=None):
     return out
 
 
-def by_body(old_path, new_path):
+def by_body(old_path, new_path, allow_new=False):
     bad, files = 0, []
     for path in (old_path, new_path):
         res = {}
@@ -42,7 +44,7 @@ def by_body(old_path, new_path):
     for what in ('bodies', 'resources'):
         old, new = (collections.Counter(f[what].values()) for f in files)
         gone, come = old - new, new - old
-        bad += sum(gone.values()) + sum(come.values())
+        bad += sum(gone.values()) + (0 if allow_new else sum(come.values()))
         print(f'{old_path} -> {new_path}, by body: {sum(old.values())} and {sum(new.values())} kernels, {len(old)} and {len(new)} '
               f'distinct {what}; {sum(gone.values())} of the first file have no equal in the second, {sum(come.values())} of the second none in the first')
         for label, side, f in (('only in the first file: ', gone, files[0]), ('only in the second file:', come, files[1])):
@@ -56,6 +58,8 @@ def by_body(old_path, new_path):
 def main():
     if len(sys.argv) == 4 and sys.argv[1] == '--by-body':
         return by_body(sys.argv[2], sys.argv[3])
+    if len(sys.argv) == 5 and sys.argv[1:3] == ['--by-body', '--allow-new']:
+        return by_body(sys.argv[3], sys.argv[4], True)
     if len(sys.argv) != 3:
         print(__doc__)
         return 2

@@ -25,7 +25,7 @@ FAMILIES = ("gemm_wn_mma_kernel", "gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_r
 # straight-line code BEHIND the loop — replayed in address order (no branch is followed), prologue and tail included, every conditional request
 # issued and every run of alternative waits taken at its weakest member
 # DECODE3_GROUPED (round 13): gemv_w4_decode3_group_kernel (gemv_decode.hip) — the single-layer gemv_w4_decode3_kernel keeps hipcc's own loads.
-# All 24 forms must be found: fewer is a failure, not "nothing could be checked".  The kernel holds gvw::ring2_run TWICE (metadata selects
+# All 40 forms must be found: fewer is a failure, not "nothing could be checked".  The kernel holds gvw::ring2_run TWICE (metadata selects
 # compiled in / out), each copy with its own first requests, loop and
 # peeled tail, each ending drained.  What the replay covers: the copy whose loop is picked (most v_dot2; the first on a tie) is replayed with its
 # wrap-around trips; the OTHER copy is replayed in address order only — first requests, ONE trip of its loop, its tail — so a touch that only a second
@@ -37,7 +37,7 @@ LINEAR_WITH_TAIL = ("gemv_wn_kernel", DECODE3_GROUPED)
 ALTERNATIVE_WAITS = ("gemm_w4_rows_kernel", "gemv_wn_kernel", "w8_rows_lds_kernel", DECODE3_GROUPED,
                      "gemm_w4_rows_group_kernel", "gemm_w4_rows_bias_group_kernel", "gemm_w4_rows_experts_kernel",
                      "gemm_w4_rows_bias_experts_kernel")
-DECODE3_GROUPED_FORMS = 24  # 2 dtypes x biased x shared x x H
+DECODE3_GROUPED_FORMS = 40  # 2 dtypes x biased x shared x x (H = 1, 2, 4 default policy + H = 2, 4 non-temporal)
 
 VREG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 
