@@ -312,6 +312,14 @@ def load():
         lib.gemlite_hip_capture_group_policy.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32]
         lib.gemlite_hip_capture_group_last_policy.restype = C.c_int
         lib.gemlite_hip_capture_group_last_policy.argtypes = []
+        lib.gemlite_hip_capture_group_merge_stats.restype = None
+        lib.gemlite_hip_capture_group_merge_stats.argtypes = [C.POINTER(C.c_uint64)]
+        lib.gemlite_hip_capture_group_rounds_max.restype = C.c_int
+        lib.gemlite_hip_capture_group_rounds_max.argtypes = []
+        lib.gemlite_hip_capture_group_last_rounds.restype = C.c_int
+        lib.gemlite_hip_capture_group_last_rounds.argtypes = []
+        lib.gemlite_hip_capture_group_round_member.restype = C.c_int
+        lib.gemlite_hip_capture_group_round_member.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         lib.gemlite_hip_capture_group_form.restype = C.c_int
         lib.gemlite_hip_capture_group_form.argtypes = [C.c_int32, C.c_int32, C.c_int64]
         lib.gemlite_hip_capture_group_shared_x_lds_bytes.restype = C.c_int64
@@ -384,6 +392,8 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_capture_group_geometry", "gemlite_hip_capture_group_tile_of",
     "gemlite_hip_capture_group_lines", "gemlite_hip_capture_group_last_lines",
     "gemlite_hip_capture_group_policy", "gemlite_hip_capture_group_last_policy",
+    "gemlite_hip_capture_group_merge_stats", "gemlite_hip_capture_group_rounds_max", "gemlite_hip_capture_group_last_rounds",
+    "gemlite_hip_capture_group_round_member",
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
     "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize", "gemlite_hip_quantize_groups_hqq",
     "gemlite_hip_quantize_rows",

@@ -76,6 +76,9 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
 bool capture_group_shared_x_enabled();
 int capture_group_last_form();
 int capture_group_last_lines();
+int capture_group_last_rounds();
+int capture_group_rounds_max();
+void capture_group_merge_stats(uint64_t* merged);
 int capture_group_last_policy();
 int capture_group_policy_forced();
 int capture_group_lines_wanted(int tiles, int members, int resident, int tb);
@@ -1037,6 +1040,19 @@ int gemlite_hip_capture_group_geometry(int32_t tiles, int32_t members, int32_t r
 }
 
 int gemlite_hip_capture_group_last_lines(void) { return capture_group_last_lines(); }
+
+void gemlite_hip_capture_group_merge_stats(uint64_t* merged) { capture_group_merge_stats(merged); }
+
+int gemlite_hip_capture_group_rounds_max(void) { return capture_group_rounds_max(); }
+
+int gemlite_hip_capture_group_last_rounds(void) { return capture_group_last_rounds(); }
+
+int gemlite_hip_capture_group_round_member(int32_t m, int32_t Y, int32_t block_y, int32_t local_layer) {
+    if (m < 1 || m > DECODE3_GMAX || Y < 1 || Y > m || block_y < 0 || local_layer < 0) return -1;
+    const int r = block_y / Y, y = block_y % Y;
+    if ((int64_t)m * (r + 1) > DECODE3_NODE_MAX || (int64_t)y + (int64_t)local_layer * Y >= m) return -1;
+    return decode3_round_member(m, Y, block_y, local_layer);
+}
 
 int gemlite_hip_capture_group_last_policy(void) { return capture_group_last_policy(); }
 

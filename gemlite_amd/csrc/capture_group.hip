@@ -44,6 +44,24 @@
 // the row pitch are multiples of 128 bytes; evaluated at every join, so one member 64 bytes into a line puts the group back on the
 // default-policy form.  GEMLITE_HIP_CAPTURE_GROUP_NT=0|1 (development, read once) forces the policy; a forced 1 still falls back where H = 1.
 //
+// ROUNDS (gl_common.h: decode3_round_member).  A node holds at most DECODE3_GMAX members because a block holds at most 16 slots, so a run of
+// 64 independent layers used to become four nodes and pay the dependent-launch boundary, the ramp and the tail four times.  When a join
+// makes the open decode group B FULL (members == the limit), B is merged into its predecessor A — the group that was open and full when
+// B's first launch was declined for the member limit, kept as this thread's "previous group" — if A is of the same capture and graph,
+// holds a whole number of full rounds below the round limit, same_launch(A, B) holds with both biased or both not, every member of B is
+// independent() of every member of A, and the RUNTIME says that the graph is the chain it should be: B's node has exactly one dependency,
+// A's node, and no dependent; A's node has exactly one dependent, B's node; the stream's only capture dependency is B's node (a fork
+// from another stream onto B, or anything foreign between A and B, rules the merge out).  A's node then becomes a node of R + 1 rounds:
+// grid (grid_x, Y (R + 1)), the table A's members followed by B's, form / H / policy by the rules above on all members (both nodes were
+// full: TB, Y and H agree); the stream's capture dependency is set back to A's node; B's node is destroyed; the open group is A, full,
+// so the next launch opens C, which merges when it fills, up to DECODE3_NODE_MAX / limit rounds.  Members of B are independent of A's
+// and of each other, so every intermediate state — B's members in both nodes — computes the right outputs; a step that fails undoes the
+// ones before it (A gets its parameters back), the runtime's error is swallowed and the capture is what it was without merging.  A
+// trailing partial group keeps its own node: its best (TB, H, form) is another.  Blocks go out x-fastest, one block is resident per CU, so
+// a CU takes its block of the next round as soon as its own block leaves.  GEMLITE_HIP_CAPTURE_GROUP_ROUNDS=1..4 (development, read once)
+// is the round limit, 1: no merging (the A/B switch inside one build); GEMLITE_HIP_NO_CAPTURE_GROUPS=1 turns merging off with the rest.
+// The rows family does not merge: its table stays at DECODE3_GMAX and its node already runs full-width members as rounds.
+//
 // ROWS GROUPS (family 2).  A serving engine captures one graph per batch size; with two or more requests in a step every 4- / 2-bit layer runs
 // gemm_w4_rows_kernel / gemm_w2_rows_kernel (gemm_wn_rows.hip, LaunchPlan::arg_kind == 2), and q / k / v, gate / up and the experts of a step
 // pay the launch boundary each.  They group under the same look-back, independence rule, member limit and counters: a rows launch joins
@@ -146,7 +164,7 @@ int env_int(const char* name, int absent) {
     return (v && *v) ? atoi(v) : absent;
 }
 
-std::atomic<uint64_t> g_seen{0}, g_joined{0};
+std::atomic<uint64_t> g_seen{0}, g_joined{0}, g_merged{0};
 
 struct Group {
     bool open = false;
@@ -157,11 +175,26 @@ struct Group {
     LaunchPlan lp{};  // member 0: kernel, grid, block, scalars
     bool same_x = true;  // every member so far reads member 0's x
     uintptr_t w_or = 0;  // every member's weight base, OR-ed: the alignment decode3_group_nt() asks about
-    GroupTable<true> tab{};  // members 1 .. and every member's bias; an unbiased kernel's argument is its prefix (gl_common.h)
-    Footprint fp[DECODE3_GMAX];
+    // members 1 .. and every member's bias; an unbiased kernel's argument is its prefix (gl_common.h).  A decode group keeps the node
+    // table (room for the rounds it may absorb), a rows group the table of its kernels
+    DecodeNodeTable<true> tab{};
+    GroupTable<true> rtab{};
+    Footprint fp[DECODE3_NODE_MAX];
     int members = 0;
+    int rounds = 1;         // decode: full rounds in the node once it has merged (members == rounds * limit then)
+    bool mergeable = true;  // false once a rewrite for a merge failed on this node
+    // the node as the last rewrite left it (decode groups): what a failed merge puts back
+    const void* node_fn = nullptr;
+    dim3 node_grid{1, 1, 1};
+    size_t node_lds = 0;
+    uint32_t node_modes = 0;
+    int node_form = 0, node_lines = 0, node_policy = -1;
 };
 thread_local Group tl_group;
+// The previous group: the one that was open and full when the launch that opened tl_group was declined for the member limit
+thread_local Group tl_prev;
+thread_local bool tl_prev_valid = false;
+thread_local int tl_last_rounds = 0;  // rounds of the last decode node this thread rewrote or merged (0: none yet)
 thread_local int tl_last_form = 0;  // of the last group node this thread rewrote: decode3_group_form()
 thread_local int tl_last_lines = 0;  // and its H (0: no grouped decode node yet)
 thread_local int tl_last_policy = -1;  // and its weight-load policy: 0 default, 1 non-temporal (-1: no grouped decode node yet)
@@ -233,6 +266,22 @@ int capture_group_policy_forced() {
 int capture_group_last_form() { return tl_last_form; }
 int capture_group_last_policy() { return tl_last_policy; }
 int capture_group_last_lines() { return tl_last_lines; }
+int capture_group_last_rounds() { return tl_last_rounds; }
+
+// Rounds a decode node may hold: GEMLITE_HIP_CAPTURE_GROUP_ROUNDS (1 .. 4, read once), within what the node table holds at this member limit
+int capture_group_rounds_max() {
+    static const int rounds = [] {
+        if (capture_group_limit() < 2) return 1;
+        const int n = env_int("GEMLITE_HIP_CAPTURE_GROUP_ROUNDS", DECODE3_ROUNDS_DEFAULT), cap = DECODE3_NODE_MAX / capture_group_limit();
+        const int r = n < 1 ? 1 : (n > DECODE3_ROUNDS_LIMIT ? DECODE3_ROUNDS_LIMIT : n);
+        return r > cap ? cap : r;
+    }();
+    return rounds;
+}
+
+void capture_group_merge_stats(uint64_t* merged) {
+    if (merged) *merged = g_merged.load(std::memory_order_relaxed);
+}
 
 void capture_group_stats(uint64_t* seen, uint64_t* joined) {
     if (seen) *seen = g_seen.load(std::memory_order_relaxed);
@@ -249,10 +298,7 @@ bool capture_group_compatible(const gemlite_hip_forward_args& a, const LaunchPla
 // What a join of either family does once its kernel, grid, LDS bytes and argument list are chosen: member g.members goes into the table
 // (its pointers behind the scalars of member 0), the node becomes `fn`, the bookkeeping.  A failed rewrite leaves the node what it was: the
 // group is dropped and this call runs on its own.
-static bool rewrite_node(Group& g, const GroupMember& mb, const uint16_t* bias, const Footprint& fb, const void* fn, dim3 grid, size_t lds,
-                         void** kargs) {
-    g.tab.m[g.members - 1] = mb;
-    g.tab.bias[g.members] = bias;
+static bool set_node(const Group& g, const void* fn, dim3 grid, size_t lds, void** kargs) {
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
     np.func = (void*)fn;
@@ -263,12 +309,129 @@ static bool rewrite_node(Group& g, const GroupMember& mb, const uint16_t* bias, 
     np.extra = nullptr;
     if (hipGraphKernelNodeSetParams(g.node, &np) != hipSuccess) {
         (void)hipGetLastError();
+        return false;
+    }
+    return true;
+}
+template <typename Table>
+static bool rewrite_node(Group& g, Table& tab, const GroupMember& mb, const uint16_t* bias, const Footprint& fb, const void* fn, dim3 grid,
+                         size_t lds, void** kargs) {
+    tab.m[g.members - 1] = mb;
+    tab.bias[g.members] = bias;
+    if (!set_node(g, fn, grid, lds, kargs)) {
         g.open = false;
         return false;
     }
     g.fp[g.members++] = fb;
     g_joined.fetch_add(1, std::memory_order_relaxed);
     return true;
+}
+
+// ROUNDS: the open decode group `b` has just become full and tl_prev is the full group in front of it.  Merge b into it when every
+// condition of the header holds; whatever happens, the capture computes what it computed without this call.  dep: the stream's only
+// capture dependency, as asked at the top of this join (b's node: the join added nothing).
+static size_t node_count(hipGraphNode_t node, bool dependents, hipGraphNode_t* only) {
+    size_t n = 0;
+    *only = nullptr;
+    if ((dependents ? hipGraphNodeGetDependentNodes(node, nullptr, &n) : hipGraphNodeGetDependencies(node, nullptr, &n)) != hipSuccess) {
+        (void)hipGetLastError();
+        return (size_t)-1;
+    }
+    if (n != 1) return n;
+    if ((dependents ? hipGraphNodeGetDependentNodes(node, only, &n) : hipGraphNodeGetDependencies(node, only, &n)) != hipSuccess) {
+        (void)hipGetLastError();
+        return (size_t)-1;
+    }
+    return n;
+}
+static void try_merge(Group& b, hipGraphNode_t dep, hipStream_t st, int resident, int dev) {
+    Group& a = tl_prev;
+    tl_prev_valid = false;  // one attempt: merged, a is the open group; not merged, b's successor has b (or nothing) in front of it
+    const int limit = capture_group_limit();
+    if (!a.mergeable || a.cap_id != b.cap_id || a.graph != b.graph || a.node == b.node || dep != b.node) return;
+    if (a.members != a.rounds * limit || b.members != limit || a.rounds >= capture_group_rounds_max() || a.members + b.members > DECODE3_NODE_MAX) return;
+    if (!same_launch(a.lp, b.lp) || (a.lp.bias != nullptr) != (b.lp.bias != nullptr) || !a.node_fn || !b.node_fn) return;
+    // the graph, as the runtime has it: ... -> A -> B, nothing else on either, and the stream waits for B alone (dep, above)
+    hipGraphNode_t only = nullptr;
+    if (node_count(b.node, false, &only) != 1 || only != a.node) return;
+    if (node_count(b.node, true, &only) != 0) return;
+    if (node_count(a.node, true, &only) != 1 || only != b.node) return;
+    for (int i = 0; i < a.members; ++i)
+        for (int j = 0; j < b.members; ++j)
+            if (!independent(a.fp[i], b.fp[j])) return;
+    // 1. A's node: one more round.  Both nodes are full, so (TB, Y, H) of a round are b's; form and policy over all members
+    Decode3Args& d = a.lp.d3;
+    const int tiles = (int)a.lp.grid.x, rounds = a.rounds + 1;
+    const Decode3TilesWanted want = capture_group_tiles_wanted(tiles, limit, resident);
+    const Decode3GroupGeometry geo = decode3_group_geometry(tiles, limit, resident, want.tb, want.span);
+    const int lines = decode3_group_lines(geo.tb, capture_group_lines_wanted(tiles, limit, resident, geo.tb));
+    uint32_t modes = decode3_group_modes(d.modes, limit, geo.grid_y, geo.tb, geo.span);
+    const dim3 grid((unsigned)geo.grid_x, (unsigned)(geo.grid_y * rounds), 1);
+    if (modes != b.node_modes || modes != a.node_modes || a.node_grid.x != grid.x || a.node_grid.y != (unsigned)(geo.grid_y * a.rounds) ||
+        lines != a.node_lines || lines != b.node_lines)
+        return;  // (a round of A and B's are not the same blocks: cannot happen with both full, and is not merged if it does)
+    const bool same_x = a.same_x && b.same_x && b.lp.d3.x == d.x;
+    int form = decode3_group_form(limit, same_x, d.nch_total, capture_group_shared_x_enabled());
+    const uintptr_t w_or = a.w_or | b.w_or;
+    const bool nt = decode3_group_nt(lines, a.lp.d3_nt && b.lp.d3_nt, (uint64_t)w_or, d.sw4, capture_group_policy_forced());
+    const bool biased = a.lp.bias != nullptr;
+    const void* fn = gemv_w4_decode3_group_fn(a.lp.d3_group_tag, biased, form == 2, lines, nt);
+    if (form == 2 && ensure_lds(fn, (size_t)DECODE3_SHARED_X_MAX_LDS, dev) != GEMLITE_OK) {
+        form = 1;
+        fn = gemv_w4_decode3_group_fn(a.lp.d3_group_tag, biased, false, lines, nt);
+    }
+    const size_t lds = form == 2 ? (size_t)decode3_shared_x_lds_bytes(d.nch_total) : 0;
+    // the table: A's members, then B's (B's member 0 travelled in B's scalars).  Entries past a.members are read by no block of A's
+    // present grid, so a failed step leaves A exactly what it was
+    const int m0 = a.members;
+    a.tab.m[m0 - 1] = GroupMember{b.lp.d3.w, b.lp.d3.x, b.lp.d3.s, b.lp.d3.z, b.lp.d3.out};
+    for (int j = 1; j < b.members; ++j) a.tab.m[m0 + j - 1] = b.tab.m[j - 1];
+    for (int j = 0; j < b.members; ++j) a.tab.bias[m0 + j] = b.tab.bias[j];
+    void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
+                     (void*)&d.nch_total, (void*)&modes, (void*)&a.tab};
+    if (!set_node(a, fn, grid, lds, kargs)) {
+        a.mergeable = false;
+        return;
+    }
+    auto restore_a = [&] {
+        void* old[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
+                       (void*)&d.nch_total, (void*)&a.node_modes, (void*)&a.tab};
+        (void)set_node(a, a.node_fn, a.node_grid, a.node_lds, old);
+    };
+    // 2. the stream waits for A's node instead of B's
+    hipGraphNode_t na = a.node;
+    if (hipStreamUpdateCaptureDependencies(st, &na, 1, hipStreamSetCaptureDependencies) != hipSuccess) {
+        (void)hipGetLastError();
+        restore_a();
+        return;
+    }
+    // 3. B's node leaves the graph
+    if (hipGraphDestroyNode(b.node) != hipSuccess) {
+        (void)hipGetLastError();
+        hipGraphNode_t nb = b.node;
+        if (hipStreamUpdateCaptureDependencies(st, &nb, 1, hipStreamSetCaptureDependencies) != hipSuccess) (void)hipGetLastError();
+        restore_a();
+        return;
+    }
+    // 4. the open group is A, full: the next launch is declined for the member limit and finds A in front of it
+    for (int j = 0; j < b.members; ++j) a.fp[m0 + j] = b.fp[j];
+    a.members = m0 + b.members;
+    a.rounds = rounds;
+    a.same_x = same_x;
+    a.w_or = w_or;
+    a.lp.d3_nt = a.lp.d3_nt && b.lp.d3_nt;
+    a.node_fn = fn;
+    a.node_grid = grid;
+    a.node_lds = lds;
+    a.node_modes = modes;
+    a.node_form = tl_last_form = form;
+    a.node_lines = tl_last_lines = lines;
+    a.node_policy = tl_last_policy = nt ? 1 : 0;
+    tl_last_rounds = rounds;
+    a.open = true;
+    a.capturing = b.capturing;
+    b = a;
+    g_merged.fetch_add(1, std::memory_order_relaxed);
 }
 
 // Called in front of every decode3 and every rows launch that carries no profile events.  true: the call was folded into the open group's node, nothing
@@ -278,21 +441,34 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
     Group& g = tl_group;
     g.capturing = false;
     const bool rows = lp.arg_kind == 2;
-    if (capture_group_limit() < 2 || (rows ? !capture_group_rows_enabled() : (lp.d3.modes & 64u) != 0)) return false;
+    if (capture_group_limit() < 2 || (rows ? !capture_group_rows_enabled() : (lp.d3.modes & 64u) != 0)) {
+        tl_prev_valid = false;
+        return false;
+    }
     unsigned long long id = 0;
     hipGraph_t graph = nullptr;
     hipGraphNode_t dep = nullptr;
     if (!capture_state(st, &id, &graph, &dep)) {
         g.open = false;
+        tl_prev_valid = false;
         return false;
     }
     g.capturing = true;
     g_seen.fetch_add(1, std::memory_order_relaxed);
-    if (!g.open || g.cap_id != id || g.graph != graph || !dep || dep != g.node || g.members >= capture_group_limit() || !same_launch(g.lp, lp))
+    const bool follows = g.open && g.cap_id == id && g.graph == graph && dep && dep == g.node && same_launch(g.lp, lp);
+    if (!follows || g.members >= capture_group_limit()) {
+        // declined: the launch opens a group of its own (note_launch).  Declined for the member limit ALONE, behind a decode node of whole
+        // rounds that may take one more: the open group is that group's predecessor, and is kept for the merge
+        tl_prev_valid = follows && !rows && g.mergeable && g.rounds < capture_group_rounds_max() && g.members == g.rounds * capture_group_limit();
+        if (tl_prev_valid) tl_prev = g;
         return false;
+    }
     const Footprint fb = footprint(a, lp);
     for (int i = 0; i < g.members; ++i)
-        if (!independent(g.fp[i], fb)) return false;
+        if (!independent(g.fp[i], fb)) {
+            tl_prev_valid = false;  // (this launch opens a group that does not follow the open one)
+            return false;
+        }
     const bool biased = g.lp.bias != nullptr;  // (lp.bias too: same_launch() compared the kernel functions)
     if (rows) {
         // grid.y one more.  The cap on dynamic LDS first (a rows block takes 146 KiB): once per grouped function and device
@@ -303,8 +479,8 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
         }
         Rows5Args& r = g.lp.r5;
         void* kargs[] = {(void*)&r.w, (void*)&r.x, (void*)&r.s, (void*)&r.z, (void*)&r.out, (void*)&r.sw4, (void*)&r.mstride2, (void*)&r.nch_total,
-                         (void*)&r.modes, (void*)&r.M, (void*)&r.sxm2, (void*)&r.som, (void*)&g.tab};
-        if (!rewrite_node(g, GroupMember{lp.r5.w, lp.r5.x, lp.r5.s, lp.r5.z, lp.r5.out}, lp.bias, fb, fn, dim3(g.lp.grid.x, (unsigned)(g.members + 1), 1),
+                         (void*)&r.modes, (void*)&r.M, (void*)&r.sxm2, (void*)&r.som, (void*)&g.rtab};
+        if (!rewrite_node(g, g.rtab, GroupMember{lp.r5.w, lp.r5.x, lp.r5.s, lp.r5.z, lp.r5.out}, lp.bias, fb, fn, dim3(g.lp.grid.x, (unsigned)(g.members + 1), 1),
                           g.lp.lds_bytes, kargs))
             return false;
         tl_last_form = 3;
@@ -332,14 +508,19 @@ bool capture_group_try_join(const gemlite_hip_forward_args& a, const LaunchPlan&
         fn = gemv_w4_decode3_group_fn(g.lp.d3_group_tag, biased, false, lines, nt);
     }
     const size_t lds = form == 2 ? (size_t)decode3_shared_x_lds_bytes(d.nch_total) : 0;
-    if (!rewrite_node(g, GroupMember{lp.d3.w, lp.d3.x, lp.d3.s, lp.d3.z, lp.d3.out}, lp.bias, fb, fn, dim3((unsigned)geo.grid_x, (unsigned)geo.grid_y, 1), lds,
-                      kargs))
-        return false;
+    const dim3 grid((unsigned)geo.grid_x, (unsigned)geo.grid_y, 1);
+    if (!rewrite_node(g, g.tab, GroupMember{lp.d3.w, lp.d3.x, lp.d3.s, lp.d3.z, lp.d3.out}, lp.bias, fb, fn, grid, lds, kargs)) return false;
     g.same_x = same_x;
     g.w_or = w_or;
-    tl_last_form = form;
-    tl_last_lines = lines;
-    tl_last_policy = nt ? 1 : 0;
+    g.node_fn = fn;
+    g.node_grid = grid;
+    g.node_lds = lds;
+    g.node_modes = modes;
+    g.node_form = tl_last_form = form;
+    g.node_lines = tl_last_lines = lines;
+    g.node_policy = tl_last_policy = nt ? 1 : 0;
+    tl_last_rounds = 1;
+    if (g.members == capture_group_limit() && tl_prev_valid) try_merge(g, dep, st, resident, dev);
     return true;
 }
 
@@ -367,8 +548,15 @@ void capture_group_note_launch(const gemlite_hip_forward_args& a, const LaunchPl
     tl_last_form = 0;  // (a group of one: no grouped node yet)
     tl_last_lines = 0;
     tl_last_policy = -1;
-    memset(&g.tab, 0, sizeof(g.tab));
-    g.tab.bias[0] = lp.bias;
+    tl_last_rounds = 0;
+    g.rounds = 1;
+    g.mergeable = true;
+    g.node_fn = nullptr;
+    // (only the one-round part of the node table: the rest is written before a kernel indexes it)
+    memset(&g.rtab, 0, sizeof(g.rtab));
+    memset(g.tab.m, 0, sizeof(GroupMember) * (DECODE3_GMAX - 1));
+    memset(g.tab.bias, 0, sizeof(g.tab.bias[0]) * DECODE3_GMAX);
+    g.tab.bias[0] = g.rtab.bias[0] = lp.bias;
     g.fp[0] = footprint(a, lp);
     g.members = 1;
     g.open = true;

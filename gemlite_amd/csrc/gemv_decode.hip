@@ -24,7 +24,7 @@
 //   kernel                                               argument behind the 14 dwords    launched by
 //   gemv_w4_decode3_kernel<Tag, NT, BIASED>              unsigned* counters (timeline) |  the planner: dependent chains, eager and profiled
 //                                                        Decode3BiasTail (BIASED)         launches, a group of one.  Wave w runs virtual wave w
-//   gemv_w4_decode3_group_kernel<Tag, BIASED, SX, HL,    GroupTable<BIASED> by value      capture_group.hip, by rewriting a capture's node
+//   gemv_w4_decode3_group_kernel<Tag, BIASED, SX, HL,    DecodeNodeTable<BIASED> by value capture_group.hip, by rewriting a capture's node
 //                                NT>
 //   gemv_w4_decode3_experts_kernel<Tag, BIASED, IDS64>   ExpertsTail by value             gemlite_hip_forward_experts (api.hip): a block per
 //                                                                                         (tile, slot), the expert id read on the GPU, then
@@ -54,6 +54,10 @@
 // its tiles, all at once: each (layer, tile) slot gets its share of the 16 waves and its own 4 KB of LDS, and the block has ONE barrier (the
 // comment at the kernel has the details).  Member count, TB and Y come in `modes`.  Layer 0's pointers are the preloaded scalars; the
 // others come out of the by-value table with scalar loads, once per wave.  No timeline probe in a group.
+// A NODE holds R >= 1 such groups as ROUNDS (capture_group.hip merges full neighbouring groups; gl_common.h: decode3_round_member): grid
+// (N / 16 / TB, Y * R), block row yy is row yy % Y of round yy / Y and works on the members m * round + y + li * Y of the table, m the
+// member count of ONE round from `modes`.  R is not in the kernel and gridDim.y is not read; blocks go out x-fastest and one block is
+// resident per CU, so a CU takes its block of the next round as soon as its own block leaves.
 #include <type_traits>
 
 #include "gl_common.h"
@@ -74,7 +78,7 @@ __device__ __forceinline__ float dpp_movf(float v) {
 
 // modes: bits 0..3 W_group_mode | 4 zero_is_scalar | 5 pair the half-line tiles on one XCD | 6 timeline probe | 8..15 log2(group)
 //        grouped launches only (capture_group.hip; gl_common.h: decode3_group_modes): 16..20 members | 21..22 log2(tiles per block) |
-//        23 span placement of the tile groups | 24..31 grid.y
+//        23 span placement of the tile groups | 24..31 grid.y of ONE round
 constexpr uint32_t M_ZSCALAR = 16u, M_PAIR = 32u, M_PROBE = 64u;
 constexpr int R = 2, NW = 16, CHUNK = 32, TC = 16;
 constexpr int RED = NW * 4 * TC;  // floats of one partial-row region: [NW * 4 DPP rows][16 columns], 4 KiB
@@ -403,7 +407,7 @@ template <typename Tag, bool BIASED, bool SX, int HL, bool NT>
 __global__ __launch_bounds__(1024, DECODE3_GROUP_WAVES_PER_SIMD)
 void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp, const char* zp, uint16_t* out,
                                   uint32_t sw4, uint32_t mstride2, int nch_total, uint32_t modes,
-                                  const GroupTable<BIASED> tab) {
+                                  const DecodeNodeTable<BIASED> tab) {
     using namespace dec3;
     using TR = F16Traits<Tag>;
     constexpr int hl = HL, H = 1 << hl;
@@ -412,7 +416,10 @@ void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 3;
     // the block's tile group and this wave's slot = (block-local layer, tile of the group); gl_common.h has the geometry
-    const int members = (int)((modes >> 16) & DECODE3_M_MEMBERS), Y = (int)(modes >> 24), y = (int)blockIdx.y;
+    // (rounds, gl_common.h: block row yy of the grid is row y of round yy / Y — one scalar divide in front of the first request; a node of
+    // one round has yy < Y.  `members` are those of ONE round)
+    const int members = (int)((modes >> 16) & DECODE3_M_MEMBERS), Y = (int)(modes >> 24), yy = (int)blockIdx.y;
+    const int y = decode3_round_row(Y, yy);
     const int tbl = (int)((modes >> DECODE3_M_TB_SHIFT) & 3u);
     const int slots = ((members - y + Y - 1) / Y) << tbl;
     // lines: the block's slots / H wave-slots are what the waves share, sub-wave h of the lanes takes tile run * H + h
@@ -438,7 +445,7 @@ void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp
     const int lq = lane & ((64 >> hl) - 1), gl = lq >> 2;
     const int slot = (split.layer < 0 ? 0 : split.layer) << hl, li = slot >> tbl, v0 = split.v0, v1 = split.v1;
     // this wave's layer: the preloaded scalars (layer 0) or the by-value table, scalar loads either way, once per wave
-    const int L = y + li * Y;
+    const int L = decode3_round_member(members, Y, yy, li);
     const char *w_ = wb, *x_ = xb, *s_ = sp, *z_ = zp;
     if (L > 0) {
         const GroupMember& m = tab.m[L - 1];
@@ -605,7 +612,7 @@ void gemv_w4_decode3_group_kernel(const char* wb, const char* xb, const char* sp
     uint16_t* o_ = out;
     uint16_t braw = 0;
     if (fin) {
-        const int Lf = y + (wave >> tbl) * Y;
+        const int Lf = decode3_round_member(members, Y, yy, wave >> tbl);
         if (Lf > 0) o_ = tab.m[Lf - 1].out;
         if constexpr (BIASED) {
             if (lane < 16) braw = tab.bias[Lf][ftile * TC + lane];

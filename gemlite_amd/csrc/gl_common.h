@@ -660,6 +660,36 @@ struct GroupTable<false> {
 // (capture_group.hip keeps ONE biased table per group and hands it to either kind of kernel: an unbiased kernel's argument is its prefix)
 static_assert(offsetof(GroupTable<true>, m) == 0 && sizeof(GroupTable<false>) == offsetof(GroupTable<true>, bias), "the unbiased table is a prefix of the biased one");
 static_assert(sizeof(GroupTable<false>) == 600 && sizeof(GroupTable<true>) == 728, "kernel-argument layout of the grouped kernels");
+// ROUNDS.  A grouped DECODE node holds R >= 1 rounds of m <= DECODE3_GMAX members each, m * R <= DECODE3_NODE_MAX (capture_group.hip merges
+// full neighbouring groups of a capture into one node): grid (grid_x, Y * R), block (x, yy) is block (x, yy % Y) of round yy / Y and does
+// on the members m * round + ... of the table what block (x, y) of a one-round node does on its own.  The decode forms therefore take a
+// table of their own, DECODE3_NODE_MAX - 1 members (and DECODE3_NODE_MAX bias pointers) by value; DECODE3_GMAX keeps meaning the members
+// of one round, the slots of a block and its LDS regions.  The rows and experts kernels keep GroupTable.
+constexpr int DECODE3_NODE_MAX = 64;
+// rounds a node may hold: the hard limit of GEMLITE_HIP_CAPTURE_GROUP_ROUNDS, and the limit when nothing is set (capture_group.hip, ROUNDS)
+constexpr int DECODE3_ROUNDS_LIMIT = 4, DECODE3_ROUNDS_DEFAULT = 4;
+static_assert(DECODE3_ROUNDS_LIMIT * DECODE3_GMAX <= DECODE3_NODE_MAX, "a node of full rounds fits its table");
+template <bool BIASED>
+struct DecodeNodeTable {
+    GroupMember m[DECODE3_NODE_MAX - 1];
+    const uint16_t* bias[DECODE3_NODE_MAX];
+};
+template <>
+struct DecodeNodeTable<false> {
+    GroupMember m[DECODE3_NODE_MAX - 1];
+};
+static_assert(offsetof(DecodeNodeTable<true>, m) == 0 && sizeof(DecodeNodeTable<false>) == offsetof(DecodeNodeTable<true>, bias),
+              "the unbiased node table is a prefix of the biased one");
+// (the whole kernel-argument segment: the nine scalars in 56 bytes, the table, and the 256 bytes of hidden arguments a code object may add)
+static_assert(56 + sizeof(DecodeNodeTable<true>) + 256 <= 4096, "kernel-argument segment of the grouped decode forms");
+// The index rule, kernel and host: the member of the node's table that block row `block_y` of a node with m members per round and
+// Y block rows per round holds as its block-local layer `li`.  One round (block_y < Y): y + li * Y, what it always was.
+// (a block row is below 2^16 and Y below 2^8: the masks tell the compiler so, and the divide is the short one through the reciprocal)
+GL_HD int decode3_round(int Y, int block_y) { return (int)((unsigned)(block_y & 0xFFFF) / (unsigned)(Y & 0xFF)); }
+GL_HD int decode3_round_row(int Y, int block_y) { return (int)((unsigned)(block_y & 0xFFFF) % (unsigned)(Y & 0xFF)); }
+GL_HD int decode3_round_member(int m, int Y, int block_y, int li) {
+    return m * decode3_round(Y, block_y) + decode3_round_row(Y, block_y) + li * Y;
+}
 // LDS of a shared-x block: the 64 KiB of partial rows (DECODE3_GMAX layers x 4 KiB), then per 16-element unit of x (K / 16 = 16 per 32-row
 // chunk) 32 bytes of pair dwords, then per unit its 4-byte sum: 64 KiB + 2.25 K bytes, dynamic.  The block's 1024 threads stage the
 // units in trips of 1024.  0: the staging area does not fit beside the partial rows in the 160 KiB of a CU (K > 43520).

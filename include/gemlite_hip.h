@@ -381,7 +381,19 @@ int gemlite_hip_launch_noop(int32_t blocks, int32_t threads, void* stream);
  *                policy (the crossover lies between 286 and 572 MB of weights per step): set GEMLITE_TF_GEMV_DEFAULT_POLICY_LOADS in
  *                such a model's tuning[3]
  *   _last_policy host only: the weight-load policy of the grouped decode node the calling thread rewrote last: 0 default, 1
- *                non-temporal, -1 none */
+ *                non-temporal, -1 none
+ * ROUNDS.  When a grouped DECODE node fills up (_max members) directly behind another full one of the same capture, with nothing else on
+ * either node, and every member of the one is independent of every member of the other, the two become ONE node of two rounds: grid
+ * (grid.x, grid.y x rounds), a CU takes its block of the next round when its own block leaves, no launch boundary in between; up to
+ * _rounds_max rounds (at most 64 members per node).  A partial trailing group keeps its own node.  _stats counts as before.
+ * GEMLITE_HIP_CAPTURE_GROUP_ROUNDS=1..4 (development, read once per process) sets the round limit, 1 = no merging.  Rows groups do not merge.
+ *   _merge_stats   process-wide count of groups merged into the node in front of them
+ *   _rounds_max    rounds a decode node may hold (1 = merging is off)
+ *   _last_rounds   host only: rounds of the grouped decode node the calling thread rewrote or merged last (0: none)
+ *   _round_member  host only, DEVELOPMENT / TEST: the index rule of the kernel.  In a node of `m` members per round (1 .. 16) and `Y`
+ *                  block rows per round (1 .. m), the member of the node's table that block row `block_y` holds as its block-local layer
+ *                  `local_layer`: m x (block_y / Y) + block_y % Y + local_layer x Y.  -1 for an argument out of range (a round past
+ *                  64 members, a layer the block does not hold) */
 int gemlite_hip_capture_group_max(void);
 void gemlite_hip_capture_group_stats(uint64_t* seen, uint64_t* joined);
 int gemlite_hip_capture_group_compatible(const gemlite_hip_forward_args* a, const gemlite_hip_forward_args* b);
@@ -396,6 +408,10 @@ int gemlite_hip_capture_group_lines(int32_t tiles, int32_t members, int32_t resi
 int gemlite_hip_capture_group_last_lines(void);
 int gemlite_hip_capture_group_policy(int32_t h, int32_t default_policy_loads, uint64_t w_bases_or, uint32_t pitch_bytes, int32_t forced);
 int gemlite_hip_capture_group_last_policy(void);
+void gemlite_hip_capture_group_merge_stats(uint64_t* merged);
+int gemlite_hip_capture_group_rounds_max(void);
+int gemlite_hip_capture_group_last_rounds(void);
+int gemlite_hip_capture_group_round_member(int32_t m, int32_t Y, int32_t block_y, int32_t local_layer);
 
 /* Bias in the launch (optional extension; gemlite_hip_forward_args and every entry point above are unchanged).  The M = 1 decode kernel
  * (gemv_w4_decode3_kernel, single and grouped) and the few-row kernels (gemm_w4_rows_kernel / gemm_w2_rows_kernel) have forms that add a
