@@ -51,7 +51,7 @@ def route_guarded(ex, ids, R):
     return ExpertsRouting(buf[:need], R, n, ex.num_experts), buf, need
 
 
-def check_routing(buf, need, ids, R):
+def check_routing(buf, need, ids, R, E=E):
     """The table against the restated contract; nothing written behind the table, nor into the entries beyond the used count."""
     table = buf.cpu().numpy()
     flat = ids.reshape(-1).cpu().numpy()
@@ -118,7 +118,7 @@ def check_outputs(ex, x, ids, out, R):
 
 CASES = [(shape, gs, dtype, zeros, bias, idt, R)
          for shape, gs, dtype, zeros, bias, idt, R in itertools.product(SHAPES, (32, 64, 128, 256), (torch.float16, torch.bfloat16),
-                                                                         ("tensor", "int"), (False, True), (torch.int32, torch.int64), (16, 32, 64))
+                                                                         ("tensor", "int"), (False, True), (torch.int32, torch.int64), (16, 32, 48, 64))
          if (R <= 32 or gs > 32)            # groups of 32: 16 / 32 rows per block (the registers of the kernel)
          and gs < SHAPES[shape][1]]         # a group that spans K (256 at K = 256) is packed as CHANNEL scales, which GemLiteExperts.from_layers
                                             # has always refused (W_group_mode 1..4, channel_scale_mode 0): not an experts layer at all
