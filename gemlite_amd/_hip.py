@@ -310,6 +310,10 @@ def load():
         lib.gemlite_hip_capture_group_last_lines.argtypes = []
         lib.gemlite_hip_capture_group_policy.restype = C.c_int
         lib.gemlite_hip_capture_group_policy.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32]
+        lib.gemlite_hip_k_order_step.restype = C.c_int
+        lib.gemlite_hip_k_order_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        lib.gemlite_hip_k_order_mode.restype = C.c_int
+        lib.gemlite_hip_k_order_mode.argtypes = [C.POINTER(ForwardArgs)]
         lib.gemlite_hip_capture_group_last_policy.restype = C.c_int
         lib.gemlite_hip_capture_group_last_policy.argtypes = []
         lib.gemlite_hip_capture_group_merge_stats.restype = None
@@ -394,6 +398,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_capture_group_policy", "gemlite_hip_capture_group_last_policy",
     "gemlite_hip_capture_group_merge_stats", "gemlite_hip_capture_group_rounds_max", "gemlite_hip_capture_group_last_rounds",
     "gemlite_hip_capture_group_round_member",
+    "gemlite_hip_k_order_step", "gemlite_hip_k_order_mode",
     "gemlite_hip_forward_ex", "gemlite_hip_bias_fused", "gemlite_hip_kernel_name_ex", "gemlite_hip_capture_group_compatible_ex",
     "gemlite_hip_quantize_groups", "gemlite_hip_quantize_mx", "gemlite_hip_dequantize", "gemlite_hip_quantize_groups_hqq",
     "gemlite_hip_quantize_rows",

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "gl_common.h"
+#include "gl_async.h"
 #include "gl_coopquant.h"
 
 namespace gl {
@@ -1059,6 +1060,33 @@ int gemlite_hip_capture_group_last_policy(void) { return capture_group_last_poli
 int gemlite_hip_capture_group_policy(int32_t h, int32_t default_policy_loads, uint64_t w_bases_or, uint32_t pitch_bytes, int32_t forced) {
     if ((h != 1 && h != 2 && h != 4) || forced < -2 || forced > 1) return -1;
     return decode3_group_nt(h, default_policy_loads == 0, w_bases_or, pitch_bytes, forced == -2 ? capture_group_policy_forced() : forced) ? 1 : 0;
+}
+
+// The K order of the unsplit 8-bit tiles, host only (nothing is launched, no device is touched).  _step evaluates the struct the kernels compile
+// (KOrder, gl_async.h: its host spelling); _mode plans like gemlite_hip_kernel_name and reads the order bits the planned kernel will be launched with.
+int gemlite_hip_k_order_step(int32_t step, int32_t mt, int32_t mtiles, int32_t nsteps, int32_t mode) {
+    if (nsteps < 1 || step < 0 || step >= nsteps || mtiles < 1 || mt < 0 || mt >= mtiles || mode < -1 || mode > 15) return -1;
+    async::KOrder k;
+    k.init(mt, mtiles, nsteps, mode < 0 ? 0 : (K_ORDER_ON | (mode << K_ORDER_GROUP_SHIFT)));
+    return k.at(step);
+}
+
+int gemlite_hip_k_order_mode(const gemlite_hip_forward_args* args) {
+    if (validate(args) != GEMLITE_OK) return -1;
+    Resolved r;
+    resolve(*args, r);
+    if (r.status != GEMLITE_OK || !r.lp.name) return -1;
+    const char* n = r.lp.name;
+    const size_t len = strlen(n);
+    const bool narrow = len > 7 && strcmp(n + len - 7, "<64x64>") == 0;
+    if (r.kind == K_A8_MMA && (strncmp(n, "gemm_a8w8_sq_kernel<", 20) == 0 || (strncmp(n, "gemm_mx_a", 9) == 0 && strstr(n, "_sq_kernel<")))) {
+        const int bm = strstr(n, "<128x128>") ? 128 : 64;
+        if (!(r.gp.flags & K_ORDER_ON) || (args->M + bm - 1) / bm < 2) return -1;
+        return (r.gp.flags >> K_ORDER_GROUP_SHIFT) & 15;
+    }
+    // the narrow 64 x 64 tiles of gemm_wn_mma_kernel: their own whole-K rotation, the group field is ignored
+    if (r.kind == K_TILED_WN && narrow && (r.wn.flags & K_ORDER_ON) && (args->M + 63) / 64 >= 2) return 0;
+    return -1;
 }
 
 int gemlite_hip_capture_group_lines(int32_t tiles, int32_t members, int32_t resident, int32_t tb, int32_t h_want) {

@@ -69,26 +69,35 @@ __device__ __forceinline__ void req_lds4(srd_t rs, uint32_t lds_addr, uint32_t v
 // to survive mtiles - 1 groups in L2 instead of a whole rotation.  A tail of fewer than mtiles groups keeps the plain order.
 // Everything per step is SCALAR arithmetic (the quotient by mtiles through a multiply-high with a constant set up once): the step offset feeds the soffset operand
 // of inline-asm requests, and an SGPR written by v_readfirstlane right in front of them would need wait states nothing inserts.
+// The struct also compiles for the HOST (gemlite_hip_k_order_step, api.hip: the tests evaluate the rule the kernels compile, not a restatement of it): the two
+// device builtins have host spellings below, chosen by __HIP_DEVICE_COMPILE__ — the device pass sees the same tokens as before.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GL_KORDER_UNIFORM(v) __builtin_amdgcn_readfirstlane(v)
+#define GL_KORDER_UMULHI(a, b) __umulhi(a, b)
+#else
+#define GL_KORDER_UNIFORM(v) (v)
+#define GL_KORDER_UMULHI(a, b) ((uint32_t)(((uint64_t)(a) * (uint64_t)(b)) >> 32))
+#endif
 struct KOrder {
     int mode;        // 0 plain, 1 whole-K rotation, 2 grouped
     int rot, nsteps; // whole rotation
     int gsh, P, mt, ngroups;
     uint32_t magic;  // ceil(2^32 / P)
-    __device__ __forceinline__ void init(int mt_, int mtiles, int nsteps_, int flags) {
+    __host__ __device__ __forceinline__ void init(int mt_, int mtiles, int nsteps_, int flags) {
         mode = 0; rot = 0; nsteps = nsteps_; gsh = 0; P = mtiles; mt = mt_; ngroups = 0; magic = 0u;
         if (!(flags & K_ORDER_ON) || mtiles < 2) return;
         const int gm = (flags >> K_ORDER_GROUP_SHIFT) & 15;
         if (gm == 0) {
             mode = 1;
-            rot = __builtin_amdgcn_readfirstlane((mt_ * nsteps_) / mtiles);
+            rot = GL_KORDER_UNIFORM((mt_ * nsteps_) / mtiles);
         } else {
             mode = 2;
             gsh = gm - 1;
             ngroups = nsteps_ >> gsh;
-            magic = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(((1ull << 32) + (uint64_t)mtiles - 1ull) / (uint64_t)mtiles));
+            magic = (uint32_t)GL_KORDER_UNIFORM((int)(uint32_t)(((1ull << 32) + (uint64_t)mtiles - 1ull) / (uint64_t)mtiles));
         }
     }
-    __device__ __forceinline__ int at(int step) const {
+    __host__ __device__ __forceinline__ int at(int step) const {
         if (mode == 0) return step;
         if (mode == 1) {
             const int k = step + rot;
@@ -96,7 +105,7 @@ struct KOrder {
         }
         int g = step >> gsh;
         const int i = step & ((1 << gsh) - 1);
-        const int base = (int)__umulhi((uint32_t)g, magic) * P;  // (g / P) * P: exact while g P < 2^32
+        const int base = (int)GL_KORDER_UMULHI((uint32_t)g, magic) * P;  // (g / P) * P: exact while g P < 2^32
         if (base + P <= ngroups) {
             int r = g - base + mt;
             if (r >= P) r -= P;
@@ -105,6 +114,8 @@ struct KOrder {
         return (g << gsh) + i;
     }
 };
+#undef GL_KORDER_UNIFORM
+#undef GL_KORDER_UMULHI
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void tie(uint32_t& v) { asm volatile("" : "+v"(v)); }

@@ -413,6 +413,23 @@ int gemlite_hip_capture_group_rounds_max(void);
 int gemlite_hip_capture_group_last_rounds(void);
 int gemlite_hip_capture_group_round_member(int32_t m, int32_t Y, int32_t block_y, int32_t local_layer);
 
+/* K order of the unsplit 8-bit tiles (host only, DEVELOPMENT / TEST: nothing is launched, no device is touched).  The row tiles of a weight
+ * column tile of gemm_a8w8_sq_kernel<64x64> / <128x128> and gemm_mx_*_sq_kernel<64x64> may walk their K steps in different orders (an L2
+ * matter; every order visits every step once).  `mode`: -1 = plain order, 0 = whole-K rotation (row tile mt starts at step
+ * mt nsteps / mtiles), 1 .. 15 = the group field of GEMLITE_TF_K_ORDER_GROUP_MASK (groups of 2^(mode - 1) steps, rotated by mt inside every
+ * full run of mtiles groups; a tail of fewer than mtiles groups, a partial last group and a group larger than nsteps are plain).
+ *   _step   the step of K that row tile `mt` of `mtiles` takes as its `step`-th of `nsteps`: evaluates the struct the kernels compile.
+ *           -1 for an argument out of range (step outside [0, nsteps), mt outside [0, mtiles), mode outside [-1, 15])
+ *   _mode   the mode the kernel planned for `args` is launched with; -1 when that kernel has no K order or walks K plain (one row tile,
+ *           GEMLITE_TF_NO_K_ROTATION, a split K, any other kernel, a request without a kernel).  The narrow 64 x 64 tiles of the weight-only
+ *           8-bit layers (gemm_a16w8_kernel<64x64>, gemm_a16w8_mxfp_kernel<64x64>) have the whole rotation only: they IGNORE the group
+ *           field, so 0 or -1 is reported for them whatever GEMLITE_TF_K_ORDER_GROUP_MASK holds.
+ * A forced group (GEMLITE_TF_K_ORDER_GROUP_MASK != 0) turns the order on for the three sq kernels wherever they have two or more row tiles —
+ * also where the column tiles are NOT a multiple of 8 and the kernel maps its blocks plainly (row tiles fastest) instead of keeping a column
+ * tile's row tiles on one XCD: the order is then of no use to the L2, and the result is the same as ever. */
+int gemlite_hip_k_order_step(int32_t step, int32_t mt, int32_t mtiles, int32_t nsteps, int32_t mode);
+int gemlite_hip_k_order_mode(const gemlite_hip_forward_args* args);
+
 /* Bias in the launch (optional extension; gemlite_hip_forward_args and every entry point above are unchanged).  The M = 1 decode kernel
  * (gemv_w4_decode3_kernel, single and grouped) and the few-row kernels (gemm_w4_rows_kernel / gemm_w2_rows_kernel) have forms that add a
  * bias[N] in their epilogue:   out[m, n] = round16( float(round16(acc[m, n])) + float(bias[n]) )   — both roundings of "matmul, then

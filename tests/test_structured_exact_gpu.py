@@ -219,7 +219,9 @@ A8_FAMILIES = [("streaming", 1, (1, 0, 0, 0)), ("rows_m1", 1, (4, 0, 0, 524288))
                ("rows_lds64", 64, (4, 0, 0, 0)),
                ("mfma_r1", 64, (2, 0, 0, 0)), ("mma32", 29, (0, 1, 1, 0)), ("mma64_sk3", 64, (0, 3, 2, 0)),
                ("mma128", 128, (0, 1, 4, 0)), ("mma128_direct_b", 128, (0, 2, 4, 64)), ("mma256_sk5", 256, (0, 5, 8, 0)),
-               ("auto_m1", 1, (0, 0, 0, 0)), ("auto_m100", 100, (0, 0, 0, 0)), ("auto_m256", 256, (0, 0, 0, 0))]
+               ("auto_m1", 1, (0, 0, 0, 0)), ("auto_m100", 100, (0, 0, 0, 0)), ("auto_m256", 256, (0, 0, 0, 0)),
+               # the unsplit tiles, forced: four ragged row tiles of 64 / two of 128 (tests/test_k_order_gpu.py walks their K orders)
+               ("sq64_m200", 200, (5, 0, 0, 0)), ("sq128_m200", 200, (10, 0, 0, 0))]
 
 
 @pytest.mark.parametrize("tdt", TDTS, ids=IDS)
@@ -242,6 +244,7 @@ def test_a8w8_families_one_hot_times_position_coded_is_exact(kind, tdt):
     assert {"a8w8_rows_kernel<16x16>", "a8w8_rows_kernel<32x16>", "a8w8_rows_kernel<64x16>"} <= set(ran), ran
     assert {"a8w8_rows_lds_kernel<16x16>", "a8w8_rows_lds_kernel<32x16>", "a8w8_rows_lds_kernel<48x16>", "a8w8_rows_lds_kernel<64x16>"} <= set(ran), ran
     assert any("gemm_a8w8_lds" in r for r in ran) and any("mma" in r for r in ran), ran
+    assert {"gemm_a8w8_sq_kernel<64x64>", "gemm_a8w8_sq_kernel<128x128>"} <= set(ran), ran
 
 
 @pytest.mark.parametrize("tdt", TDTS, ids=IDS)
