@@ -370,7 +370,7 @@ def _hip_matmul(x: Tensor, W_q: Tensor, scales: Tensor, zeros: Tensor, scales_x:
 
 # ---- in-launch activation quantisation: ONE source of truth ------------------------------------------------------------
 # Whether a kernel takes the UNQUANTISED 16-bit rows of a dynamically quantised layer (per-token int8 / fp8, or block-scaled MXFP8 /
-# MXFP4 / NVFP4) is decided in ONE place — resolve() in csrc/api.hip — and asked through gemlite_hip_query, which plans and never
+# MXFP4 / NVFP4) is decided in ONE place — resolve() in csrc/plan_forward.hip — and asked through gemlite_hip_query, which plans and never
 # launches, on exactly the arguments the launch would carry (_call_args).  Rounds 3-4 kept three hand-written copies of the library's
 # preconditions here (alignment, K % 16, K <= 65536, packed / unpacked, one row / several) plus a memo of refusals under a key that
 # left out what a refusal depends on.  The answer is cached per everything it depends on: the layer (meta ints, shapes,
@@ -402,7 +402,7 @@ def _library_quantises_inside(x2: Tensor, W_q: Tensor, scales: Tensor, zeros: Te
     return ans
 
 
-# ---- bias inside the launch: the same scheme.  resolve() + apply_bias() in csrc/api.hip decide, gemlite_hip_bias_fused asks them on the
+# ---- bias inside the launch: the same scheme.  resolve() + apply_bias() in csrc/plan_forward.hip decide, gemlite_hip_bias_fused asks them on the
 # arguments the launch would carry; the answer is cached per layer / shape / alignment / bias type / tuning epoch.
 _FUSED_BIAS_ANSWERS: dict = {}
 

@@ -77,14 +77,9 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
-
-// gemv_decode.hip: the grouped forms (h: tiles per wave; nt: non-temporal weight requests, H >= 2 only).  A group holds biased launches
-// or unbiased ones, never both, and launches of one load policy: their kernel functions differ, so same_launch() keeps them apart
-const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h, bool nt);
-int ensure_lds(const void* fn, size_t lds, int dev);            // api.hip
 
 namespace {
 

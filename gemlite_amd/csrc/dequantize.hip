@@ -26,6 +26,7 @@
 //   unaligned out.  Correct and slow.
 // Lanes beyond N or K load nothing and store nothing (K % 8 == 0 in the two tiled kernels: a piece of 8 k is inside K or outside).
 #include "gl_common.h"
+#include "gl_host.h"
 
 #pragma clang fp contract(off)
 

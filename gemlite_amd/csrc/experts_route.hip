@@ -7,6 +7,7 @@
 // E.  Entries beyond the used count are not written.  Limits: E <= ROUTE_MAX_EXPERTS (the three LDS arrays), n_slots <= 65535 — at most
 // 64 slots per thread and pass; the launch costs a few microseconds and is off the weight stream.
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 

@@ -17,13 +17,13 @@
 #include "gl_async.h"
 #include "gl_coopquant.h"
 #include "gl_w8cvt.h"
+#include "gl_host.h"
 
 #include <type_traits>
 
 namespace gl {
 
-bool plan_w8_rows_lds(const gemlite_hip_forward_args& a, LaunchPlan& lp, int mt, bool two);  // gemm_w8_rows.hip
-// row tiles per block of that kernel and whether the two-blocks-per-CU form applies: layers with more 16-column blocks than CUs, up to 32 rows
+// row tiles per block of w8_rows_lds_kernel (gemm_w8_rows.hip) and whether the two-blocks-per-CU form applies: layers with more 16-column blocks than CUs, up to 32 rows
 static inline int w8_lds_mt(int64_t M) { return M <= 16 ? 1 : (M <= 32 ? 2 : (M <= 48 ? 3 : 4)); }
 static inline bool w8_lds_two(const gemlite_hip_forward_args& a) { return a.N / 16 > resident_block_limit() && a.M <= 32; }
 
@@ -995,7 +995,7 @@ __global__ __launch_bounds__(512, 2) void gemm_a8w8_sq128_kernel(const GenericPa
     }
 }
 
-// tuning[0] = 10 forces it (tuning[2]: stage geometry); automatic: a8w8_sq128_pays() in api.hip
+// tuning[0] = 10 forces it (tuning[2]: stage geometry); automatic: a8w8_sq128_pays() in plan_forward.hip
 bool plan_gemm_a8w8_sq128(const gemlite_hip_forward_args& a, GenericParams& g, LaunchPlan& lp) {
     if (a.elements_per_sample != 1 || a.W_group_mode != 0 || a.M < 2) return false;
     if (a.w_dtype != a.input_dtype) return false;
@@ -1084,7 +1084,7 @@ bool plan_gemm_a8w8_sq(const gemlite_hip_forward_args& a, GenericParams& g, Laun
     const int oal = a.output_dtype == GEMLITE_DT_FP32 ? 16 : 8;  // 4 outputs per store
     if (((uintptr_t)a.out % oal) != 0 || (a.stride_om * (oal / 4)) % oal != 0) return false;
     const int64_t tiles = (int64_t)(a.N / 64) * ((a.M + 63) / 64);
-    // tuning[0] = 5 forces this kernel.  Automatic: see the caller (api.hip) — 65 .. 256 rows whose 64 x 64 tiles fill the chip once
+    // tuning[0] = 5 forces this kernel.  Automatic: see the caller (plan_forward.hip) — 65 .. 256 rows whose 64 x 64 tiles fill the chip once
     typedef void (*fn_t)(const GenericParams);
     // tuning[2] = 2 / 3: two (64 KB of LDS: two blocks per CU) / three stages (development A/B); default four
     // (one round of tiles: 4 stages in flight per block; two rounds: 2 stages = 64 KB of LDS, two co-resident blocks per CU cover each
@@ -1578,7 +1578,7 @@ __global__ __launch_bounds__(512) void a16w8_rows_kernel(const GenericParams p) 
     }
 }
 
-// Where w8_rows_lds_kernel runs AHEAD of the 8-bit weight-only tile kernel (api.hip asks before its M N K > 850 M rule; measured `layer(x)`,
+// Where w8_rows_lds_kernel runs AHEAD of the 8-bit weight-only tile kernel (plan_forward.hip asks before its M N K > 850 M rule; measured `layer(x)`,
 // profiles/r06/probe_w8_rows_lds_*.log, A16W8_INT8 / _FP8):
 //   * one resident round of 16-column blocks (N <= 4096 on 256 CUs), 4 .. 64 rows, while the blocks' re-reads of x stay below 256 MiB:
 //     4096^2 M = 64 (134 MB) 17.0 (tile) -> 12.7 us; 4096 x 14336 M = 16 / 32 (117 / 235 MB) 26.0 / 26.8 -> 20.2 / 25.3, M = 64 (470 MB) 29.6 vs 34.3;

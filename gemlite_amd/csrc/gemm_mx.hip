@@ -26,6 +26,7 @@
 
 #include "gl_common.h"
 #include "gl_async.h"
+#include "gl_host.h"
 
 namespace gl {
 
@@ -1578,8 +1579,6 @@ __global__ __launch_bounds__(512, (NST <= 2 ? 2 : 1)) void gemm_mx_sq_kernel(con
 }
 
 // 65 .. ~256 rows whose 64 x 64 tiles fill the chip about once (the caller's rule), fp8 x fp8 / fp4 x fp4 / fp8 x fp4; tuning[0] = 6 forces it
-int k_order_flags(const gemlite_hip_forward_args& a, int64_t tile_bytes);  // gemm_a8w8.hip
-
 bool plan_gemm_mx_sq(const gemlite_hip_forward_args& a, GenericParams& g, LaunchPlan& lp) {
     if (g.mx_scale_e4m3 || g.group_size != 32 || a.M < 1) return false;
     const bool f8 = g.mx_x == MX_FP8 && g.mx_w == MX_FP8, f4 = g.mx_x == MX_FP4 && g.mx_w == MX_FP4;

@@ -24,6 +24,7 @@
 #include "gl_common.h"
 #include "gl_async.h"
 #include "gl_w8cvt.h"
+#include "gl_host.h"
 
 namespace gl {
 

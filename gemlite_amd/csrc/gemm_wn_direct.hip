@@ -19,6 +19,7 @@
 // The bytes in flight per wave are kept constant (two pieces of 16 dwords per lane) by walking 16 / V k-steps
 // per piece.
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 

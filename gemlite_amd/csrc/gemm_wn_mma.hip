@@ -1,18 +1,9 @@
 // gemm_wn_mma.hip — host-side planning of the 8-wave MFMA tile kernel (kernel: gemm_wn_mma_kernel.inc, compiled per 16-bit type in
 // gemm_wn_mma_f16.hip / gemm_wn_mma_bf16.hip).
 #include "gemm_wn_mma_kernel.inc"
+#include "gl_host.h"
 
 namespace gl {
-
-bool k_rotation_pays(const gemlite_hip_forward_args& a, int64_t tile_bytes);  // gemm_a8w8.hip
-
-
-const void* mma_lookup_f16(int kind, int nbits, int mi, int xdt);
-const void* mma_lookup_bf16(int kind, int nbits, int mi, int xdt);
-const void* mma_lookup_pw_f16_b8(int kind, int nbits, int mi);
-const void* mma_lookup_pw_f16_b16(int kind, int nbits, int mi);
-const void* mma_lookup_pw_bf16_b8(int kind, int nbits, int mi);
-const void* mma_lookup_pw_bf16_b16(int kind, int nbits, int mi);
 
 // 8- / 16-bit packed words (w_pack_bits 8 / 16, WBY = 1 / 2 in gemm_wn_mma_kernel.inc): the register-path forms (kind 0 / 1 / 4 / 6 variant 0)
 static const void* mma_lookup_pw(bool f16, int pack_bits, int kind, int nbits, int mi) {
@@ -260,7 +251,7 @@ bool plan_gemm_wn_mma(const gemlite_hip_forward_args& a, WnParams& p, LaunchPlan
         // Groups of 32 (round 6): 32-row tiles with TWO (scale, zero) pairs per column and 64-k sub-block (template parameter NGS = 2).
         // What reaches this: 1- and 8-bit packed words and fp8 activations x 4- / 2-bit words at M >= 2 (4- / 2-bit words under 16-bit activations
         // have the rows kernel in front) — shapes that ran on the coverage kernel until round 5 (4096^2 M = 64: ~3.8 ms).
-        if (p.group_size % 32 != 0 || a.K % 256 != 0 || a.N % mma::BN != 0 || xdt == GEMLITE_DT_INT8) return false;  // (odd multiples of 32 above 32: gs_magic, api.hip)
+        if (p.group_size % 32 != 0 || a.K % 256 != 0 || a.N % mma::BN != 0 || xdt == GEMLITE_DT_INT8) return false;  // (odd multiples of 32 above 32: gs_magic, plan_forward.hip)
         if (pw) return false;  // (no 8- / 16-bit word form of these tiles: the coverage kernel)
         if (a.tuning[0] != 0 || a.tuning[2] != 0) return false;
         const int rows = (int)(a.K / e), units = (int)(a.K / 256);

@@ -33,6 +33,7 @@
 // All memory requests are inline asm retired by hand-counted waits (gl_async.h has the reasoning; scripts/isa_asmloads.py audits the
 // generated code).  Scalar kernel arguments, the first 14 dwords preloaded into SGPRs (-amdgpu-kernarg-preload-count, see gemv_decode.hip).
 #include "gl_rows5.h"
+#include "gl_host.h"
 
 namespace gl {
 
@@ -57,8 +58,6 @@ namespace gl {
 // ---------------------------------------------------------------------------------------------------------------------
 // host-side planning.  tuning[0] = 9 forces this kernel (any M), GEMLITE_TF_NO_ROWS_KERNEL = never (the round-4 choice, A/B runs)
 // ---------------------------------------------------------------------------------------------------------------------
-const void* gemm_wn_rows_group_fn(int tag, int mt, int spg, int nt, int bits, bool biased);  // gemm_wn_rows_group.hip: the grouped forms
-
 typedef void (*rows5_fn)(const char*, const char*, const char*, const char*, uint16_t*, uint32_t, uint32_t, int, uint32_t, int, uint32_t, uint32_t);
 
 template <typename Tag, int MT>

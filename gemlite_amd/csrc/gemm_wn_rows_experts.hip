@@ -9,6 +9,7 @@
 //
 // A translation unit of its own so that the build stays parallel.
 #include "gl_rows5.h"
+#include "gl_host.h"
 
 namespace gl {
 

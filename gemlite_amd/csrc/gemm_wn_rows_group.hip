@@ -9,6 +9,7 @@
 //
 // A translation unit of its own so that the build stays parallel: one grouped form per form rows5_pick / rows5_bias_pick can return.
 #include "gl_rows5.h"
+#include "gl_host.h"
 
 namespace gl {
 

@@ -22,6 +22,7 @@
 // their metadata for the next piece are requested before the current piece is consumed; the 4 waves' partial
 // sums are combined in LDS and K slices with the write-through slab + ticket protocol (gl_common.h).
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 

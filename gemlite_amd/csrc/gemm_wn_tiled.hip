@@ -14,6 +14,7 @@
 //   * K is optionally split over gridDim.y (128-column tiles alone rarely fill 256 CUs at M = 256); slices are
 //     combined with the write-through slab + ticket protocol (gl_common.h).
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 

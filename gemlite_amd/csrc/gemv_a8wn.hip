@@ -14,6 +14,7 @@
 //   activations of that packed row (8 or 16 bytes per batch row) and the group's (scale, zero) come from L2 (shared by
 //   all blocks).  Partial sums: 4 xor-shuffles inside the wave, then 16 waves through LDS in fixed order (deterministic).
 #include "gl_common.h"
+#include "gl_host.h"
 
 #include <type_traits>
 

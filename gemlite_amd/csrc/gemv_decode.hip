@@ -61,6 +61,7 @@
 #include <type_traits>
 
 #include "gl_common.h"
+#include "gl_host.h"
 #include "gl_async.h"  // gvw: counted asm requests, ring2_run (the grouped kernel)
 
 namespace gl {

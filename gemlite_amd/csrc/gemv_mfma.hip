@@ -20,6 +20,7 @@
 //     requests in flight (all of its K range at 4096), non-temporal loads.
 // Numerics: fp32 accumulation in the matrix core, raw codes are exact, scale / zero in fp32 per group.
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 

@@ -27,15 +27,13 @@
 //     fixed slice order (run-to-run deterministic), applies the epilogue and stores.
 #include "gl_common.h"
 #include "gl_async.h"  // gvw: the counted asm requests and ring2_run (they lived here until the grouped decode kernel needed them too)
+#include "gl_host.h"
 
 #ifndef GL_GEMV_NT
 #define GL_GEMV_NT 1  // -DGL_GEMV_NT=0: default-policy weight loads (A/B builds)
 #endif
 
 namespace gl {
-
-const void* gemv_w4_decode3_fn(int tag, bool nt);  // gemv_decode.hip
-const void* gemv_w4_decode3_bias_fn(int tag, bool nt);
 
 // Unpack geometry.  One AND turns packed bits into two 16-bit floats q * 2^(NBITS*i) (i = position of the
 // element inside a WINDOW of consecutive bit fields that still fits the mantissa); the matching x pair is stored

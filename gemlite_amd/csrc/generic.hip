@@ -11,6 +11,7 @@
 // accumulation.  One deliberate fidelity point: for fp8 activations the reference casts the dequantised
 // weight to the input dtype before the dot (`b.to(input_dtype)`, gemm_kernels.py:384) — so do we.
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) void kmajor_matmul_kernel(const GenericParams 
                     for (int b = 0; b < 4; ++b) accf[i] = __builtin_fmaf(xf[b], wf[b], accf[i]);
                 }
             }
-            // (fp8 with MB = 4 is not planned: api.hip sends fp8 x fp8 at M > 1 to the MFMA kernels, manual GEMV types at M > 1 to
+            // (fp8 with MB = 4 is not planned: plan_forward.hip sends fp8 x fp8 at M > 1 to the MFMA kernels, manual GEMV types at M > 1 to
             //  the coverage kernel.  Round 2 carried a software-conversion fallback here because the hardware-converter form of this
             //  instantiation faulted on the MI355X for a reason that was never found; the variant is gone instead of parked.)
         }

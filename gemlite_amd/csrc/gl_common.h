@@ -863,7 +863,7 @@ struct LaunchPlan {
     int arg_kind;         // 0: the kernel takes its parameter struct by value | 1: the scalar arguments of `d3` | 2: those of `r5`
     Decode3Args d3;
     Rows5Args r5;
-    // the form of `bias_of` that adds a 16-bit bias[N] of the output's type in its epilogue (decode3 and rows kernels only; api.hip swaps
+    // the form of `bias_of` that adds a 16-bit bias[N] of the output's type in its epilogue (decode3 and rows kernels only; apply_bias, plan_forward.hip, swaps
     // it in when the caller's gemlite_hip_forward_ext qualifies and `fn` is still `bias_of`), and the bias pointer once it has
     const void* fn_bias = nullptr;
     const void* bias_of = nullptr;

@@ -23,6 +23,7 @@
 //             again per sum (L2 hits while 64 rows x span fit); the fp32 terms of a sum are added in fp64 here.
 // The order of every sum is fixed by the lane layout alone: 8 values per lane in k order (per 512-k chunk in the wave form), then the butterfly.
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 

@@ -19,6 +19,7 @@
 // [N * K/g, 1] (the quantiser's return) are the same code.  K % 32 == 0, so a piece of 8 k, and a whole block with it, is inside K or
 // outside: lanes beyond N or K only ever shuffle with each other and store nothing.
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 

@@ -20,6 +20,7 @@
 // A piece leaves as one 8-byte store.  A `w` / row pitch that is not 16-byte aligned, a `q_out` / ld_q that is not 8-byte aligned and the
 // last piece of a K that is no multiple of 8 take element loads / byte stores, each guarded by k < K: nothing outside the windows is touched.
 #include "gl_common.h"
+#include "gl_host.h"
 
 namespace gl {
 

@@ -1,6 +1,6 @@
 """Round 5: the unsplit 128 x 128 A8W8 tile kernel (tuning[0] = 10) against the round-3 / round-4 choices (tuning[0] = 6: both operands
 through LDS with K slices, tuning[0] = 5: unsplit 64 x 64 tiles), graph-replayed time per launch over rotating layers, outputs compared
-with the first candidate.  The planner's rule (a8w8_sq128_pays in api.hip) comes from this log.
+with the first candidate.  The planner's rule (a8w8_sq128_pays in plan_forward.hip) comes from this log.
     python scripts/probe_a8w8_sq128.py [workload ...]"""
 import json, os, sys
 import numpy as np

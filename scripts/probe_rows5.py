@@ -1,6 +1,6 @@
 """Round 5: the decode-shaped A16W4 rows kernel (gemm_wn_rows.hip, tuning[0] = 9) against the round-4 choice (tuning[3] & 65536) on LLM layer
 shapes x M = 2 .. 64 — graph-replayed us per `layer(x)` launch over HBM-cold rotating layers (the bench's clock).  The planner's budget in
-api.hip (rows5_min_m / rows5_budget_bytes) comes from this log.
+plan_forward.hip (rows5_min_m / rows5_budget_bytes) comes from this log.
     python scripts/probe_rows5.py [M ...]        GL_SHAPES="4096x4096,8192x8192" GL_DT=bf16 GL_GS=64"""
 import json, os, sys, time
 import torch

@@ -1028,7 +1028,7 @@ def test_w8_rows_lds_layout():
 
 
 def test_group_index_by_multiply_high():
-    """gs_magic (api.hip, round 6): the tile kernel finds the metadata row of a 32-k slice of a group size that is a multiple of 32 and not a power
+    """gs_magic (plan_forward.hip, round 6): the tile kernel finds the metadata row of a 32-k slice of a group size that is a multiple of 32 and not a power
     of two as mulhi(k / 32, ceil(2^32 / (group / 32))).  Exact for every slice of every (K, group) pair the planner admits (K * group < 2^40)."""
     rng = np.random.default_rng(9)
     for gs in [96, 160, 192, 224, 288, 320, 384, 480, 768, 1056, 3 * 4096, 5 * 8192, 96 * 341]:
