@@ -13,38 +13,12 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gemlite_amd import _hip  # noqa: E402
 from tests.test_host_cpu import _args  # noqa: E402
+from tests.kernel_forms import _a8, _mx  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "planner_tile_families.json")
 SHAPES = [(1024, 4096), (1536, 8960), (2048, 8192), (2560, 9728), (3072, 8192), (4096, 1024), (4096, 4096), (4096, 11008), (4096, 14336), (5120, 5120), (5120, 13824), (6144, 4096),
           (8192, 2048), (8192, 3072), (8192, 8192), (8960, 1536), (11008, 4096), (12288, 4096), (13824, 5120), (14336, 4096)]
 MS = (128, 256, 384, 512)
-
-
-def _mx(in_dt, nbits, M, c_mode, N, K, group=32):
-    """A block-scaled request in the K-contiguous layout of pack() (input types: 14 / 15 = fp16 / bf16 over MX weights, 16 = MXFP8, 17 = MXFP4, 18 = NVFP4)."""
-    a = _hip.ForwardArgs()
-    a.struct_size = C.sizeof(_hip.ForwardArgs)
-    a.matmul_type = -1
-    a.x = a.w_q = a.scales = a.out = a.scales_x = 0x1000
-    a.M, a.N, a.K = M, N, K
-    a.W_nbits, a.group_size, a.unpack_mask = nbits, group, 2 ** nbits - 1
-    a.elements_per_sample = 1 if nbits == 8 else 2
-    a.w_pack_bits = 0 if nbits == 8 else 8
-    a.w_dtype = 3 if nbits == 8 else 5
-    a.input_dtype, a.output_dtype, a.meta_dtype = in_dt, (1 if in_dt == 14 else 2), 5
-    a.channel_scale_mode, a.W_group_mode = c_mode, 0
-    a.stride_xm, a.stride_xk = (K if in_dt in (14, 15, 16) else K // 2), 1
-    a.stride_wk, a.stride_wn = 1, (K if nbits == 8 else K // 2)
-    a.stride_om, a.stride_on = N, 1
-    a.stride_meta_g, a.stride_meta_n = N, 1
-    a.stride_sx_m = K // group
-    return a
-
-
-def _a8(in_dt, M, N, K):
-    a = _args(M=M, N=N, K=K, nbits=8, e=1, in_dt=in_dt, w_mode=0, c_mode=3, out_dt=1, gs=K)
-    a.scales_x = 0x1000
-    return a
 
 
 FAMILIES = {
