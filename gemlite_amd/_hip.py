@@ -245,7 +245,41 @@ class ExpertsRowsArgs(C.Structure):
     ]
 
 
+class ExpertsRowsGluArgs(C.Structure):
+    """struct gemlite_hip_experts_rows_glu_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("activation", C.c_int32),
+        ("rows", ExpertsRowsArgs),
+        ("reserved", C.c_int64 * 2),
+    ]
+
+
+class ExpertsCombineArgs(C.Structure):
+    """struct gemlite_hip_experts_combine_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dtype", C.c_int32),
+        ("ids_dtype", C.c_int32),
+        ("weights_dtype", C.c_int32),
+        ("y", C.c_void_p),
+        ("ids", C.c_void_p),
+        ("weights", C.c_void_p),
+        ("out", C.c_void_p),
+        ("n_slots", C.c_int64),
+        ("n_experts", C.c_int64),
+        ("slots_per_token", C.c_int64),
+        ("N", C.c_int64),
+        ("stride_y_slot", C.c_int64),
+        ("stride_out_token", C.c_int64),
+        ("reserved", C.c_int64 * 2),
+    ]
+
+
 EXPERTS_ROWS_MAX_EXPERTS = 4096  # GEMLITE_EXPERTS_ROWS_MAX_EXPERTS of the header
+EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN = 64  # GEMLITE_EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN of the header
 EXPERTS_GLU, EXPERTS_COMBINE, ACT_SILU = 1, 2, 1  # gemlite_hip_experts_fused_args.epilogue / .activation
 BIAS_NOT_ADDED = 1  # gemlite_hip_forward_ex: launched without the bias, the caller adds it
 
@@ -377,6 +411,15 @@ def load():
         for name in ("gemlite_hip_experts_route", "gemlite_hip_forward_experts_rows"):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = [C.POINTER(ExpertsRowsArgs), C.c_void_p]
+        for name in ("gemlite_hip_experts_rows_glu_per_block", "gemlite_hip_experts_rows_glu_query"):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [C.POINTER(ExpertsRowsGluArgs)]
+        lib.gemlite_hip_forward_experts_rows_glu.restype = C.c_int
+        lib.gemlite_hip_forward_experts_rows_glu.argtypes = [C.POINTER(ExpertsRowsGluArgs), C.c_void_p]
+        lib.gemlite_hip_experts_combine.restype = C.c_int
+        lib.gemlite_hip_experts_combine.argtypes = [C.POINTER(ExpertsCombineArgs), C.c_void_p]
+        lib.gemlite_hip_experts_combine_query.restype = C.c_int
+        lib.gemlite_hip_experts_combine_query.argtypes = [C.POINTER(ExpertsCombineArgs)]
         if lib.gemlite_hip_abi_version() != ABI_VERSION:
             raise GemliteHipError("libgemlite_hip.so ABI version mismatch; rebuild it")
         _lib = lib
@@ -406,6 +449,8 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_forward_experts_fused", "gemlite_hip_experts_fused_query",
     "gemlite_hip_experts_rows_workspace_bytes", "gemlite_hip_experts_rows_per_block", "gemlite_hip_experts_route",
     "gemlite_hip_forward_experts_rows", "gemlite_hip_experts_rows_query",
+    "gemlite_hip_forward_experts_rows_glu", "gemlite_hip_experts_rows_glu_query", "gemlite_hip_experts_rows_glu_per_block",
+    "gemlite_hip_experts_combine", "gemlite_hip_experts_combine_query",
 )
 
 

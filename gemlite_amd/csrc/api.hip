@@ -693,6 +693,126 @@ int gemlite_hip_forward_experts_rows(const gemlite_hip_experts_rows_args* args, 
     return launch(L.fn, L.grid, dim3(64 * 8, 1, 1), kargs, lds, (hipStream_t)stream);
 }
 
+// ---- the batched gate/up launch with SwiGLU inside (gemm_wn_rows_experts_glu.hip: gemm_w4_rows_experts_glu_kernel): the nested request by
+// experts_rows_plan's rules, unchanged, then the GLU forms' own.  Grid (I / 16, Bmax); the table is the one the route launch wrote.
+struct ExpertsRowsGluLaunch {
+    ExpertsRowsLaunch base;
+    ExpertsRowsGluTail tail;
+    const void* fn;
+    dim3 grid;
+};
+
+static int experts_rows_glu_plan(const gemlite_hip_experts_rows_glu_args* g, ExpertsRowsGluLaunch& L, bool with_workspace) {
+    if (!g || g->struct_size != sizeof(gemlite_hip_experts_rows_glu_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    // the nested request first, without its workspace: the table's size depends on R, and the default R on the GLU cap
+    const int v = experts_rows_plan(&g->rows, L.base, false);
+    if (v != GEMLITE_OK) return v;
+    if (g->activation != GEMLITE_ACT_SILU) return GEMLITE_ERR_UNSUPPORTED;
+    const gemlite_hip_experts_args& e = g->rows.experts;
+    if (e.layer.N % 32 != 0) return GEMLITE_ERR_BAD_SHAPE;
+    const uint32_t gs_shift = (L.base.base.d3.modes >> 8) & 255u;
+    if (gs_shift < 6) return GEMLITE_ERR_UNSUPPORTED;  // groups of 32: the two-tile body spills
+    const int spg = gs_shift >= 7 ? 4 : 2, cap = spg == 4 ? 64 : 32;
+    if (g->rows.rows_per_block > cap) return GEMLITE_ERR_BAD_SHAPE;
+    gemlite_hip_experts_rows_args rows = g->rows;
+    if (!rows.rows_per_block) rows.rows_per_block = experts_rows_default_r(e.n_slots, e.n_experts, cap);
+    const int vw = experts_rows_plan(&rows, L.base, with_workspace);  // (again at the resolved R: the workspace rule, the tail)
+    if (vw != GEMLITE_OK) return vw;
+    L.fn = gemm_wn_rows_experts_glu_fn(e.layer.input_dtype == GEMLITE_DT_FP16 ? 0 : 1, L.base.R / 16, spg, e.bias != nullptr);
+    if (!L.fn) return GEMLITE_ERR_UNSUPPORTED;
+    L.tail.rows = L.base.tail;
+    L.tail.half_tiles = (uint32_t)(e.layer.N / 32);
+    L.grid = dim3((unsigned)(e.layer.N / 32), (unsigned)experts_rows_bmax(e.n_slots, e.n_experts, L.base.R), 1);
+    return GEMLITE_OK;
+}
+
+int gemlite_hip_experts_rows_glu_query(const gemlite_hip_experts_rows_glu_args* args) {
+    ExpertsRowsGluLaunch L;
+    return experts_rows_glu_plan(args, L, true);
+}
+
+int gemlite_hip_experts_rows_glu_per_block(const gemlite_hip_experts_rows_glu_args* args) {
+    ExpertsRowsGluLaunch L;
+    const int v = experts_rows_glu_plan(args, L, false);
+    return v != GEMLITE_OK ? v : L.base.R;
+}
+
+int gemlite_hip_forward_experts_rows_glu(const gemlite_hip_experts_rows_glu_args* args, void* stream) {
+    ExpertsRowsGluLaunch L;
+    const int v = experts_rows_glu_plan(args, L, true);
+    if (v != GEMLITE_OK) return v;
+    int dev = 0;
+    const int dv = check_device(&dev);
+    if (dv != GEMLITE_OK) return dv;
+    const size_t lds = gemm_wn_rows_experts_lds_bytes();
+    const int le = ensure_lds(L.fn, lds, dev);
+    if (le != GEMLITE_OK) return le;
+    Decode3Args& d = L.base.base.d3;
+    int M = L.base.R;
+    void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
+                     (void*)&d.nch_total, (void*)&d.modes, (void*)&M, (void*)&L.base.sxm2, (void*)&L.base.som, (void*)&L.tail};
+    return launch(L.fn, L.grid, dim3(64 * 8, 1, 1), kargs, lds, (hipStream_t)stream);
+}
+
+// ---- the routing-weight sum of a batch (experts_combine.hip: experts_combine_kernel): one memory-bound launch, grid (column groups, tokens) ----
+struct ExpertsCombineLaunch {
+    ExpertsCombineArgs a;
+    const void* fn;
+    dim3 grid, block;
+};
+
+static int experts_combine_plan(const gemlite_hip_experts_combine_args* c, ExpertsCombineLaunch& L) {
+    if (!c || c->struct_size != sizeof(gemlite_hip_experts_combine_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (!c->y || !c->ids || !c->weights || !c->out) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (c->n_slots <= 0 || c->n_experts <= 0 || c->slots_per_token <= 0 || c->N <= 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    const bool f16 = c->dtype == GEMLITE_DT_FP16, ids64 = c->ids_dtype == GEMLITE_DT_INT64, w32 = c->weights_dtype == GEMLITE_DT_FP32;
+    if (!f16 && c->dtype != GEMLITE_DT_BF16) return GEMLITE_ERR_UNSUPPORTED;
+    if (!ids64 && c->ids_dtype != GEMLITE_DT_INT32) return GEMLITE_ERR_UNSUPPORTED;
+    if (!w32 && c->weights_dtype != c->dtype) return GEMLITE_ERR_UNSUPPORTED;
+    if (((uintptr_t)c->y % 4) != 0 || ((uintptr_t)c->out % 4) != 0 || ((uintptr_t)c->ids % (ids64 ? 8 : 4)) != 0 ||
+        ((uintptr_t)c->weights % (w32 ? 4 : 2)) != 0)
+        return GEMLITE_ERR_BAD_ARGUMENT;
+    if (c->stride_y_slot < 0 || c->stride_out_token < 0 || (c->stride_y_slot % 2) != 0 || (c->stride_out_token % 2) != 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (c->N % 16 != 0 || c->slots_per_token > GEMLITE_EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN || c->n_slots % c->slots_per_token != 0 ||
+        c->n_slots > 65535 || c->n_experts > 0x7FFFFFFF)
+        return GEMLITE_ERR_BAD_SHAPE;
+    const int64_t tokens = c->n_slots / c->slots_per_token;
+    if (c->N >= (1ll << 31) || c->stride_y_slot >= (1ll << 31) || c->stride_out_token >= (1ll << 31) ||
+        (c->n_slots - 1) * c->stride_y_slot + c->N >= (1ll << 31) || (tokens - 1) * c->stride_out_token + c->N >= (1ll << 31))
+        return GEMLITE_ERR_BAD_SHAPE;
+    const bool wide = ((uintptr_t)c->y % 16) == 0 && ((uintptr_t)c->out % 16) == 0 && (c->stride_y_slot % 8) == 0 && (c->stride_out_token % 8) == 0;
+    L.a.y = (const uint16_t*)c->y;
+    L.a.ids = c->ids;
+    L.a.weights = c->weights;
+    L.a.out = (uint16_t*)c->out;
+    L.a.n_experts = (uint32_t)c->n_experts;
+    L.a.spt = (uint32_t)c->slots_per_token;
+    L.a.N = (uint32_t)c->N;
+    L.a.stride_y = (uint32_t)c->stride_y_slot;
+    L.a.stride_out = (uint32_t)c->stride_out_token;
+    L.fn = experts_combine_fn(f16 ? 0 : 1, ids64, w32, wide);
+    const int64_t threads = experts_combine_threads(), per_block = threads * (wide ? 8 : 2);
+    L.block = dim3((unsigned)threads, 1, 1);
+    L.grid = dim3((unsigned)((c->N + per_block - 1) / per_block), (unsigned)tokens, 1);
+    return GEMLITE_OK;
+}
+
+int gemlite_hip_experts_combine_query(const gemlite_hip_experts_combine_args* args) {
+    ExpertsCombineLaunch L;
+    return experts_combine_plan(args, L);
+}
+
+int gemlite_hip_experts_combine(const gemlite_hip_experts_combine_args* args, void* stream) {
+    ExpertsCombineLaunch L;
+    const int v = experts_combine_plan(args, L);
+    if (v != GEMLITE_OK) return v;
+    int dev = 0;
+    const int dv = check_device(&dev);
+    if (dv != GEMLITE_OK) return dv;
+    void* kargs[] = {(void*)&L.a};
+    return launch(L.fn, L.grid, L.block, kargs, 0, (hipStream_t)stream);
+}
+
 int gemlite_hip_scale_activations_per_token(const void* x, void* y, float* scales, int64_t M, int64_t K,
                                             int64_t stride_xm, int32_t in_dtype, int32_t out_dtype, void* stream) {
     if (!x || !y || !scales || M <= 0 || K <= 0) return GEMLITE_ERR_BAD_ARGUMENT;

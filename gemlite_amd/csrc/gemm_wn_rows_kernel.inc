@@ -14,6 +14,15 @@
 //       slot's output row (SCATTER); a block of the invalid bucket stores zeros.  Everything between is the single-layer body, and a row
 //       of the MFMA result depends on no other row: a slot is bit-identical to its row of the single-layer form.  Undefined or 0: the
 //       forms above, token for token.
+//   GL_ROWS5_EXPERTS_GLU = 1 on top of GL_ROWS5_EXPERTS (gemm_wn_rows_experts_glu.hip: gemm_w4_rows_experts_glu_kernel /
+//       gemm_w4_rows_bias_experts_glu_kernel), instantiated with NT = 2: the experts form with SwiGLU in its epilogue — grid (I / 16, Bmax),
+//       I = N / 2; block (t, b) computes tile t (gate, columns [0, I)) and tile t + I / 16 (up) of work block b.  The body is the NT = 2 body
+//       whose second tile lies half_tiles tiles further instead of adjacent (GL_ROWS5_COL0 / _W_NEXT / _M_NEXT below, and + I elements
+//       in the bias); requests per chunk, wait counts, LDS layout and the x gather are those of NT = 2, a piece of x read from LDS feeds
+//       both tiles, and the MFMA / fold sequence of a tile is that of NT = 1.  Behind the 8-wave sum one thread holds the gate pair and
+//       the up pair of (row, column pair): each is rounded as the experts form rounds it (bias included), then from_float(silu(g16) *
+//       u16) — fp32, one rounding — goes to the slot's I-wide row; a block of the invalid bucket stores I zeros per slot.  Undefined
+//       or 0: the forms above, token for token (the three macros expand to what stood in their place).
 #if defined(GL_ROWS5_GROUP) && GL_ROWS5_GROUP
 #define GL_ROWS5_GROUPED 1
 #else
@@ -24,7 +33,25 @@
 #else
 #define GL_ROWS5_EXP 0
 #endif
-#if GL_ROWS5_EXP
+#if defined(GL_ROWS5_EXPERTS_GLU) && GL_ROWS5_EXPERTS_GLU
+#if !GL_ROWS5_EXP
+#error "GL_ROWS5_EXPERTS_GLU is a form of GL_ROWS5_EXPERTS"
+#endif
+#define GL_ROWS5_GLU 1
+#define GL_ROWS5_OUT_COLS TC                         // output columns of a block
+#define GL_ROWS5_COL0 (tile * TC)                    // first column of the block's first tile (weights, metadata, bias, output)
+#define GL_ROWS5_W_NEXT(n) ((uint32_t)(n) * glu_w4)  // bytes from the first tile to tile n inside a packed row
+#define GL_ROWS5_M_NEXT(n) ((uint32_t)(n) * glu_m2)  // ... inside a metadata row
+#else
+#define GL_ROWS5_GLU 0
+#define GL_ROWS5_OUT_COLS TCN
+#define GL_ROWS5_COL0 (tile * TCN)
+#define GL_ROWS5_W_NEXT(n) ((uint32_t)(n * 64))
+#define GL_ROWS5_M_NEXT(n) ((uint32_t)(n * 32))
+#endif
+#if GL_ROWS5_GLU
+#define GL_ROWS5_BIAS_PARAM , const ExpertsRowsGluTail gtail
+#elif GL_ROWS5_EXP
 #define GL_ROWS5_BIAS_PARAM , const ExpertsRowsTail tail
 #elif GL_ROWS5_GROUPED
 #define GL_ROWS5_BIAS_PARAM , const GroupTable<GL_ROWS5_BIAS != 0> tab
@@ -65,6 +92,11 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
         const int xcd = tile & 7, idx = tile >> 3;
         tile = (((idx >> 1) << 3) + xcd) * 2 + (idx & 1);
     }
+#if GL_ROWS5_GLU
+    static_assert(NT == 2, "a gate tile and an up tile");
+    const ExpertsRowsTail& tail = gtail.rows;
+    const uint32_t glu_w4 = gtail.half_tiles * 64u, glu_m2 = gtail.half_tiles * 32u;
+#endif
 #if GL_ROWS5_EXP
     // this block's work block: beyond the used count -> nothing to do (uniform, in front of any address arithmetic)
     const int32_t* const wtab = tail.table;
@@ -73,10 +105,10 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
     const int32_t* const brow = wtab + EXPERTS_ROWS_HEADER + gridDim.y + (size_t)blockIdx.y * (16 * MT);  // the block's 16 MT slots, -1 = none
     M = 16 * MT;
     if (expert >= tail.n_experts) {  // the invalid bucket: zeros to this tile of its slots, nothing is dereferenced
-        for (int o = tid; o < MT * 16 * (TCN / 2); o += NW * 64) {
-            const int m = o / (TCN / 2), cp = o % (TCN / 2);
+        for (int o = tid; o < MT * 16 * (GL_ROWS5_OUT_COLS / 2); o += NW * 64) {
+            const int m = o / (GL_ROWS5_OUT_COLS / 2), cp = o % (GL_ROWS5_OUT_COLS / 2);
             const int slot = brow[m];
-            if ((uint32_t)slot < tail.n_slots) *(uint32_t*)(out + (size_t)slot * som + (size_t)(tile * TCN + cp * 2)) = 0u;
+            if ((uint32_t)slot < tail.n_slots) *(uint32_t*)(out + (size_t)slot * som + (size_t)(GL_ROWS5_COL0 + cp * 2)) = 0u;
         }
         return;
     }
@@ -123,7 +155,7 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
     const int rd_off = BITS == 4 ? (kb & 1) * WSLOT_I1 + (kb >> 1) * 16 + j   // row 4 s + kb: + 32 s
                                  : (kb >> 1) * WSLOT_I1 + j;                  // 2-bit: row 2 s + (kb >> 1): + 16 s (kb = 2 m, 2 m + 1 read the same dword)
     const uint32_t half_sh = (uint32_t)(kb & 1) * 16u;                        // 2-bit: which half of that word
-    const uint32_t wo0 = (uint32_t)(wave * CHUNK + g * 2) * sw4 + (uint32_t)(tile * TCN + c * 4) * 4u;  // (+ 64 bytes per further column tile)
+    const uint32_t wo0 = (uint32_t)(wave * CHUNK + g * 2) * sw4 + (uint32_t)(GL_ROWS5_COL0 + c * 4) * 4u;  // (+ 64 bytes per further column tile)
 
     // ---- x pieces: LDS slot (row r, 16-byte slot p') of a buffer holds piece p = p' ^ f(r) of the row; DMA instruction q fills rows
     //      q RPI .. q RPI + RPI - 1 lane-linearly.  f: the low bits of r that separate the rows one ds_read_b128 lane group touches
@@ -163,14 +195,14 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
     //      always in bounds — so the loop stays branch-free)
     const char* sbase = need_s ? sp : wb;
     const char* zbase = need_z ? zp : wb;
-    const uint32_t mcol = (uint32_t)(tile * TCN + j) * 2u;  // (+ 32 bytes per further column tile)
+    const uint32_t mcol = (uint32_t)(GL_ROWS5_COL0 + j) * 2u;  // (+ 32 bytes per further column tile)
     struct WSet { u32x4 w0[NT], w1[NT]; uint32_t s[NT][NML], z[NT][NML]; };
     auto issue_w = [&](WSet& S, int ch) {
         const uint32_t wo = wo0 + (uint32_t)(ch * CSTRIDE) * sw4;
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-            gld128_nt(S.w0[n], wb, wo + (uint32_t)(n * 64));
-            gld128_nt(S.w1[n], wb, wo + sw4 + (uint32_t)(n * 64));
+            gld128_nt(S.w0[n], wb, wo + GL_ROWS5_W_NEXT(n));
+            gld128_nt(S.w1[n], wb, wo + sw4 + GL_ROWS5_W_NEXT(n));
         }
         const uint32_t k0 = (uint32_t)(ch * CSTRIDE + wave * CHUNK) * (uint32_t)E;
 #pragma unroll
@@ -178,7 +210,7 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
 #pragma unroll
             for (int l = 0; l < NML; ++l) {
                 const int gq = 4 * l + kb < NG ? 4 * l + kb : NG - 1;
-                const uint32_t mo = ((k0 + (uint32_t)(gq * 32 * SPG)) >> gs_shift) * mstride2 + mcol + (uint32_t)(n * 32);
+                const uint32_t mo = ((k0 + (uint32_t)(gq * 32 * SPG)) >> gs_shift) * mstride2 + mcol + GL_ROWS5_M_NEXT(n);
                 gld16(S.s[n][l], sbase, need_s ? mo : 0u);
                 gld16(S.z[n][l], zbase, need_z ? mo : 0u);
             }
@@ -307,6 +339,38 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
 #pragma unroll
             for (int r = 0; r < 4; ++r) part[(t * 16 + 4 * kb + r) * TCN + n * TC + j] = tot[t][n][r];
     __syncthreads();
+#if GL_ROWS5_GLU
+    constexpr int CPR = TC / 2;                // pairs of adjacent OUTPUT columns per row of the block
+    constexpr int NPAIR = MT * 16 * CPR;
+    for (int o = tid; o < NPAIR; o += NW * 64) {
+        const int m = o / CPR, cp = o % CPR;
+        float g0 = 0.f, g1 = 0.f, u0 = 0.f, u1 = 0.f;  // the sums of the experts form, pair by pair: gate at column cp * 2, up TC further
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float2 pg = *(const float2*)(smem + (size_t)w * WAVE_LDS + (size_t)(m * TCN + cp * 2) * 4);
+            const float2 pu = *(const float2*)(smem + (size_t)w * WAVE_LDS + (size_t)(m * TCN + TC + cp * 2) * 4);
+            g0 += pg.x;
+            g1 += pg.y;
+            u0 += pu.x;
+            u1 += pu.y;
+        }
+        uint16_t hg0 = TR::from_float(g0), hg1 = TR::from_float(g1), hu0 = TR::from_float(u0), hu1 = TR::from_float(u1);
+#if GL_ROWS5_BIAS
+        // (the two roundings of "matmul, then out += bias", as the experts form has them)
+        const uint16_t* bp = bias + (size_t)(GL_ROWS5_COL0 + cp * 2);
+        const uint32_t glu_i = gtail.half_tiles * 16u;  // the up half of the bias lies I elements further
+        hg0 = TR::from_float(TR::to_float(hg0) + TR::to_float(bp[0]));
+        hg1 = TR::from_float(TR::to_float(hg1) + TR::to_float(bp[1]));
+        hu0 = TR::from_float(TR::to_float(hu0) + TR::to_float(bp[glu_i]));
+        hu1 = TR::from_float(TR::to_float(hu1) + TR::to_float(bp[glu_i + 1]));
+#endif
+        const uint16_t h0 = TR::from_float(silu_f32(TR::to_float(hg0)) * TR::to_float(hu0));
+        const uint16_t h1 = TR::from_float(silu_f32(TR::to_float(hg1)) * TR::to_float(hu1));
+        const int oslot = brow[m];  // scatter: the row's slot; nothing is stored for a -1 entry
+        if ((uint32_t)oslot < tail.n_slots)
+            *(uint32_t*)(out + (size_t)(uint32_t)oslot * som + (size_t)(GL_ROWS5_COL0 + cp * 2)) = (uint32_t)h0 | ((uint32_t)h1 << 16);
+    }
+#else
     constexpr int CPR = TCN / 2;               // pairs of adjacent columns per row of the block
     constexpr int NPAIR = MT * 16 * CPR;
     for (int o = tid; o < NPAIR; o += NW * 64) {
@@ -351,8 +415,14 @@ __global__ __launch_bounds__(rows5::NW * 64, 1) void GL_ROWS5_KERNEL(const char*
 #undef GL_ROWS5_STORE_IF
 #undef GL_ROWS5_OUT_ROW
     }
+#endif
 }
 
 #undef GL_ROWS5_BIAS_PARAM
 #undef GL_ROWS5_GROUPED
 #undef GL_ROWS5_EXP
+#undef GL_ROWS5_GLU
+#undef GL_ROWS5_OUT_COLS
+#undef GL_ROWS5_COL0
+#undef GL_ROWS5_W_NEXT
+#undef GL_ROWS5_M_NEXT

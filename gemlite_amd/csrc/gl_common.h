@@ -648,6 +648,34 @@ struct ExpertsRowsTail {
 inline int64_t experts_rows_bmax(int64_t n_slots, int64_t n_experts, int64_t R) {
     return (n_slots + R - 1) / R + (n_experts + 1 < n_slots ? n_experts + 1 : n_slots);
 }
+// gemm_w4_rows_experts_glu_kernel (gemm_wn_rows_experts_glu.hip; gemlite_hip_forward_experts_rows_glu): the rows tail, then the distance
+// between a block's gate tile and its up tile.  The launch's output rows are I = 16 half_tiles wide
+struct ExpertsRowsGluTail {
+    ExpertsRowsTail rows;
+    uint32_t half_tiles;  // I / 16
+};
+// experts_combine_kernel (experts_combine.hip; gemlite_hip_experts_combine): out[t] = round(sum_k w[t spt + k] * y[t spt + k]) over the
+// slots with a valid id.  Strides in elements, below 2^31 with the row behind them
+struct ExpertsCombineArgs {
+    const uint16_t* y;
+    const void* ids;      // int32 or int64 (the kernel's IDS64)
+    const void* weights;  // fp32 or the type of y (the kernel's W32)
+    uint16_t* out;
+    uint32_t n_experts, spt, N;
+    uint32_t stride_y, stride_out;
+};
+
+// silu of the GLU epilogues (gemv_w4_decode3_experts_fused_kernel, gemm_w4_rows_experts_glu_kernel): v / (1 + exp(-v)) in fp32.  Below
+// -88 exp(-v) leaves fp32 and the quotient is -0, while silu(v) = v exp(v) is a normal bf16 number down to about -92 and a subnormal
+// one down to -97: there v exp(v / 2) exp(v / 2), whose factors stay normal.  v = -Inf gives -Inf * 0 = NaN, as the quotient does
+__device__ __forceinline__ float silu_f32(float v) {
+    float act = v / (1.f + expf(-v));
+    if (v < -88.f) {
+        const float hv = expf(0.5f * v);
+        act = (v * hv) * hv;
+    }
+    return act;
+}
 template <bool BIASED>
 struct GroupTable {
     GroupMember m[DECODE3_GMAX - 1];

@@ -66,7 +66,10 @@ const void* gemv_w4_decode3_experts_fused_fn(int tag, int epilogue, bool biased,
 const void* gemm_wn_rows_group_fn(int tag, int mt, int spg, int nt, int bits, bool biased);  // gemm_wn_rows_group.hip: the grouped forms
 const void* gemm_wn_rows_experts_fn(int tag, int mt, int spg, bool biased);  // gemm_wn_rows_experts.hip
 size_t gemm_wn_rows_experts_lds_bytes();
+const void* gemm_wn_rows_experts_glu_fn(int tag, int mt, int spg, bool biased);  // gemm_wn_rows_experts_glu.hip (nullptr: no such form)
 const void* experts_route_fn(bool ids64);  // experts_route.hip
+const void* experts_combine_fn(int tag, bool ids64, bool w32, bool wide);  // experts_combine.hip
+int experts_combine_threads();
 // the instantiations of gemm_wn_mma_kernel.inc, one translation unit per activation type and word width (gemm_wn_mma_*.hip)
 const void* mma_lookup_f16(int kind, int nbits, int mi, int xdt);
 const void* mma_lookup_bf16(int kind, int nbits, int mi, int xdt);

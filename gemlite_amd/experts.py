@@ -15,6 +15,10 @@ routing-weight sum over a token's slots.  Every member is rounded as its slot of
 Batches: ``experts.route(ids)`` sorts the slots by expert on the GPU into work blocks (an ``ExpertsRouting``) and
 ``experts.forward_batched(x, ids, routing)`` streams every expert's weights once per work block through the MFMA rows kernel
 (``gemlite_hip_experts_route`` / ``gemlite_hip_forward_experts_rows``).  Opt-in: ``forward`` never dispatches to it.
+
+The batched MLP in four launches: ``experts.forward_batched_glu`` is the rows launch with SwiGLU in its epilogue
+(``gemlite_hip_forward_experts_rows_glu``), ``experts.combine_batched`` the routing-weight sum over a token's slots in one launch
+(``gemlite_hip_experts_combine``), ``GemLiteExpertsMLP.forward_batched_fused`` route + GLU + down + combine.  Opt-in as well.
 """
 import threading
 from typing import List, Optional, Sequence
@@ -352,6 +356,157 @@ def _forward_experts_rows_fake(x, expert_ids, workspace, rows_per_block, bias, t
     return torch.empty(tuple(expert_ids.shape) + (W_q.shape[2],), device=x.device, dtype=x.dtype)
 
 
+# ---- the batched MLP without an fp32 intermediate: SwiGLU inside the gate/up rows launch, the combine in one launch ----
+GLU_ROWS_DOMAIN = ("domain: N % 32 == 0 ([gate; up] halves in whole 16-column tiles), groups of 64 or more (groups of 32 have no GLU form), "
+                   "rows_per_block up to 64 for groups >= 128 and up to 32 for groups of 64")
+COMBINE_DOMAIN = ("domain: fp16 / bf16 y with N %% 16 == 0, 1 <= top_k <= %d, at most %d slots, 4-byte aligned rows with even strides"
+                  % (_hip.EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN, MAX_SLOTS))
+
+
+def _glu_rows_args(r: "_hip.ExpertsRowsArgs") -> "_hip.ExpertsRowsGluArgs":
+    g = _hip.ExpertsRowsGluArgs()
+    g.struct_size = _hip.C.sizeof(_hip.ExpertsRowsGluArgs)
+    g.activation = _hip.ACT_SILU
+    g.rows = r
+    return g
+
+
+def _raise_glu_rows(rc: int, what: str):
+    if rc in (_hip.ERR_BAD_SHAPE, _hip.ERR_UNSUPPORTED, _hip.ERR_BAD_ARGUMENT, _hip.ERR_WORKSPACE):
+        raise NotImplementedError(f"{what}: {_hip.status_string(rc)} ({GLU_ROWS_DOMAIN}; {ROWS_DOMAIN})")
+    _hip.raise_for_status(rc, what)
+
+
+def _resolve_rows_glu(bias: Optional[Tensor], tensor_args, meta_args, n_slots: int, rows_per_block: Optional[int]) -> int:
+    """_resolve_rows for the GLU launch: the R gemlite_hip_experts_rows_glu_per_block resolves (host only); refusals in words."""
+    want = 0 if rows_per_block is None else int(rows_per_block)
+    if want and want not in ROWS_PER_BLOCK:
+        raise ValueError(f"rows_per_block is {rows_per_block}: one of {ROWS_PER_BLOCK}, or None for the library's default")
+    g = _glu_rows_args(_rows_args(_stand_in_args(bias, tensor_args, meta_args, n_slots), want, None))
+    rc = _hip.load().gemlite_hip_experts_rows_glu_per_block(_hip.C.byref(g))
+    if rc < 0:
+        _raise_glu_rows(rc, f"GemLiteExperts.forward_batched_glu: N={tensor_args[0].shape[2]}, groups of {meta_args[2]}, {n_slots} slots over "
+                            f"{tensor_args[0].shape[0]} experts, rows_per_block={rows_per_block}")
+    return rc
+
+
+def _forward_rows_glu_impl(x: Tensor, expert_ids: Tensor, workspace: Tensor, rows_per_block: int, bias: Optional[Tensor],
+                           tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    W_q = tensor_args[0]
+    N, K = W_q.shape[2], W_q.shape[1] * meta_args[4]
+    lib = _hip.load()
+    for t, name in ((x, "x"), (expert_ids, "expert_ids"), (workspace, "workspace"), (W_q, "W_q")):
+        _hip.require_gpu_tensor(t, name)
+    if x.device != W_q.device or expert_ids.device != W_q.device or workspace.device != W_q.device:
+        raise _hip.GemliteHipError(f"x is on {x.device}, expert_ids on {expert_ids.device}, the routing on {workspace.device}, "
+                                   f"the packed weights on {W_q.device}")
+    if expert_ids.dtype not in (torch.int32, torch.int64):
+        raise NotImplementedError(f"expert_ids are {expert_ids.dtype}: int32 or int64")
+    rows, spx = _split(x, expert_ids, K)
+    out = torch.empty(tuple(expert_ids.shape) + (N // 2,), dtype=x.dtype, device=x.device)
+    if expert_ids.numel() == 0:
+        return out
+    if workspace.dtype != torch.int32 or not workspace.is_contiguous():
+        raise ValueError(f"the routing workspace is {workspace.dtype}, contiguous={workspace.is_contiguous()}: a contiguous int32 tensor")
+    x2 = x.contiguous().view(rows, K)
+    ids = expert_ids.contiguous()
+    e = _call_args(x2, ids, out.data_ptr(), bias, tensor_args, meta_args, spx)
+    e.stride_out_slot = N // 2
+    g = _glu_rows_args(_rows_args(e, rows_per_block, workspace))
+    with _hip.on_device(x.device):
+        rc = lib.gemlite_hip_forward_experts_rows_glu(_hip.C.byref(g), _hip.current_stream_handle(x.device))
+    if rc != _hip.OK:
+        _raise_glu_rows(rc, "gemlite_hip_forward_experts_rows_glu")
+    return out
+
+
+def _combine_args(y2: Tensor, ids: Tensor, w: Tensor, out2: Tensor, n_experts: int, top_k: int) -> "_hip.ExpertsCombineArgs":
+    """y2 [slots, N] and out2 [tokens, N] with unit inner strides; ids and w contiguous, one entry per slot."""
+    c = _hip.ExpertsCombineArgs()
+    c.struct_size = _hip.C.sizeof(_hip.ExpertsCombineArgs)
+    c.dtype = TORCH_TO_DTYPE[y2.dtype].value
+    c.ids_dtype = TORCH_TO_DTYPE[ids.dtype].value
+    c.weights_dtype = TORCH_TO_DTYPE[w.dtype].value
+    c.y, c.ids, c.weights, c.out = y2.data_ptr(), ids.data_ptr(), w.data_ptr(), out2.data_ptr()
+    c.n_slots, c.n_experts, c.slots_per_token, c.N = y2.shape[0], n_experts, top_k, y2.shape[1]
+    c.stride_y_slot, c.stride_out_token = y2.stride(0), out2.stride(0)
+    return c
+
+
+def _rows_of(y: Tensor) -> Tensor:
+    """[..., N] -> [rows, N] with a unit inner stride and one row stride, as a VIEW where the layout allows (a sliced output of
+    forward_batched stays in place), else a copy."""
+    N = y.shape[-1]
+    if y.dim() >= 1 and y.stride(-1) == 1:
+        try:
+            return y.view(-1, N)
+        except RuntimeError:
+            pass
+    return y.reshape(-1, N).contiguous()
+
+
+def _combine_impl(y: Tensor, expert_ids: Tensor, weights: Tensor, n_experts: int) -> Tensor:
+    lib = _hip.load()
+    _combine_check(y, expert_ids, weights)
+    tensors = ((y, "y"), (expert_ids, "expert_ids"), (weights, "weights"))
+    for t, name in tensors:
+        _hip.require_gpu_tensor(t, name)
+    if any(t.device != y.device for t, _ in tensors):
+        raise _hip.GemliteHipError("y, expert_ids and weights live on different devices: " + ", ".join(f"{name} on {t.device}" for t, name in tensors))
+    N, top_k = y.shape[-1], expert_ids.shape[-1]
+    out = torch.empty(tuple(expert_ids.shape[:-1]) + (N,), dtype=y.dtype, device=y.device)
+    if out.numel() == 0:
+        return out
+    if top_k == 0:
+        return out.zero_()  # (a sum without terms)
+    y2 = _rows_of(y)
+    if y2.data_ptr() % 4 or y2.stride(0) % 2:
+        y2 = y2.contiguous()
+    c = _combine_args(y2, expert_ids.contiguous(), weights.contiguous(), out.view(-1, N), n_experts, top_k)
+    with _hip.on_device(y.device):
+        rc = lib.gemlite_hip_experts_combine(_hip.C.byref(c), _hip.current_stream_handle(y.device))
+    if rc in (_hip.ERR_BAD_SHAPE, _hip.ERR_UNSUPPORTED):
+        raise NotImplementedError(f"gemlite_hip_experts_combine: y {tuple(y.shape)}, top_k={top_k}: {_hip.status_string(rc)} ({COMBINE_DOMAIN})")
+    _hip.raise_for_status(rc, "gemlite_hip_experts_combine")
+    return out
+
+
+def _combine_check(y: Tensor, expert_ids: Tensor, weights: Tensor):
+    if expert_ids.dim() < 1:
+        raise ValueError("expert_ids should be [..., top_k]")
+    if y.dim() < 2 or tuple(y.shape[:-1]) != tuple(expert_ids.shape):
+        raise ValueError(f"y is {tuple(y.shape)}; expert_ids {tuple(expert_ids.shape)} asks for {tuple(expert_ids.shape) + ('N',)}")
+    if y.dtype not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"y is {y.dtype}: float16 or bfloat16")
+    if expert_ids.dtype not in (torch.int32, torch.int64):
+        raise NotImplementedError(f"expert_ids are {expert_ids.dtype}: int32 or int64")
+    _weights_like(weights, expert_ids, y)
+
+
+@torch.library.custom_op("gemlite::forward_experts_rows_glu", mutates_args=())
+def forward_experts_rows_glu(x: Tensor, expert_ids: Tensor, workspace: Tensor, rows_per_block: int, bias: Optional[Tensor],
+                             tensor_args: List[Tensor], meta_args: List[int]) -> Tensor:
+    return _forward_rows_glu_impl(x, expert_ids, workspace, rows_per_block, bias, tensor_args, meta_args)
+
+
+@torch.library.register_fake("gemlite::forward_experts_rows_glu")
+def _forward_experts_rows_glu_fake(x, expert_ids, workspace, rows_per_block, bias, tensor_args, meta_args):
+    W_q = tensor_args[0]
+    _split(x, expert_ids, W_q.shape[1] * meta_args[4])
+    return torch.empty(tuple(expert_ids.shape) + (W_q.shape[2] // 2,), device=x.device, dtype=x.dtype)
+
+
+@torch.library.custom_op("gemlite::experts_combine", mutates_args=())
+def experts_combine(y: Tensor, expert_ids: Tensor, weights: Tensor, n_experts: int) -> Tensor:
+    return _combine_impl(y, expert_ids, weights, n_experts)
+
+
+@torch.library.register_fake("gemlite::experts_combine")
+def _experts_combine_fake(y, expert_ids, weights, n_experts):
+    _combine_check(y, expert_ids, weights)
+    return torch.empty(tuple(expert_ids.shape[:-1]) + (y.shape[-1],), device=y.device, dtype=y.dtype)
+
+
 class ExpertsRouting:
     """The work table of one set of expert ids (``GemLiteExperts.route``): the slots sorted into work blocks of at most
     ``rows_per_block`` slots of one expert, on the GPU.  Owns the workspace tensor; valid for every ``GemLiteExperts`` with ``n_experts``
@@ -547,8 +702,12 @@ class GemLiteExperts(torch.nn.Module):
         return _forward_impl(x, expert_ids, self.bias, self.get_tensor_args(), self._meta)
 
     # ------------------------------------------------------------------------------------- batches
-    def rows_per_block(self, n_slots: int, rows_per_block: Optional[int] = None) -> int:
-        """The work-block size R the library resolves for `n_slots` slots on these experts (None: its default); host only."""
+    def rows_per_block(self, n_slots: int, rows_per_block: Optional[int] = None, glu: bool = False) -> int:
+        """The work-block size R the library resolves for `n_slots` slots on these experts (None: its default); host only.
+        ``glu=True``: the answer for ``forward_batched_glu``, whose two-tile blocks cap groups of 64 at 32 rows and have no form for
+        groups of 32 (NotImplementedError)."""
+        if glu:
+            return _resolve_rows_glu(self.bias, self.get_tensor_args(), self._meta, n_slots, rows_per_block)
         return _resolve_rows(self.bias, self.get_tensor_args(), self._meta, n_slots, rows_per_block)
 
     def route(self, expert_ids: Tensor, rows_per_block: Optional[int] = None) -> ExpertsRouting:
@@ -586,6 +745,36 @@ class GemLiteExperts(torch.nn.Module):
                                       "(route with rows_per_block=32, or with the stack of the smaller group size)")
         args = (x, expert_ids, routing.workspace, routing.rows_per_block, self.bias, self.get_tensor_args(), self._meta)
         return forward_experts_rows(*args) if torch.compiler.is_compiling() else _forward_rows_impl(*args)
+
+    def forward_batched_glu(self, x: Tensor, expert_ids: Tensor, routing: Optional[ExpertsRouting] = None) -> Tensor:
+        """-> ``[..., top_k, N // 2]``: ``silu(y[..., :I]) * y[..., I:]`` of ``y = forward_batched(x, expert_ids, routing)`` — fp32 on the
+        rounded values, one rounding — in the same one launch; no ``[..., top_k, N]`` intermediate exists.  Experts stacked
+        ``[gate; up]`` along N (``from_gate_up``).  Out of the domain (N % 32, groups of 32, a routing above the GLU cap): NotImplementedError."""
+        self._check_x(x)
+        if expert_ids.dim() < 1:
+            raise ValueError("expert_ids should be [..., top_k]")
+        _split(x, expert_ids, self.in_features)
+        if routing is None:
+            n_slots = expert_ids.numel()
+            if n_slots > MAX_SLOTS:
+                raise NotImplementedError(f"GemLiteExperts.forward_batched_glu: {n_slots} slots; one routing holds at most {MAX_SLOTS}")
+            routing = self.route(expert_ids, self.rows_per_block(n_slots, glu=True))
+        elif not isinstance(routing, ExpertsRouting):
+            raise TypeError(f"routing is a {type(routing).__name__}: an ExpertsRouting from GemLiteExperts.route, or None")
+        if routing.n_slots != expert_ids.numel() or routing.n_experts != self.num_experts:
+            raise ValueError(f"the routing holds {routing.n_slots} slots over {routing.n_experts} experts; expert_ids has "
+                             f"{expert_ids.numel()} slots and these are {self.num_experts} experts")
+        self.rows_per_block(max(routing.n_slots, 1), routing.rows_per_block, glu=True)  # the library's refusals, in words (host only)
+        args = (x, expert_ids, routing.workspace, routing.rows_per_block, self.bias, self.get_tensor_args(), self._meta)
+        return forward_experts_rows_glu(*args) if torch.compiler.is_compiling() else _forward_rows_glu_impl(*args)
+
+    def combine_batched(self, y: Tensor, expert_ids: Tensor, weights: Tensor) -> Tensor:
+        """-> ``[..., N]``: ``sum_k weights[..., k] * y[..., k, :]`` over the slots with an id in [0, E), in ONE launch — fp32 products and
+        adds in ascending k, one rounding: on the same ``y`` the bits of ``forward_combine``.  ``y`` is any ``[..., top_k, N]`` output of
+        ``forward_batched`` or ``forward`` (views with a unit inner stride are read in place); invalid slots are skipped unread."""
+        if torch.compiler.is_compiling():
+            return experts_combine(y, expert_ids, weights, self.num_experts)
+        return _combine_impl(y, expert_ids, weights, self.num_experts)
 
     def _check_fused(self, epilogue: int, top_k: int):
         """The library's answer for a fused epilogue on these experts (gemlite_hip_experts_fused_query on stand-ins, as _check_domain asks
@@ -671,6 +860,38 @@ class GemLiteExpertsMLP(torch.nn.Module):
         """The work-block size both stacks take: each one's own default where they agree, else the smaller (valid for both: only the
         cap of groups of 32 separates the defaults of two stacks with the same experts and slots)."""
         return min(self.gate_up.rows_per_block(n_slots), self.down.rows_per_block(n_slots))
+
+    def glu_fused(self) -> bool:
+        """Whether ``gate_up`` has a GLU form of the batched launch (N % 32 == 0 and groups of 64 or more); host only."""
+        try:
+            self.gate_up.rows_per_block(1, glu=True)
+        except NotImplementedError:
+            return False
+        return True
+
+    def rows_per_block_fused(self, n_slots: int) -> int:
+        """The work-block size ``forward_batched_fused`` routes with (host only): the smaller of gate_up's GLU answer and down's plain
+        answer — valid for both, since a stack takes every R up to its cap.  Where gate_up has no GLU form: ``rows_per_block``."""
+        if not self.glu_fused():
+            return self.rows_per_block(n_slots)
+        return min(self.gate_up.rows_per_block(n_slots, glu=True), self.down.rows_per_block(n_slots))
+
+    def forward_batched_fused(self, x: Tensor, topk_ids: Tensor, topk_weights: Tensor) -> Tensor:
+        """``forward_batched`` in four launches and without an fp32 intermediate in memory: ONE route, ``gate_up.forward_batched_glu``
+        (SwiGLU inside the rows launch), ``down.forward_batched`` on the SAME routing, ``down.combine_batched`` -> ``[..., hidden]``.
+        Where gate_up is outside the GLU domain (groups of 32) the gate/up launch and the torch SwiGLU of ``forward_batched`` stand in
+        for the second launch; the combine is one launch all the same."""
+        if topk_ids.dim() < 1:
+            raise ValueError("topk_ids should be [..., top_k]")
+        _weights_like(topk_weights, topk_ids, x)
+        routing = self.gate_up.route(topk_ids, self.rows_per_block_fused(topk_ids.numel()))
+        if self.glu_fused():
+            h = self.gate_up.forward_batched_glu(x, topk_ids, routing)
+        else:
+            y = self.gate_up.forward_batched(x, topk_ids, routing).float()
+            inter = self.intermediate_size
+            h = (torch.nn.functional.silu(y[..., :inter]) * y[..., inter:]).to(x.dtype)
+        return self.down.combine_batched(self.down.forward_batched(h, topk_ids, routing), topk_ids, topk_weights)
 
     def forward_batched(self, x: Tensor, topk_ids: Tensor, topk_weights: Tensor) -> Tensor:
         """``forward`` for MORE THAN ONE token: ONE route, ``gate_up.forward_batched``, ``silu(gate) * up`` in torch (fp32, one rounding),

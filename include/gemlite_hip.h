@@ -560,6 +560,63 @@ int gemlite_hip_experts_route(const gemlite_hip_experts_rows_args* args, void* s
 int gemlite_hip_forward_experts_rows(const gemlite_hip_experts_rows_args* args, void* stream);
 int gemlite_hip_experts_rows_query(const gemlite_hip_experts_rows_args* args);
 
+/* The batched expert MLP without an fp32 intermediate in memory: route, gate/up with SwiGLU inside, down, combine — four launches.
+ *   gemlite_hip_forward_experts_rows_glu  gemlite_hip_forward_experts_rows on experts whose N columns are [gate; up] halves of I = N / 2
+ *                                         columns (the layout of GEMLITE_EXPERTS_GLU), with the GLU epilogue of that call: grid (I / 16,
+ *                                         Bmax), block (t, b) computes tile t and tile t + I / 16 of work block b.  With g, u the outputs
+ *                                         of slot s as gemlite_hip_forward_experts_rows rounds them at the same R (bias included), its I
+ *                                         outputs at rows.experts.layer.out + s * stride_out_slot are round(silu(g) * u): fp32, one
+ *                                         rounding, silu exactly as GEMLITE_EXPERTS_GLU states it.  A slot of the invalid bucket gets I zeros.
+ *                                         `rows` is a complete gemlite_hip_forward_experts_rows request (its own struct_size set) and is
+ *                                         validated by the same rules first, stride_out_slot being the stride of the I-wide output rows;
+ *                                         the work table is the one gemlite_hip_experts_route writes for the same R.
+ *     Refusals beyond those of `rows`: GEMLITE_ERR_BAD_ARGUMENT (null struct, struct_size), GEMLITE_ERR_UNSUPPORTED (activation; groups
+ *     of 32: the two-tile body has no form that fits the registers), GEMLITE_ERR_BAD_SHAPE (N % 32 != 0; rows_per_block above the GLU cap:
+ *     64 for groups >= 128, 32 for groups of 64).  rows_per_block 0: the default rule of gemlite_hip_experts_rows_per_block under that cap.
+ *   gemlite_hip_experts_rows_glu_per_block the R the library resolves for `args` (workspace fields not read), or a negative status
+ *   gemlite_hip_experts_rows_glu_query     validates and never launches or dereferences; works without a GPU */
+typedef struct gemlite_hip_experts_rows_glu_args {
+    uint32_t struct_size;               /* sizeof(gemlite_hip_experts_rows_glu_args), ABI guard */
+    int32_t activation;                 /* GEMLITE_ACT_SILU */
+    gemlite_hip_experts_rows_args rows; /* exactly as for gemlite_hip_forward_experts_rows; out rows are I = N / 2 wide */
+    int64_t reserved[2];
+} gemlite_hip_experts_rows_glu_args;
+int gemlite_hip_forward_experts_rows_glu(const gemlite_hip_experts_rows_glu_args* args, void* stream);
+int gemlite_hip_experts_rows_glu_query(const gemlite_hip_experts_rows_glu_args* args);
+int gemlite_hip_experts_rows_glu_per_block(const gemlite_hip_experts_rows_glu_args* args);
+
+/*   gemlite_hip_experts_combine  the routing-weight sum over a token's slots in ONE launch (experts_combine_kernel): token t = the slots
+ *                                t * slots_per_token + k, k < slots_per_token; with y_k the row of slot k at y + slot * stride_y_slot,
+ *                                out + t * stride_out_token gets round(sum_k weights[slot_k] * float(y_k)) over the slots whose id lies in
+ *                                [0, n_experts): each product an fp32 multiply of its own, then an fp32 add, ascending k from 0, one
+ *                                rounding, no fused multiply-add — the numerics of GEMLITE_EXPERTS_COMBINE, so the same y gives the same
+ *                                bits.  A slot with an invalid id (negative, too large, an int64 with a high dword) is skipped: neither
+ *                                its y row nor its weight is read; a token without a valid id gets N zeros (+0).
+ *     (The rows launches sort the slots by expert, so a token's slots lie in different work blocks: the sum is a launch of its own.)
+ *     Domain: y and out fp16 or bf16 of the same type (`dtype`); ids int32 or int64; weights fp32 or `dtype`; N % 16 == 0;
+ *     1 <= slots_per_token <= 64, a divisor of n_slots; n_slots <= 65535; y and out 4-byte aligned with even, non-negative row strides
+ *     (what gemlite_hip_forward_experts_rows accepts for its output); every row offset plus N below 2^31 elements.  Rows that are
+ *     16-byte aligned (pointers % 16, strides % 8) are moved in 16-byte requests, others in 4-byte requests: the same bits.
+ *     GEMLITE_ERR_BAD_ARGUMENT (null or misaligned pointers, struct_size, non-positive counts, odd or negative strides),
+ *     GEMLITE_ERR_UNSUPPORTED (dtypes), GEMLITE_ERR_BAD_SHAPE (N, slots_per_token, n_slots, the offset limit).
+ *   gemlite_hip_experts_combine_query  validates and never launches or dereferences; works without a GPU */
+#define GEMLITE_EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN 64
+typedef struct gemlite_hip_experts_combine_args {
+    uint32_t struct_size;           /* sizeof(gemlite_hip_experts_combine_args), ABI guard */
+    int32_t dtype;                  /* of y and out: GEMLITE_DT_FP16 | GEMLITE_DT_BF16 */
+    int32_t ids_dtype;              /* GEMLITE_DT_INT32 | GEMLITE_DT_INT64 */
+    int32_t weights_dtype;          /* GEMLITE_DT_FP32 or dtype */
+    const void* y;                  /* device, n_slots rows of N */
+    const void* ids;                /* device, n_slots entries */
+    const void* weights;            /* device, n_slots entries in the order of ids */
+    void* out;                      /* device, n_slots / slots_per_token rows of N */
+    int64_t n_slots, n_experts, slots_per_token, N;
+    int64_t stride_y_slot, stride_out_token; /* elements */
+    int64_t reserved[2];
+} gemlite_hip_experts_combine_args;
+int gemlite_hip_experts_combine(const gemlite_hip_experts_combine_args* args, void* stream);
+int gemlite_hip_experts_combine_query(const gemlite_hip_experts_combine_args* args);
+
 /* Per-token dynamic activation quantisation: for each row m of x[M,K] (fp16/bf16/fp32)
  *   s[m] = max(amax(|x[m,:]|) / qmax, 1e-6) (fp32);  y = clamp(x / s, qmin, qmax);
  *   int8: round half away from zero;  fp8: round-to-nearest-even cast.
