@@ -20,7 +20,7 @@ from .core import (  # noqa: F401
     set_kernel_caching,
     set_packing_bitwidth,
 )
-from .experts import ExpertsRouting, GemLiteExperts, GemLiteExpertsMLP  # noqa: F401,E402
+from .experts import ExpertsRouter, ExpertsRouting, GemLiteExperts, GemLiteExpertsMLP, experts_topk  # noqa: F401,E402
 from . import helper  # noqa: F401,E402
 
 load_config = GemLiteLinear.load_config

@@ -278,6 +278,32 @@ class ExpertsCombineArgs(C.Structure):
     ]
 
 
+class ExpertsTopkArgs(C.Structure):
+    """struct gemlite_hip_experts_topk_args (field order/types must match the header)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("logits_dtype", C.c_int32),
+        ("ids_dtype", C.c_int32),
+        ("weights_dtype", C.c_int32),
+        ("scoring", C.c_int32),
+        ("renormalize", C.c_int32),
+        ("scale", C.c_float),
+        ("reserved0", C.c_int32),
+        ("logits", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("ids", C.c_void_p),
+        ("weights", C.c_void_p),
+        ("n_tokens", C.c_int64),
+        ("n_experts", C.c_int64),
+        ("top_k", C.c_int64),
+        ("stride_logits_token", C.c_int64),
+        ("reserved", C.c_int64 * 2),
+    ]
+
+
+EXPERTS_TOPK_MAX_EXPERTS = 1024  # GEMLITE_EXPERTS_TOPK_MAX_EXPERTS of the header
+EXPERTS_TOPK_SOFTMAX, EXPERTS_TOPK_SIGMOID = 0, 1  # gemlite_hip_experts_topk_args.scoring
 EXPERTS_ROWS_MAX_EXPERTS = 4096  # GEMLITE_EXPERTS_ROWS_MAX_EXPERTS of the header
 EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN = 64  # GEMLITE_EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN of the header
 EXPERTS_GLU, EXPERTS_COMBINE, ACT_SILU = 1, 2, 1  # gemlite_hip_experts_fused_args.epilogue / .activation
@@ -420,6 +446,10 @@ def load():
         lib.gemlite_hip_experts_combine.argtypes = [C.POINTER(ExpertsCombineArgs), C.c_void_p]
         lib.gemlite_hip_experts_combine_query.restype = C.c_int
         lib.gemlite_hip_experts_combine_query.argtypes = [C.POINTER(ExpertsCombineArgs)]
+        lib.gemlite_hip_experts_topk.restype = C.c_int
+        lib.gemlite_hip_experts_topk.argtypes = [C.POINTER(ExpertsTopkArgs), C.c_void_p]
+        lib.gemlite_hip_experts_topk_query.restype = C.c_int
+        lib.gemlite_hip_experts_topk_query.argtypes = [C.POINTER(ExpertsTopkArgs)]
         if lib.gemlite_hip_abi_version() != ABI_VERSION:
             raise GemliteHipError("libgemlite_hip.so ABI version mismatch; rebuild it")
         _lib = lib
@@ -451,6 +481,7 @@ EXPORTED_SYMBOLS = (
     "gemlite_hip_forward_experts_rows", "gemlite_hip_experts_rows_query",
     "gemlite_hip_forward_experts_rows_glu", "gemlite_hip_experts_rows_glu_query", "gemlite_hip_experts_rows_glu_per_block",
     "gemlite_hip_experts_combine", "gemlite_hip_experts_combine_query",
+    "gemlite_hip_experts_topk", "gemlite_hip_experts_topk_query",
 )
 
 

@@ -813,6 +813,70 @@ int gemlite_hip_experts_combine(const gemlite_hip_experts_combine_args* args, vo
     return launch(L.fn, L.grid, L.block, kargs, 0, (hipStream_t)stream);
 }
 
+// ---- the router's top-k (experts_topk.hip: experts_topk_kernel): one wave per token, four tokens per block ----
+struct ExpertsTopkLaunch {
+    ExpertsTopkArgs a;
+    const void* fn;
+    dim3 grid, block;
+};
+
+static int experts_topk_plan(const gemlite_hip_experts_topk_args* t, ExpertsTopkLaunch& L) {
+    if (!t || t->struct_size != sizeof(gemlite_hip_experts_topk_args)) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (!t->logits || !t->ids || !t->weights) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (t->n_tokens <= 0 || t->n_experts <= 0 || t->top_k <= 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (t->renormalize != 0 && t->renormalize != 1) return GEMLITE_ERR_BAD_ARGUMENT;
+    const int ldt = t->logits_dtype == GEMLITE_DT_FP16 ? 0 : t->logits_dtype == GEMLITE_DT_BF16 ? 1 : t->logits_dtype == GEMLITE_DT_FP32 ? 2 : -1;
+    const int wdt = t->weights_dtype == GEMLITE_DT_FP16 ? 0 : t->weights_dtype == GEMLITE_DT_BF16 ? 1 : t->weights_dtype == GEMLITE_DT_FP32 ? 2 : -1;
+    const bool ids64 = t->ids_dtype == GEMLITE_DT_INT64;
+    if (ldt < 0 || wdt < 0 || (!ids64 && t->ids_dtype != GEMLITE_DT_INT32)) return GEMLITE_ERR_UNSUPPORTED;
+    if (t->scoring != GEMLITE_EXPERTS_TOPK_SOFTMAX && t->scoring != GEMLITE_EXPERTS_TOPK_SIGMOID) return GEMLITE_ERR_UNSUPPORTED;
+    if (t->bias && t->scoring != GEMLITE_EXPERTS_TOPK_SIGMOID) return GEMLITE_ERR_UNSUPPORTED;
+    if (((uintptr_t)t->logits % (ldt == 2 ? 4 : 2)) != 0 || ((uintptr_t)t->ids % (ids64 ? 8 : 4)) != 0 ||
+        ((uintptr_t)t->weights % (wdt == 2 ? 4 : 2)) != 0 || ((uintptr_t)t->bias % 4) != 0)
+        return GEMLITE_ERR_BAD_ARGUMENT;
+    const int64_t k_max = t->n_experts < GEMLITE_EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN ? t->n_experts : GEMLITE_EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN;
+    if (t->n_experts > GEMLITE_EXPERTS_TOPK_MAX_EXPERTS || t->top_k > k_max || t->stride_logits_token < t->n_experts) return GEMLITE_ERR_BAD_SHAPE;
+    if (t->n_tokens > 0xFFFFFFFFll / t->top_k) return GEMLITE_ERR_BAD_SHAPE;             // n_tokens top_k < 2^32
+    if (t->stride_logits_token > (1ll << 62) / t->n_tokens) return GEMLITE_ERR_BAD_SHAPE;  // (byte offsets stay in 64 bits)
+    L.a.logits = t->logits;
+    L.a.bias = (const float*)t->bias;
+    L.a.ids = t->ids;
+    L.a.weights = t->weights;
+    L.a.stride = t->stride_logits_token;
+    L.a.n_tokens = (uint32_t)t->n_tokens;
+    L.a.E = (uint32_t)t->n_experts;
+    L.a.top_k = (uint32_t)t->top_k;
+    L.a.sigmoid = t->scoring == GEMLITE_EXPERTS_TOPK_SIGMOID;
+    L.a.renorm = (uint32_t)t->renormalize;
+    L.a.ids64 = ids64;
+    L.a.w_dt = (uint32_t)wdt;
+    L.a.scale = t->scale;
+    int per = 1;
+    while (64 * per < t->n_experts) per *= 2;
+    L.fn = experts_topk_fn(ldt, per);
+    if (!L.fn) return GEMLITE_ERR_UNSUPPORTED;
+    const int64_t threads = experts_topk_threads(), waves = threads / 64;
+    L.block = dim3((unsigned)threads, 1, 1);
+    L.grid = dim3((unsigned)((t->n_tokens + waves - 1) / waves), 1, 1);
+    return GEMLITE_OK;
+}
+
+int gemlite_hip_experts_topk_query(const gemlite_hip_experts_topk_args* args) {
+    ExpertsTopkLaunch L;
+    return experts_topk_plan(args, L);
+}
+
+int gemlite_hip_experts_topk(const gemlite_hip_experts_topk_args* args, void* stream) {
+    ExpertsTopkLaunch L;
+    const int v = experts_topk_plan(args, L);
+    if (v != GEMLITE_OK) return v;
+    int dev = 0;
+    const int dv = check_device(&dev);
+    if (dv != GEMLITE_OK) return dv;
+    void* kargs[] = {(void*)&L.a};
+    return launch(L.fn, L.grid, L.block, kargs, 0, (hipStream_t)stream);
+}
+
 int gemlite_hip_scale_activations_per_token(const void* x, void* y, float* scales, int64_t M, int64_t K,
                                             int64_t stride_xm, int32_t in_dtype, int32_t out_dtype, void* stream) {
     if (!x || !y || !scales || M <= 0 || K <= 0) return GEMLITE_ERR_BAD_ARGUMENT;

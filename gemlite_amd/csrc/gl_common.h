@@ -664,6 +664,17 @@ struct ExpertsCombineArgs {
     uint32_t n_experts, spt, N;
     uint32_t stride_y, stride_out;
 };
+// experts_topk_kernel (experts_topk.hip; gemlite_hip_experts_topk): one wave per token; the row stride in elements, 64-bit
+struct ExpertsTopkArgs {
+    const void* logits;
+    const float* bias;  // sigmoid only; nullptr: the key is the logit
+    void* ids;          // int32 or int64 (ids64)
+    void* weights;      // fp32, fp16 or bf16 (w_dt)
+    int64_t stride;
+    uint32_t n_tokens, E, top_k;
+    uint32_t sigmoid, renorm, ids64, w_dt;  // w_dt 0: fp16, 1: bf16, 2: fp32
+    float scale;
+};
 
 // silu of the GLU epilogues (gemv_w4_decode3_experts_fused_kernel, gemm_w4_rows_experts_glu_kernel): v / (1 + exp(-v)) in fp32.  Below
 // -88 exp(-v) leaves fp32 and the quotient is -0, while silu(v) = v exp(v) is a normal bf16 number down to about -92 and a subnormal

@@ -70,6 +70,8 @@ const void* gemm_wn_rows_experts_glu_fn(int tag, int mt, int spg, bool biased); 
 const void* experts_route_fn(bool ids64);  // experts_route.hip
 const void* experts_combine_fn(int tag, bool ids64, bool w32, bool wide);  // experts_combine.hip
 int experts_combine_threads();
+const void* experts_topk_fn(int ldt, int per_lane);  // experts_topk.hip; ldt 0: fp16, 1: bf16, 2: fp32; per_lane 1 / 2 / 4 / 8 / 16
+int experts_topk_threads();
 // the instantiations of gemm_wn_mma_kernel.inc, one translation unit per activation type and word width (gemm_wn_mma_*.hip)
 const void* mma_lookup_f16(int kind, int nbits, int mi, int xdt);
 const void* mma_lookup_bf16(int kind, int nbits, int mi, int xdt);

@@ -19,9 +19,13 @@ Batches: ``experts.route(ids)`` sorts the slots by expert on
 The batched MLP in four launches: ``experts.forward_batched_glu`` is the rows launch with SwiGLU in its epilogue
 (``gemlite_hip_forward_experts_rows_glu``), ``experts.combine_batched`` the routing-weight sum over a token's slots in one launch
 (``gemlite_hip_experts_combine``), ``GemLiteExpertsMLP.forward_batched_fused`` route + GLU + down + combine.  Opt-in as well.
+
+The router's top-k: ``experts_topk(logits, top_k, ...)`` / ``ExpertsRouter`` turn router logits into the ``topk_ids`` and
+``topk_weights`` all of the above begin with, in one launch (``gemlite_hip_experts_topk``); ``GemLiteExpertsMLP.forward_routed`` and
+``forward_batched_fused_routed`` put it in front of the MLP.  Opt-in as well.
 """
 import threading
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -507,6 +511,129 @@ def _experts_combine_fake(y, expert_ids, weights, n_experts):
     return torch.empty(tuple(expert_ids.shape[:-1]) + (y.shape[-1],), device=y.device, dtype=y.dtype)
 
 
+# ---- the router's top-k (gemlite_hip_experts_topk): logits -> (ids, weights) in one launch ----
+TOPK_SCORING = {"softmax": _hip.EXPERTS_TOPK_SOFTMAX, "sigmoid": _hip.EXPERTS_TOPK_SIGMOID}
+TOPK_DOMAIN = ("domain: fp16 / bf16 / fp32 logits [..., E] with 1 <= E <= %d, 1 <= top_k <= min(E, %d), int32 / int64 ids, "
+               "fp32 / fp16 / bf16 weights, an fp32 bias [E] with sigmoid scoring only"
+               % (_hip.EXPERTS_TOPK_MAX_EXPERTS, _hip.EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN))
+
+
+def _topk_check(logits: Tensor, top_k: int, scoring: str, bias: Optional[Tensor], ids_dtype, weights_dtype):
+    if scoring not in TOPK_SCORING:
+        raise ValueError(f"scoring is {scoring!r}: 'softmax' or 'sigmoid'")
+    if logits.dim() < 1:
+        raise ValueError("logits should be [..., E]")
+    E = logits.shape[-1]
+    if logits.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise NotImplementedError(f"logits are {logits.dtype}: float16, bfloat16 or float32")
+    if ids_dtype not in (torch.int32, torch.int64):
+        raise NotImplementedError(f"ids_dtype is {ids_dtype}: int32 or int64")
+    if weights_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"weights_dtype is {weights_dtype}: float32, float16 or bfloat16")
+    if not 1 <= E <= _hip.EXPERTS_TOPK_MAX_EXPERTS:
+        raise NotImplementedError(f"experts_topk: {E} experts ({TOPK_DOMAIN})")
+    if not 1 <= top_k <= min(E, _hip.EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN):
+        raise NotImplementedError(f"experts_topk: top_k={top_k} of {E} experts ({TOPK_DOMAIN})")
+    if bias is not None:
+        if scoring != "sigmoid":
+            raise ValueError("a selection bias goes with scoring='sigmoid' only")
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (E,):
+            raise ValueError(f"bias is {bias.dtype} {tuple(bias.shape)}: float32 ({E},)")
+
+
+def _topk_impl(logits: Tensor, top_k: int, scoring: str, renormalize: bool, scale: float, bias: Optional[Tensor], ids_dtype,
+               weights_dtype):
+    lib = _hip.load()
+    _topk_check(logits, top_k, scoring, bias, ids_dtype, weights_dtype)
+    tensors = ((logits, "logits"),) + (() if bias is None else ((bias, "bias"),))
+    for t, name in tensors:
+        _hip.require_gpu_tensor(t, name)
+    if bias is not None and bias.device != logits.device:
+        raise _hip.GemliteHipError(f"logits are on {logits.device}, bias on {bias.device}")
+    lead, E = tuple(logits.shape[:-1]), logits.shape[-1]
+    ids = torch.empty(lead + (top_k,), dtype=ids_dtype, device=logits.device)
+    weights = torch.empty(lead + (top_k,), dtype=weights_dtype, device=logits.device)
+    if ids.numel() == 0:
+        return ids, weights
+    l2 = _rows_of(logits)
+    if l2.shape[0] > 1 and l2.stride(0) < E:  # (an expanded row: the library takes row strides >= E)
+        l2 = l2.contiguous()
+    t = _hip.ExpertsTopkArgs()
+    t.struct_size = _hip.C.sizeof(_hip.ExpertsTopkArgs)
+    t.logits_dtype = TORCH_TO_DTYPE[l2.dtype].value
+    t.ids_dtype, t.weights_dtype = TORCH_TO_DTYPE[ids_dtype].value, TORCH_TO_DTYPE[weights_dtype].value
+    t.scoring, t.renormalize, t.scale = TOPK_SCORING[scoring], int(bool(renormalize)), float(scale)
+    t.logits, t.ids, t.weights = l2.data_ptr(), ids.data_ptr(), weights.data_ptr()
+    if bias is not None:
+        bias = bias.contiguous()
+        t.bias = bias.data_ptr()
+    t.n_tokens, t.n_experts, t.top_k = l2.shape[0], E, top_k
+    t.stride_logits_token = max(l2.stride(0), E)
+    with _hip.on_device(logits.device):
+        rc = lib.gemlite_hip_experts_topk(_hip.C.byref(t), _hip.current_stream_handle(logits.device))
+    if rc in (_hip.ERR_BAD_SHAPE, _hip.ERR_UNSUPPORTED):
+        raise NotImplementedError(f"gemlite_hip_experts_topk: logits {tuple(logits.shape)}, top_k={top_k}: {_hip.status_string(rc)} ({TOPK_DOMAIN})")
+    _hip.raise_for_status(rc, "gemlite_hip_experts_topk")
+    return ids, weights
+
+
+@torch.library.custom_op("gemlite::experts_topk", mutates_args=())
+def _experts_topk_op(logits: Tensor, top_k: int, scoring: str, renormalize: bool, scale: float, bias: Optional[Tensor],
+                     ids_dtype: torch.dtype, weights_dtype: torch.dtype) -> Tuple[Tensor, Tensor]:
+    return _topk_impl(logits, top_k, scoring, renormalize, scale, bias, ids_dtype, weights_dtype)
+
+
+@torch.library.register_fake("gemlite::experts_topk")
+def _experts_topk_fake(logits, top_k, scoring, renormalize, scale, bias, ids_dtype, weights_dtype):
+    _topk_check(logits, top_k, scoring, bias, ids_dtype, weights_dtype)
+    shape = tuple(logits.shape[:-1]) + (top_k,)
+    return torch.empty(shape, device=logits.device, dtype=ids_dtype), torch.empty(shape, device=logits.device, dtype=weights_dtype)
+
+
+def experts_topk(logits: Tensor, top_k: int, scoring: str = "softmax", renormalize: bool = True, scale: float = 1.0,
+                 bias: Optional[Tensor] = None, ids_dtype: torch.dtype = torch.int32, weights_dtype: torch.dtype = torch.float32):
+    """Router logits ``[..., E]`` -> ``(ids, weights)``, both ``[..., top_k]``, in ONE launch (``gemlite_hip_experts_topk``, DESIGN.md
+    §3.1.5): what ``GemLiteExperts`` / ``GemLiteExpertsMLP`` take as ``topk_ids`` and ``topk_weights``.  ``scoring='softmax'``: the weights
+    are the softmax of the logits over the selected experts (``renormalize``) or over all; ``'sigmoid'``: ``sigmoid(logit)``, selected by
+    ``sigmoid(logit) + bias`` where a ``bias`` (float32 ``[E]``) is given, divided by their sum with ``renormalize``; then times ``scale``.
+    Ids are distinct, in ``[0, E)`` and in descending order of the key (ties: the lower index) for every input, NaN rows included.
+    A non-unit inner stride, or leading dimensions without one row stride, are copied.  There is no CPU path."""
+    top_k = int(top_k)
+    if torch.compiler.is_compiling():
+        ids, weights = _experts_topk_op(logits, top_k, scoring, bool(renormalize), float(scale), bias, ids_dtype, weights_dtype)
+        return ids, weights
+    return _topk_impl(logits, top_k, scoring, renormalize, scale, bias, ids_dtype, weights_dtype)
+
+
+class ExpertsRouter(torch.nn.Module):
+    """``router(logits)`` -> ``(ids, weights)``: ``experts_topk`` with its settings kept; ``bias`` (float32 ``[E]``, sigmoid scoring) is a
+    buffer, so it moves and saves with the model."""
+
+    def __init__(self, top_k: int, scoring: str = "softmax", renormalize: bool = True, scale: float = 1.0, bias: Optional[Tensor] = None,
+                 weights_dtype: torch.dtype = torch.float32):
+        super().__init__()
+        if scoring not in TOPK_SCORING:
+            raise ValueError(f"scoring is {scoring!r}: 'softmax' or 'sigmoid'")
+        if not 1 <= int(top_k) <= _hip.EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN:
+            raise NotImplementedError(f"ExpertsRouter: top_k={top_k} ({TOPK_DOMAIN})")
+        if bias is not None:
+            if scoring != "sigmoid":
+                raise ValueError("a selection bias goes with scoring='sigmoid' only")
+            if bias.dim() != 1:
+                raise ValueError(f"bias is {tuple(bias.shape)}: one float32 entry per expert")
+            bias = bias.detach().to(torch.float32).contiguous()
+        self.top_k, self.scoring, self.renormalize, self.scale = int(top_k), scoring, bool(renormalize), float(scale)
+        self.weights_dtype = weights_dtype
+        self.register_buffer("bias", bias)
+
+    def forward(self, logits: Tensor):
+        return experts_topk(logits, self.top_k, self.scoring, self.renormalize, self.scale, self.bias, torch.int32, self.weights_dtype)
+
+    def extra_repr(self):
+        return (f"top_k={self.top_k}, scoring={self.scoring!r}, renormalize={self.renormalize}, scale={self.scale}, "
+                f"bias={self.bias is not None}, weights_dtype={self.weights_dtype}")
+
+
 class ExpertsRouting:
     """The work table of one set of expert ids (``GemLiteExperts.route``): the slots sorted into work blocks of at most
     ``rows_per_block`` slots of one expert, on the GPU.  Owns the workspace tensor; valid for every ``GemLiteExperts`` with ``n_experts``
@@ -855,6 +982,14 @@ class GemLiteExpertsMLP(torch.nn.Module):
 
     def forward(self, x: Tensor, topk_ids: Tensor, topk_weights: Tensor) -> Tensor:
         return self.down.forward_combine(self.gate_up.forward_glu(x, topk_ids), topk_ids, topk_weights)
+
+    def forward_routed(self, x: Tensor, logits: Tensor, router: "ExpertsRouter") -> Tensor:
+        """``self(x, *router(logits))``: router logits to ``[..., hidden]`` in three launches, no torch arithmetic between them."""
+        return self(x, *router(logits))
+
+    def forward_batched_fused_routed(self, x: Tensor, logits: Tensor, router: "ExpertsRouter") -> Tensor:
+        """``self.forward_batched_fused(x, *router(logits))``: five launches for a batch of tokens."""
+        return self.forward_batched_fused(x, *router(logits))
 
     def rows_per_block(self, n_slots: int) -> int:
         """The work-block size both stacks take: each one's own default where they agree, else the smaller (valid for both: only the

@@ -617,6 +617,50 @@ typedef struct gemlite_hip_experts_combine_args {
 int gemlite_hip_experts_combine(const gemlite_hip_experts_combine_args* args, void* stream);
 int gemlite_hip_experts_combine_query(const gemlite_hip_experts_combine_args* args);
 
+/*   gemlite_hip_experts_topk  the router's top-k in ONE launch (experts_topk_kernel): token t reads its n_experts logits at
+ *                             logits + t * stride_logits_token and writes top_k ids and top_k routing weights at ids / weights + t * top_k —
+ *                             what the experts launches above take as ids and weights.
+ *     Selection: top_k rounds of an arg-max over (key, index): the greater key wins, among equal keys (-0 == +0) the lower index, a NaN
+ *     key ranks above every number and NaNs tie among themselves by index.  Ids come out in selection order (descending key, like a
+ *     sorted top-k).  For EVERY bit pattern of logits and bias the top_k ids of a token are distinct and lie in [0, n_experts).
+ *     Arithmetic in fp32 (fp16 / bf16 logits convert exactly); a 16-bit weight is the fp32 weight rounded once.
+ *       GEMLITE_EXPERTS_TOPK_SOFTMAX  key = the logit (softmax is monotone: the selection is exact).  With m the largest logit and
+ *                                     p_j = exp(l_j - m): w_j = p_j / sum of p over the SELECTED (renormalize) or over ALL experts.
+ *       GEMLITE_EXPERTS_TOPK_SIGMOID  key = the logit without bias (exact), sigmoid(l_j) + bias_j with it (bias fp32 [n_experts], the
+ *                                     selection bias of DeepSeek-V3-style routers); w_j = sigmoid(l_j) = 1 / (1 + exp(-l_j)) never
+ *                                     includes the bias, and is divided by the sum of w over the selected when renormalize is set.
+ *     Both then multiply by `scale` (a multiply of its own).
+ *     Domain: 1 <= n_experts <= GEMLITE_EXPERTS_TOPK_MAX_EXPERTS; 1 <= top_k <= min(n_experts,
+ *     GEMLITE_EXPERTS_COMBINE_MAX_SLOTS_PER_TOKEN); logits fp16 / bf16 / fp32 with a unit inner stride, stride_logits_token >= n_experts,
+ *     element-aligned; ids int32 / int64; weights fp32 / fp16 / bf16; bias fp32, contiguous, SIGMOID only; n_tokens >= 1 and
+ *     n_tokens * top_k < 2^32.
+ *     GEMLITE_ERR_BAD_ARGUMENT (null or misaligned pointers, struct_size, non-positive counts, renormalize not 0 / 1),
+ *     GEMLITE_ERR_UNSUPPORTED (dtypes, scoring, a bias with SOFTMAX), GEMLITE_ERR_BAD_SHAPE (n_experts, top_k, the row stride, the
+ *     n_tokens * top_k limit).
+ *   gemlite_hip_experts_topk_query  validates and never launches or dereferences; works without a GPU */
+#define GEMLITE_EXPERTS_TOPK_MAX_EXPERTS 1024
+#define GEMLITE_EXPERTS_TOPK_SOFTMAX 0
+#define GEMLITE_EXPERTS_TOPK_SIGMOID 1
+typedef struct gemlite_hip_experts_topk_args {
+    uint32_t struct_size;           /* sizeof(gemlite_hip_experts_topk_args), ABI guard */
+    int32_t logits_dtype;           /* GEMLITE_DT_FP16 | GEMLITE_DT_BF16 | GEMLITE_DT_FP32 */
+    int32_t ids_dtype;              /* GEMLITE_DT_INT32 | GEMLITE_DT_INT64 */
+    int32_t weights_dtype;          /* GEMLITE_DT_FP32 | GEMLITE_DT_FP16 | GEMLITE_DT_BF16 */
+    int32_t scoring;                /* GEMLITE_EXPERTS_TOPK_SOFTMAX | GEMLITE_EXPERTS_TOPK_SIGMOID */
+    int32_t renormalize;            /* 0 | 1 */
+    float scale;                    /* the weights' last factor (1.f: none) */
+    int32_t reserved0;
+    const void* logits;             /* device, n_tokens rows of n_experts */
+    const void* bias;               /* device, n_experts fp32 entries, or NULL */
+    void* ids;                      /* device, n_tokens * top_k entries */
+    void* weights;                  /* device, n_tokens * top_k entries */
+    int64_t n_tokens, n_experts, top_k;
+    int64_t stride_logits_token;    /* elements */
+    int64_t reserved[2];
+} gemlite_hip_experts_topk_args;
+int gemlite_hip_experts_topk(const gemlite_hip_experts_topk_args* args, void* stream);
+int gemlite_hip_experts_topk_query(const gemlite_hip_experts_topk_args* args);
+
 /* Per-token dynamic activation quantisation: for each row m of x[M,K] (fp16/bf16/fp32)
  *   s[m] = max(amax(|x[m,:]|) / qmax, 1e-6) (fp32);  y = clamp(x / s, qmin, qmax);
  *   int8: round half away from zero;  fp8: round-to-nearest-even cast.
