@@ -429,7 +429,76 @@ struct ExpertsLaunch {
     ExpertsTail tail;
     const void* fn;
     dim3 grid;
+    // the MXFP4 branch (gemv_mx_experts.hip: gemv_mxw4_experts_kernel): its own argument block, block size and dynamic LDS
+    bool mx;
+    MxExpertsArgs mxa;
+    int mx_waves;
+    size_t mx_lds;
 };
+
+// MXFP4 experts, the block size: a 16-column tile holds 16 K / 256 units (128-byte lines) and a block of NW waves has 8 NW / COLS
+// 8-lane groups per column (COLS = 16, GLU: 32).  Measured (profiles/r29/probe_experts_mx.log, every cell with 4 / 8 / 16 waves forced):
+// 16 waves never win — a grid of many blocks pays each block's stage and barriers one after another, and small blocks overlap them
+// (Mixtral gate/up 8.6 / 9.3 / 12.9 us per slot, Qwen down 0.60 / 0.85 / 1.02) — and 8 waves are ahead of 4 only where the grid is at
+// most two rounds of the chip and a column has 8 .. 16 lines (Qwen gate/up 0.64 / 0.60, 4096^2 top_k 2 3.85 / 3.62).  That is the rule;
+// layer.tuning[2] = 4 / 8 / 16 forces a size (A/B runs: scripts/probe_experts_mx.py); the bits do not depend on it.
+static int mx_experts_waves(int64_t K, int64_t blocks, int forced) {
+    if (forced) return forced;
+    const int64_t lines = K / 256;
+    return blocks <= 512 && lines >= 8 && lines <= 16 ? 8 : 4;
+}
+
+// The MXFP4 member of the experts family: weight-only e2m1 codes, K-contiguous per column, e8m0 scales [K / 32][N], fp16 / bf16 x.
+// `glu`: plan the GLU form (experts_fused_plan asks again once it knows the epilogue).
+static int experts_plan_mx(const gemlite_hip_experts_args* e, ExpertsLaunch& L, bool glu) {
+    const gemlite_hip_forward_args& a = e->layer;
+    const bool f16 = a.input_dtype == GEMLITE_DT_MXFP16;
+    if (a.output_dtype != (f16 ? GEMLITE_DT_FP16 : GEMLITE_DT_BF16)) return GEMLITE_ERR_UNSUPPORTED;
+    if (a.W_nbits != 4 || a.elements_per_sample != 2 || a.w_pack_bits != 8 || a.group_size != 32) return GEMLITE_ERR_UNSUPPORTED;  // (fp8 weights)
+    if (a.meta_dtype != GEMLITE_DT_UINT8 && a.meta_dtype != GEMLITE_DT_E8M0) return GEMLITE_ERR_UNSUPPORTED;
+    if (a.channel_scale_mode != 0) return GEMLITE_ERR_UNSUPPORTED;
+    if (a.stride_xk != 1 || a.stride_wk != 1 || a.stride_on != 1 || a.stride_meta_n != 1) return GEMLITE_ERR_UNSUPPORTED;
+    if (a.M != 1 || a.N % 16 != 0 || a.K % 256 != 0 || (glu && a.N % 32 != 0)) return GEMLITE_ERR_BAD_SHAPE;
+    if (e->n_slots > 65535 || e->n_experts > 0x7FFFFFFF) return GEMLITE_ERR_BAD_SHAPE;
+    if (e->stride_expert_w < 0 || e->stride_expert_meta < 0 || e->stride_expert_bias < 0 || e->stride_x_row < 0 || e->stride_out_slot < 0 ||
+        a.stride_wn <= 0 || a.stride_meta_g <= 0)
+        return GEMLITE_ERR_BAD_ARGUMENT;
+    // every base a slot can produce keeps the alignment of the kernel's 16-byte requests: weight lines, x rows, scale rows; 2-byte bias
+    if (((uintptr_t)a.w_q % 16) != 0 || (a.stride_wn % 16) != 0 || (e->stride_expert_w % 16) != 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)a.x % 16) != 0 || (e->stride_x_row % 8) != 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)a.scales % 16) != 0 || (a.stride_meta_g % 16) != 0 || (e->stride_expert_meta % 16) != 0) return GEMLITE_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)a.out % 2) != 0 || (e->bias && (((uintptr_t)e->bias % 2) != 0 || (e->stride_expert_bias % 2) != 0))) return GEMLITE_ERR_BAD_ARGUMENT;
+    const int forced = a.tuning[2];
+    if (forced != 0 && forced != 4 && forced != 8 && forced != 16) return GEMLITE_ERR_BAD_ARGUMENT;
+    // 32-bit byte offsets inside one expert: the last weight line, the last scale row
+    if ((a.N - 1) * a.stride_wn + a.K / 2 >= (1ll << 32) || (a.K / 32 - 1) * a.stride_meta_g + a.N >= (1ll << 32)) return GEMLITE_ERR_BAD_SHAPE;
+    L.mx_lds = gemv_mxw4_experts_lds_bytes(a.K, glu);
+    if (L.mx_lds > 65536) return GEMLITE_ERR_BAD_SHAPE;  // the x row and the scale stage of one block
+
+    L.mx = true;
+    L.mx_waves = mx_experts_waves(a.K, (glu ? a.N / 32 : a.N / 16) * e->n_slots, forced);
+    L.mxa.w = (const char*)a.w_q;
+    L.mxa.x = (const char*)a.x;
+    L.mxa.s = (const char*)a.scales;
+    L.mxa.out = (uint16_t*)a.out;
+    L.mxa.K = (uint32_t)a.K;
+    L.mxa.stride_wn = (uint32_t)a.stride_wn;
+    L.mxa.stride_sg = (uint32_t)a.stride_meta_g;
+    L.mxa.half_tiles = glu ? (uint32_t)(a.N / 32) : 0u;
+    ExpertsTail& t = L.mxa.tail;
+    t.ids = e->ids;
+    t.bias = (const uint16_t*)e->bias;
+    t.stride_w = e->stride_expert_w;
+    t.stride_meta = e->stride_expert_meta;
+    t.stride_bias = e->stride_expert_bias;
+    t.stride_x = e->stride_x_row * 2;
+    t.stride_out = e->stride_out_slot;
+    t.n_experts = (uint32_t)e->n_experts;
+    t.slots_per_x_row = (uint32_t)(e->slots_per_x_row > 65536 ? 65536 : e->slots_per_x_row);
+    L.fn = gemv_mxw4_experts_fn(f16 ? 0 : 1, glu ? GEMLITE_EXPERTS_GLU : 0, e->bias != nullptr, e->ids_dtype == GEMLITE_DT_INT64, L.mx_waves);
+    L.grid = dim3((unsigned)(glu ? a.N / 32 : a.N / 16), (unsigned)e->n_slots, 1);
+    return GEMLITE_OK;
+}
 
 static int experts_plan(const gemlite_hip_experts_args* e, ExpertsLaunch& L) {
     if (!e || e->struct_size != sizeof(gemlite_hip_experts_args)) return GEMLITE_ERR_BAD_ARGUMENT;
@@ -438,6 +507,8 @@ static int experts_plan(const gemlite_hip_experts_args* e, ExpertsLaunch& L) {
     if (v != GEMLITE_OK) return v;
     if (!e->ids || e->n_slots <= 0 || e->n_experts <= 0 || e->slots_per_x_row <= 0) return GEMLITE_ERR_BAD_ARGUMENT;
     if (e->ids_dtype != GEMLITE_DT_INT32 && e->ids_dtype != GEMLITE_DT_INT64) return GEMLITE_ERR_UNSUPPORTED;
+    L.mx = false;
+    if (a.input_dtype == GEMLITE_DT_MXFP16 || a.input_dtype == GEMLITE_DT_MXBF16) return experts_plan_mx(e, L, false);
     const bool f16 = a.input_dtype == GEMLITE_DT_FP16;
     if ((!f16 && a.input_dtype != GEMLITE_DT_BF16) || a.output_dtype != a.input_dtype) return GEMLITE_ERR_UNSUPPORTED;
     if (a.W_nbits != 4 || a.elements_per_sample != 8 || a.w_pack_bits != 32) return GEMLITE_ERR_UNSUPPORTED;
@@ -503,6 +574,10 @@ int gemlite_hip_forward_experts(const gemlite_hip_experts_args* args, void* stre
     int dev = 0;
     const int dv = check_device(&dev);
     if (dv != GEMLITE_OK) return dv;
+    if (L.mx) {
+        void* margs[] = {(void*)&L.mxa};
+        return launch(L.fn, L.grid, dim3(64 * L.mx_waves, 1, 1), margs, L.mx_lds, (hipStream_t)stream);
+    }
     Decode3Args& d = L.d3;
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                      (void*)&d.nch_total, (void*)&d.modes, (void*)&L.tail};
@@ -524,6 +599,15 @@ static int experts_fused_plan(const gemlite_hip_experts_fused_args* f, ExpertsFu
     const int v = experts_plan(&f->experts, L.base);
     if (v != GEMLITE_OK) return v;
     const gemlite_hip_experts_args& e = f->experts;
+    if (L.base.mx) {  // MXFP4 experts: the GLU form of gemv_mxw4_experts_kernel; the COMBINE epilogue is not fused (gemlite_hip_experts_combine)
+        if (f->epilogue != GEMLITE_EXPERTS_GLU) return GEMLITE_ERR_UNSUPPORTED;
+        if (f->activation != GEMLITE_ACT_SILU) return GEMLITE_ERR_UNSUPPORTED;
+        const int vg = experts_plan_mx(&e, L.base, true);
+        if (vg != GEMLITE_OK) return vg;
+        L.fn = L.base.fn;
+        L.grid = L.base.grid;
+        return GEMLITE_OK;
+    }
     const int64_t tiles = e.layer.N / 16;
     L.tail.e = L.base.tail;
     L.tail.weights = nullptr;
@@ -568,6 +652,10 @@ int gemlite_hip_forward_experts_fused(const gemlite_hip_experts_fused_args* args
     int dev = 0;
     const int dv = check_device(&dev);
     if (dv != GEMLITE_OK) return dv;
+    if (L.base.mx) {
+        void* margs[] = {(void*)&L.base.mxa};
+        return launch(L.fn, L.grid, dim3(64 * L.base.mx_waves, 1, 1), margs, L.base.mx_lds, (hipStream_t)stream);
+    }
     Decode3Args& d = L.base.d3;
     void* kargs[] = {(void*)&d.w, (void*)&d.x, (void*)&d.s, (void*)&d.z, (void*)&d.out, (void*)&d.sw4, (void*)&d.mstride2,
                      (void*)&d.nch_total, (void*)&d.modes, (void*)&L.tail};
@@ -610,6 +698,7 @@ static int experts_rows_plan(const gemlite_hip_experts_rows_args* r, ExpertsRows
     if (!r || r->struct_size != sizeof(gemlite_hip_experts_rows_args)) return GEMLITE_ERR_BAD_ARGUMENT;
     const int v = experts_plan(&r->experts, L.base);
     if (v != GEMLITE_OK) return v;
+    if (L.base.mx) return GEMLITE_ERR_UNSUPPORTED;  // (MXFP4 experts have the decode launches only)
     const gemlite_hip_experts_args& e = r->experts;
     const gemlite_hip_forward_args& a = e.layer;
     // the rows kernel's own rules (plan_gemm_wn_rows): packed pairs of outputs, 32-bit offsets inside an expert, an x extent below 2^31

@@ -319,18 +319,7 @@ __device__ __forceinline__ void run_member(const char* wb, const char* xb, const
     }
 }
 
-// An experts launch, the prologue of a member.  The id of a slot is a SCALAR load (uniform per wave; int32 or int64 as the router wrote
-// it); an id outside [0, n_experts) is never turned into an address
-template <bool IDS64>
-__device__ __forceinline__ uint64_t expert_id(const ExpertsTail& t, uint32_t slot) {
-    // (int32: a negative id is >= 2^31 as unsigned and n_experts is below 2^31; int64: the high dword takes part in the comparison)
-    if constexpr (IDS64) {
-        return (uint64_t)((const int64_t*)t.ids)[slot];
-    } else {
-        return (uint64_t)(uint32_t)((const int32_t*)t.ids)[slot];
-    }
-}
-__device__ __forceinline__ bool expert_valid(const ExpertsTail& t, uint64_t e) { return e < (uint64_t)t.n_experts; }
+// An experts launch, the prologue of a member: expert_id / expert_valid / expert_bias live in gl_common.h (gemv_mx_experts.hip shares them)
 // Expert e's bases: base + e * stride in 64-bit scalar arithmetic (a stacked tensor is far beyond 4 GiB; the offsets inside an expert
 // stay 32-bit), and the x row of the slot
 __device__ __forceinline__ void expert_bases(const ExpertsTail& t, uint64_t e, uint32_t slot, uint32_t modes, const char*& wb,
@@ -339,9 +328,6 @@ __device__ __forceinline__ void expert_bases(const ExpertsTail& t, uint64_t e, u
     sp += e * (uint64_t)t.stride_meta;
     if (!(modes & M_ZSCALAR)) zp += e * (uint64_t)t.stride_meta;  // (one scalar zero is shared by all experts)
     xb += (uint64_t)(slot / t.slots_per_x_row) * (uint64_t)t.stride_x;
-}
-__device__ __forceinline__ const uint16_t* expert_bias(const ExpertsTail& t, uint64_t e) {
-    return (const uint16_t*)((const char*)t.bias + e * (uint64_t)t.stride_bias);
 }
 
 }  // namespace dec3

@@ -625,6 +625,34 @@ struct ExpertsTail {
     int64_t stride_x, stride_out;                // between x rows / output slots
     uint32_t n_experts, slots_per_x_row;
 };
+namespace dec3 {
+// An experts launch, the prologue of a member.  The id of a slot is a SCALAR load (uniform per wave; int32 or int64 as the router wrote
+// it); an id outside [0, n_experts) is never turned into an address
+template <bool IDS64>
+__device__ __forceinline__ uint64_t expert_id(const ExpertsTail& t, uint32_t slot) {
+    // (int32: a negative id is >= 2^31 as unsigned and n_experts is below 2^31; int64: the high dword takes part in the comparison)
+    if constexpr (IDS64) {
+        return (uint64_t)((const int64_t*)t.ids)[slot];
+    } else {
+        return (uint64_t)(uint32_t)((const int32_t*)t.ids)[slot];
+    }
+}
+__device__ __forceinline__ bool expert_valid(const ExpertsTail& t, uint64_t e) { return e < (uint64_t)t.n_experts; }
+__device__ __forceinline__ const uint16_t* expert_bias(const ExpertsTail& t, uint64_t e) {
+    return (const uint16_t*)((const char*)t.bias + e * (uint64_t)t.stride_bias);
+}
+}  // namespace dec3
+// gemv_mxw4_experts_kernel (gemv_mx_experts.hip; gemlite_hip_forward_experts / _fused on MXFP4 experts): expert 0's pointers, x row 0 and
+// slot 0 of the output, by value; the tail as above (stride_meta: between the experts' scale bytes).  Offsets inside one expert are 32-bit
+struct MxExpertsArgs {
+    const char *w, *x, *s;  // e2m1 codes [N][K / 2] bytes, the 16-bit x rows, e8m0 bytes [K / 32][N]
+    uint16_t* out;
+    uint32_t K;
+    uint32_t stride_wn;     // bytes between columns of the codes
+    uint32_t stride_sg;     // bytes between block rows of the scales
+    uint32_t half_tiles;    // GLU: I / 16, the tiles between a block's gate tile and its up tile
+    ExpertsTail tail;
+};
 // gemv_w4_decode3_experts_fused_kernel (gemlite_hip_forward_experts_fused): the experts tail, then what the epilogue needs.  stride_out is
 // between the output rows of the launch: slots (GLU) or tokens (COMBINE)
 struct ExpertsFusedTail {

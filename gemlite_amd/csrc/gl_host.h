@@ -63,6 +63,8 @@ const void* gemv_w4_decode3_bias_fn(int tag, bool nt);
 const void* gemv_w4_decode3_group_fn(int tag, bool biased, bool shared_x, int h, bool nt);
 const void* gemv_w4_decode3_experts_fn(int tag, bool biased, bool ids64);
 const void* gemv_w4_decode3_experts_fused_fn(int tag, int epilogue, bool biased, bool ids64);
+const void* gemv_mxw4_experts_fn(int tag, int epilogue, bool biased, bool ids64, int waves);  // gemv_mx_experts.hip
+size_t gemv_mxw4_experts_lds_bytes(int64_t K, bool glu);
 const void* gemm_wn_rows_group_fn(int tag, int mt, int spg, int nt, int bits, bool biased);  // gemm_wn_rows_group.hip: the grouped forms
 const void* gemm_wn_rows_experts_fn(int tag, int mt, int spg, bool biased);  // gemm_wn_rows_experts.hip
 size_t gemm_wn_rows_experts_lds_bytes();

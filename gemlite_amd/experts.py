@@ -8,6 +8,11 @@ by the kernel, so the call can be captured once and replayed with other ids.  An
 row of zeros.  Domain: DESIGN.md §3.1.3 — 4-bit weights in 32-bit words, fp16 / bf16, grouped scales / zeros, N % 16 == 0, K % 256 == 0.
 There is no slow path: layers outside the domain are refused by ``from_layers``.
 
+MXFP4 experts: ``A16W4_MXFP`` layers (e2m1 codes, one e8m0 scale per 32 k, fp16 / bf16 activations) stack the same way
+— ``[E, K/2, N]`` bytes, K-contiguous per column as the layers hold them — and ``forward`` / ``forward_glu`` run a kernel of their own
+(``gemv_mxw4_experts_kernel``).  ``forward_combine``, ``route`` and ``forward_batched*`` raise ``NotImplementedError`` for them;
+``GemLiteExpertsMLP.forward`` on MXFP4 stacks is three launches (GLU, down, ``combine_batched``).
+
 ``GemLiteExpertsMLP`` runs a whole expert MLP in two such launches (``gemlite_hip_forward_experts_fused``):
 ``gate_up.forward_glu`` stores ``silu(gate) * up`` of experts stacked ``[gate; up]`` along N, ``down.forward_combine`` stores the
 routing-weight sum over a token's slots.  Every member is rounded as its slot of ``forward``; the epilogues run in fp32 on those values.
@@ -35,6 +40,8 @@ from . import core
 from .dtypes import DTYPE_TO_TORCH, TORCH_TO_DTYPE, DType
 
 MAX_SLOTS = 65535  # of one launch (grid.y)
+MX_DTYPES = (DType.MXFP16.value, DType.MXBF16.value)  # A16W4_MXFP layers: MXFP4 weights under fp16 / bf16 activations
+MX_WAVES_OVERRIDE: Optional[int] = None  # 4 / 8 / 16: force the block size of the MXFP4 launches (A/B runs; the bits do not depend on it)
 
 _TEMPLATES: dict = {}
 _TEMPLATES_LOCK = threading.Lock()
@@ -80,7 +87,11 @@ def _call_args(x2: Tensor, ids: Tensor, out_ptr: int, bias: Optional[Tensor], te
     W_q, scales, zeros = tensor_args
     e = _static_args(W_q, scales, zeros, bias, meta_args)
     e.layer.x, e.layer.out = x2.data_ptr(), out_ptr
-    e.layer.input_dtype = TORCH_TO_DTYPE[x2.dtype].value
+    if meta_args[5] in MX_DTYPES:  # the layer's format pair names what x holds (forward() has checked x.dtype against it)
+        e.layer.input_dtype = meta_args[5]
+        e.layer.tuning[2] = MX_WAVES_OVERRIDE or 0
+    else:
+        e.layer.input_dtype = TORCH_TO_DTYPE[x2.dtype].value
     e.layer.stride_xm = x2.stride(0)
     e.ids = ids.data_ptr()
     e.ids_dtype = TORCH_TO_DTYPE[ids.dtype].value
@@ -703,6 +714,12 @@ class GemLiteExperts(torch.nn.Module):
         meta = cls._check_same(layers)
         first = layers[0]
         stack = lambda name: torch.stack([getattr(l, name).data for l in layers]).contiguous()  # noqa: E731
+        if meta[5] in MX_DTYPES:
+            W_q, scales = cls._stack_mx([[l] for l in layers])
+            zeros = first.zeros.data
+            bias = None if first.bias is None else stack("bias")
+            self = cls._from_stacked(meta, W_q, scales, zeros, bias, first.out_features, first.in_features)
+            return cls._del_orig(self, layers, del_orig)
         W_q = stack("W_q")
         scales = stack("scales") if first.scales.numel() > 0 else first.scales.data
         zeros = stack("zeros") if first.zeros.numel() > 1 else first.zeros.data
@@ -725,6 +742,11 @@ class GemLiteExperts(torch.nn.Module):
         first = gate_layers[0]
         pair = lambda name: torch.stack([torch.cat([getattr(g, name).data, getattr(u, name).data], dim=-1)  # noqa: E731
                                          for g, u in zip(gate_layers, up_layers)]).contiguous()
+        if meta[5] in MX_DTYPES:
+            W_q, scales = cls._stack_mx([[g, u] for g, u in zip(gate_layers, up_layers)])
+            bias = None if first.bias is None else pair("bias")
+            self = cls._from_stacked(meta, W_q, scales, first.zeros.data, bias, 2 * first.out_features, first.in_features)
+            return cls._del_orig(self, gate_layers + up_layers, del_orig)
         W_q = pair("W_q")
         scales = pair("scales") if first.scales.numel() > 0 else first.scales.data
         zeros = pair("zeros") if first.zeros.numel() > 1 else first.zeros.data
@@ -732,6 +754,28 @@ class GemLiteExperts(torch.nn.Module):
         self = cls._from_stacked(meta, W_q, scales, zeros, bias, 2 * first.out_features, first.in_features)
         if del_orig:
             for layer in gate_layers + up_layers:
+                layer.W_q = layer.scales = layer.zeros = layer.bias = None
+        return self
+
+    @staticmethod
+    def _stack_mx(groups: list):
+        """MXFP4 layers: `groups[e]` are the layers whose columns make up expert e, side by side along N.  A layer's W_q is a [K/2, N]
+        VIEW of [N, K/2] bytes and its scales a [N, K/32] view of [K/32, N] bytes (torch.stack(...).contiguous() on the views would
+        silently transpose the memory): the storage is stacked — N is the OUTER axis of the codes, the inner one of the scales — and the
+        views are kept: W_q [E, K/2, N] with strides (N K/2, 1, K/2), scales [E, N, K/32] with strides (N K/32, 1, N)."""
+        for layers in groups:
+            for l in layers:
+                if l.W_q.dim() != 2 or l.W_q.stride(0) != 1 or l.scales.dim() != 2 or l.scales.stride(0) != 1:
+                    raise NotImplementedError("GemLiteExperts: MXFP4 layers hold K-contiguous codes ([K/2, N] views of [N, K/2] bytes) and "
+                                              f"scales stored [K/32, N]; got W_q strides {l.W_q.stride()}, scales strides {l.scales.stride()}")
+        W_q = torch.stack([torch.cat([l.W_q.data.t() for l in layers], dim=0) for layers in groups]).contiguous()
+        scales = torch.stack([torch.cat([l.scales.data.t() for l in layers], dim=1) for layers in groups]).contiguous()
+        return W_q.transpose(1, 2), scales.transpose(1, 2)
+
+    @staticmethod
+    def _del_orig(self, layers: list, del_orig: bool):
+        if del_orig:
+            for layer in layers:
                 layer.W_q = layer.scales = layer.zeros = layer.bias = None
         return self
 
@@ -761,6 +805,8 @@ class GemLiteExperts(torch.nn.Module):
         """The library's own answer (gemlite_hip_experts_query plans and never launches, with or without a GPU), on the stacked tensors
         with stand-ins for x / out / ids; the most common refusals first, in words."""
         m = self._meta
+        if m[5] in MX_DTYPES:
+            return self._check_domain_mx(W_q, scales, zeros, bias)
         if m[0] or m[5] not in (DType.FP16.value, DType.BF16.value) or m[6] != m[5]:
             raise NotImplementedError("GemLiteExperts: weight-only layers with fp16 / bf16 activations and outputs of the same type")
         if m[1] != 4 or m[4] != 8 or W_q.dtype != torch.int32:
@@ -779,6 +825,35 @@ class GemLiteExperts(torch.nn.Module):
             raise NotImplementedError(f"GemLiteExperts: N={e.layer.N} K={e.layer.K} group_size={m[2]} W_group_mode={m[10]}: "
                                       f"{_hip.status_string(rc)} (domain: N % 16 == 0, K % 256 == 0, a power-of-two group_size >= 32, "
                                       "16-byte aligned contiguous weights)")
+
+    def _check_domain_mx(self, W_q: Tensor, scales: Tensor, zeros: Tensor, bias: Optional[Tensor]):
+        """_check_domain for MXFP4 experts (A16W4_MXFP layers): the same query, the refusals of the MX branch in words."""
+        m = self._meta
+        if m[0] or DTYPE_TO_TORCH[m[6]] != DTYPE_TO_TORCH[m[5]]:
+            raise NotImplementedError("GemLiteExperts: weight-only MXFP4 layers with fp16 / bf16 activations and outputs of the same type")
+        if m[1] != 4 or m[4] != 2 or W_q.dtype != torch.uint8:
+            raise NotImplementedError(f"GemLiteExperts: block-scaled experts take MXFP4 weights, e2m1 codes two per byte (W_nbits={m[1]}, "
+                                      f"{W_q.dtype}); MXFP8 weights have no experts launch")
+        e = _static_args(W_q, scales, zeros, bias, m)
+        e.layer.x = e.layer.out = e.ids = 0x1000
+        e.layer.stride_xm = e.stride_x_row = e.layer.K
+        e.ids_dtype = DType.INT32.value
+        e.n_slots = e.slots_per_x_row = 1
+        e.stride_out_slot = e.layer.N
+        rc = _hip.load().gemlite_hip_experts_query(_hip.C.byref(e))
+        if rc != _hip.OK:
+            raise NotImplementedError(f"GemLiteExperts: MXFP4 N={e.layer.N} K={e.layer.K}: {_hip.status_string(rc)} (domain: N % 16 == 0, "
+                                      "K % 256 == 0, K-contiguous codes, 16-byte aligned codes, scales and expert strides, the x row "
+                                      "and the scale stage of a block within 64 KiB of LDS)")
+
+    @property
+    def is_mx(self) -> bool:
+        return bool(self._meta) and self._meta[5] in MX_DTYPES
+
+    def _no_mx(self, what: str):
+        if self.is_mx:
+            raise NotImplementedError(f"GemLiteExperts.{what}: MXFP4 experts have the decode launches only (forward, forward_glu; "
+                                      "combine_batched for the routing-weight sum)")
 
     # ------------------------------------------------------------------------------- (de)serialise
     def load_state_dict(self, state_dict, strict=True, assign=False):
@@ -833,6 +908,7 @@ class GemLiteExperts(torch.nn.Module):
         """The work-block size R the library resolves for `n_slots` slots on these experts (None: its default); host only.
         ``glu=True``: the answer for ``forward_batched_glu``, whose two-tile blocks cap groups of 64 at 32 rows and have no form for
         groups of 32 (NotImplementedError)."""
+        self._no_mx("rows_per_block")
         if glu:
             return _resolve_rows_glu(self.bias, self.get_tensor_args(), self._meta, n_slots, rows_per_block)
         return _resolve_rows(self.bias, self.get_tensor_args(), self._meta, n_slots, rows_per_block)
@@ -840,6 +916,7 @@ class GemLiteExperts(torch.nn.Module):
     def route(self, expert_ids: Tensor, rows_per_block: Optional[int] = None) -> ExpertsRouting:
         """Sort the slots of ``expert_ids`` by expert into work blocks, in ONE launch that reads the ids on the GPU (no host
         synchronisation; capturable).  The result feeds ``forward_batched`` of every stack with as many experts that takes its R."""
+        self._no_mx("route")
         if expert_ids.dim() < 1:
             raise ValueError("expert_ids should be [..., top_k]")
         n_slots = expert_ids.numel()
@@ -856,6 +933,7 @@ class GemLiteExperts(torch.nn.Module):
         """-> ``[..., top_k, N]`` like ``forward``, for MORE THAN ONE token: every expert's weights stream once per work block of the
         routing through the MFMA rows kernel.  A valid slot is bit-identical to its row of that expert's own rows-kernel launch (NOT to
         ``forward``, whose decode kernel sums K in another order); a slot with an id outside [0, E) is a row of zeros."""
+        self._no_mx("forward_batched")
         self._check_x(x)
         if expert_ids.dim() < 1:
             raise ValueError("expert_ids should be [..., top_k]")
@@ -877,6 +955,7 @@ class GemLiteExperts(torch.nn.Module):
         """-> ``[..., top_k, N // 2]``: ``silu(y[..., :I]) * y[..., I:]`` of ``y = forward_batched(x, expert_ids, routing)`` — fp32 on the
         rounded values, one rounding — in the same one launch; no ``[..., top_k, N]`` intermediate exists.  Experts stacked
         ``[gate; up]`` along N (``from_gate_up``).  Out of the domain (N % 32, groups of 32, a routing above the GLU cap): NotImplementedError."""
+        self._no_mx("forward_batched_glu")
         self._check_x(x)
         if expert_ids.dim() < 1:
             raise ValueError("expert_ids should be [..., top_k]")
@@ -935,6 +1014,7 @@ class GemLiteExperts(torch.nn.Module):
 
     def forward_combine(self, x: Tensor, expert_ids: Tensor, weights: Tensor) -> Tensor:
         """-> ``[..., N]``: ``(forward(x, expert_ids) * weights.unsqueeze(-1)).sum(-2)`` with an fp32 sum, in the same one launch."""
+        self._no_mx("forward_combine")
         self._check_x(x)
         if expert_ids.dim() < 1:
             raise ValueError("expert_ids should be [..., top_k]")
@@ -947,6 +1027,7 @@ class GemLiteExperts(torch.nn.Module):
 class GemLiteExpertsMLP(torch.nn.Module):
     """The expert MLP of a mixture-of-experts layer in two launches: ``mlp(x, topk_ids, topk_weights)`` -> ``[..., hidden]`` is
     ``down.forward_combine(gate_up.forward_glu(x, ids), ids, w)``.  ``gate_up`` holds [gate; up] along N (GemLiteExperts.from_gate_up).
+    MXFP4 stacks: three launches, ``down.combine_batched(down(gate_up.forward_glu(x, ids), ids), ids, w)``; ``forward_batched*`` refuse.
     Without arguments: an empty module for ``load_state_dict``."""
 
     def __init__(self, gate_up: Optional[GemLiteExperts] = None, down: Optional[GemLiteExperts] = None):
@@ -981,6 +1062,9 @@ class GemLiteExpertsMLP(torch.nn.Module):
         self._check()
 
     def forward(self, x: Tensor, topk_ids: Tensor, topk_weights: Tensor) -> Tensor:
+        if self.down.is_mx:  # MXFP4 stacks: the COMBINE epilogue is not fused — GLU launch, down launch, the one-launch combine
+            h = self.gate_up.forward_glu(x, topk_ids)
+            return self.down.combine_batched(self.down(h, topk_ids), topk_ids, topk_weights)
         return self.down.forward_combine(self.gate_up.forward_glu(x, topk_ids), topk_ids, topk_weights)
 
     def forward_routed(self, x: Tensor, logits: Tensor, router: "ExpertsRouter") -> Tensor:

@@ -471,6 +471,18 @@ int gemlite_hip_capture_group_compatible_ex(const gemlite_hip_forward_args* a, c
  * Everything is validated before the launch: GEMLITE_ERR_BAD_ARGUMENT (null pointers, struct_size, non-positive counts, misaligned
  * or negative strides), GEMLITE_ERR_UNSUPPORTED (dtypes, bit width, modes, ids dtype, inner strides), GEMLITE_ERR_BAD_SHAPE (M, N, K, group
  * size, slot count, offset limits).  layer.matmul_type / tuning / workspace are not read.
+ * MXFP4 experts (gemv_mxw4_experts_kernel): layer.input_dtype GEMLITE_DT_MXFP16 / GEMLITE_DT_MXBF16 selects the block-scaled member of the
+ * family — weight-only e2m1 codes under fp16 / bf16 activations, `layer` filled as for an A16W4_MXFP layer: W_nbits 4, elements_per_sample 2,
+ * w_pack_bits 8, group_size 32, stride_wk == 1 and stride_wn the bytes between columns (K / 2 when packed densely), e8m0 scale bytes
+ * (meta_dtype UINT8 or E8M0) with stride_meta_n == 1 and stride_meta_g the bytes between block rows, output_dtype FP16 / BF16 to match,
+ * channel_scale_mode 0; zeros unused.  Slots, ids, bias, strides between experts and the zero rows of invalid ids as above.  Numerics:
+ * codes converted at scale 1.0, fp32 sums per 32-k block, acc = fma(2^e, block_sum, acc); a slot's bits depend on K, x and the expert
+ * only (not on its place in the grid or the block size); bias as above.  Domain: M = 1; N % 16 == 0; K % 256 == 0; 16-byte aligned w_q,
+ * x and scales; stride_wn, stride_meta_g, stride_expert_w and stride_expert_meta multiples of 16, stride_x_row of 8; 1 <= n_slots <= 65535;
+ * (N - 1) stride_wn + K / 2 and (K / 32 - 1) stride_meta_g + N below 2^32; the x row and the scale stage of a block within 64 KiB of LDS
+ * (2 K + 256 + K / 2 + 512 bytes; GLU: 2 K + 256 + K + 1024) — GEMLITE_ERR_BAD_SHAPE above.  layer.tuning[2] = 4 / 8 / 16 forces the waves
+ * per block (0: the library's rule; anything else GEMLITE_ERR_BAD_ARGUMENT); nothing else of tuning is read.  fp8 weights (MXFP8), NVFP4
+ * and fp8 / fp4 activations: GEMLITE_ERR_UNSUPPORTED.
  *   gemlite_hip_experts_query   validates and never launches or dereferences; works without a GPU */
 typedef struct gemlite_hip_experts_args {
     uint32_t struct_size;           /* sizeof(gemlite_hip_experts_args), ABI guard */
@@ -502,6 +514,9 @@ int gemlite_hip_experts_query(const gemlite_hip_experts_args* args);
  * Refusals beyond those of the nested request: GEMLITE_ERR_BAD_ARGUMENT (null struct, struct_size, COMBINE: null or misaligned weights,
  * slots_per_token <= 0), GEMLITE_ERR_UNSUPPORTED (epilogue, activation, weights_dtype), GEMLITE_ERR_BAD_SHAPE (GLU: N % 32 != 0; COMBINE:
  * slots_per_token > 16 or not a divisor of n_slots).  Fields of the other epilogue are not read.
+ * MXFP4 experts (see gemlite_hip_forward_experts): GEMLITE_EXPERTS_GLU runs the GLU form of gemv_mxw4_experts_kernel, grid (I / 16, slots),
+ * the members rounded as the plain launch rounds them; GEMLITE_EXPERTS_COMBINE returns GEMLITE_ERR_UNSUPPORTED (gemlite_hip_experts_combine
+ * sums the slots of the plain launch in one launch), and so do the batched entry points below.
  *   gemlite_hip_experts_fused_query   validates and never launches or dereferences; works without a GPU */
 #define GEMLITE_EXPERTS_GLU 1
 #define GEMLITE_EXPERTS_COMBINE 2
